@@ -3,6 +3,8 @@
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: starts its own N rank processes)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --full                           (adds every side measurement below)
+    python bench.py ... --dump-outputs DIR               (writes the last timed step's outputs as DIR/*.npy)
 
 A "step" is one pass of the hot path over one batch of synthetic sweeps that
 are already resident in HBM: HIP pillar voxelizer -> PPFeatureNet -> scatter ->
@@ -16,11 +18,15 @@ train.py:120-121): ONE launch per step (k_step) does the split stage of batch i,
 i-1, the order stage of batch i-2 and the emit stage of batch i-3 side by side, and the network consumes
 batch i-3 -- every step does one batch's worth of every stage (`--three-launch`: three dependent launches per step instead).
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the contract
+fields with
   roofline      the dominant hand-written kernel: k_step (= the whole voxelizer), algorithmic bytes per
                 launch / its mean duration, timed live with HIP events bound to the dispatch packets during
-                the timed steps; `three_launch`: the same forward with k_split, k_tile, k_emit as three
-                launches per step (their durations, their sum's fraction, k_emit's own)
+                the timed steps; traffic from the committed constant (profiles/emit_traffic.json)
+With `--full` the line also carries what takes runs of its own:
+  roofline      `three_launch`: the same forward with k_split, k_tile, k_emit as three launches per step
+                (their durations, their sum's fraction, k_emit's own); `traffic` measured live (rocprofv3 --pmc)
+  overlapped    the same forward with the voxelizer's launch on a second stream
   voxelizer_only   wall time per voxelizer call alone, pipelined and (`three_launch`) as three launches:
                 default (scrambled) order, `row_major_order`, `one_sweep_per_launch` (configs[3]'s per-GPU
                 shape), `c1_shapes` (configs[0]'s 100x100 grid on the GPU)
@@ -598,6 +604,28 @@ def ranks_min_max(ctx, us, bytes_per_launch, device=None, name="k_step_us"):
                     "duration / 8 TB/s: [min, max] over the ranks"}
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """`--dump-outputs`: the arrays one timed step handed its caller, as DIR/<name>.npy (f32; f64 stays f64).  Beyond
+    DUMP_BYTES in all, only the leading sweeps of the batch that fit are written -- the same sweeps in every run."""
+    host = {}
+    for name, t in arrays.items():
+        v = t.detach().cpu().numpy()
+        host[name] = v if v.dtype in (np.float32, np.float64) else v.astype(np.float32)
+    total = sum(v.nbytes for v in host.values())
+    if total > DUMP_BYTES:
+        batch = min(v.shape[0] for v in host.values())
+        keep = DUMP_BYTES * batch // total
+        if keep < 1:
+            raise SystemExit(f"--dump-outputs: one sweep's outputs alone exceed {DUMP_BYTES >> 20} MB")
+        host = {name: v[:keep] for name, v in host.items()}
+    os.makedirs(directory, exist_ok=True)
+    for name, v in host.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(v))
+
+
 def self_launch(n_ranks):
     """Start `n_ranks` rank processes of this script (one per GPU) under torch.distributed.run and
     wait for them.  Called before anything in this process has touched the GPU."""
@@ -655,7 +683,17 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (the contract); gloo only to rehearse the multi-rank "
                          "code path on a box with fewer GPUs than ranks (all ranks share device 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every side measurement (three-launch and overlapped forms, voxelizer_only, "
+                         "fused_feature_net, train_c3, stress_c5, reference_default, next_rows, dropin_host, "
+                         "cpu_baseline, live PMC traffic); without it the run sets up, warms up, times the "
+                         "headline steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step handed back (fwd: cls.npy, "
+                         "reg.npy; train: losses.npy) into DIR; rank 0 only")
     a = ap.parse_args()
+    if not a.full:
+        a.headline_only = True          # a plain run: the headline loop alone
     if a.headline_only:
         a.no_cpu_baseline = a.no_fused = a.no_train_leg = a.no_stress = a.no_dropin = a.no_next_rows = True
 
@@ -737,6 +775,8 @@ def main():
         return shard.reduce_loss_scalars(ctx, *losses, n_local=a.batch, device=dev)
 
     pipelined = a.mode == "fwd" and not a.three_launch
+    keep_last = a.dump_outputs is not None and ctx.rank == 0
+    last = [None]                       # what the latest step handed back (kept for --dump-outputs only)
 
     def step():
         if a.mode == "fwd":
@@ -745,8 +785,12 @@ def main():
             # network runs on batch i-3.  Every step does one batch's worth of every stage.
             step_no[0] += 1
             pts_ = point_sets[step_no[0] % len(point_sets)]
-            return pipe.forward_pipelined(pts_) if pipelined else pipe.forward(pts_)
-        return train_step(pipe, gts)
+            r_ = pipe.forward_pipelined(pts_) if pipelined else pipe.forward(pts_)
+        else:
+            r_ = train_step(pipe, gts)
+        if keep_last:
+            last[0] = r_
+        return r_
 
     def timed_loop(fn, steps):
         torch.cuda.synchronize()
@@ -765,6 +809,9 @@ def main():
         step()
     pipe.voxelizer.set_timing(min(a.steps, 4096))
     elapsed = timed_loop(step, a.steps)
+    if keep_last:
+        dump_outputs(a.dump_outputs, dict(zip(("cls", "reg"), last[0])) if a.mode == "fwd" else {"losses": last[0]})
+        last[0] = None
     kern_us, launches = kernel_means_us(pipe.voxelizer)
     pipe.voxelizer.set_timing(0)
     bytes_per_launch = cfg.algorithmic_bytes(N_POINTS) * a.batch

@@ -49,6 +49,26 @@ def test_dropin_record_arithmetic():
     assert b.dropin_record(0.1, 4.99, "x")["meets_50x"] is False
 
 
+def test_dump_outputs_float_arrays_within_64_mb(tmp_path):
+    """bench.py --dump-outputs: f32 (f64 kept), one DIR/<name>.npy per array, at most 64 MB in all -- beyond that the
+    leading sweeps of the batch that fit, the same ones every time"""
+    import numpy as np
+    import torch
+    b = _bench()
+    cls = torch.arange(10 * 2 * 1024 * 1024, dtype=torch.float32).reshape(10, 2, 1024, 1024)     # 80 MB
+    idx = torch.arange(30, dtype=torch.int64).reshape(10, 3)
+    b.dump_outputs(str(tmp_path / "big"), {"cls": cls, "idx": idx})
+    c, i = np.load(tmp_path / "big" / "cls.npy"), np.load(tmp_path / "big" / "idx.npy")
+    assert c.dtype == np.float32 and i.dtype == np.float32
+    assert c.nbytes + i.nbytes <= 64 << 20 and c.shape == (7, 2, 1024, 1024) and i.shape == (7, 3)
+    assert np.array_equal(c, cls[:7].numpy()) and np.array_equal(i, idx[:7].numpy().astype(np.float32))
+    small = torch.tensor([0.5, 1.5, 2.5, 4.5], dtype=torch.float64)
+    b.dump_outputs(str(tmp_path / "small"), {"losses": small})
+    s = np.load(tmp_path / "small" / "losses.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, small.numpy())
+    assert sorted(os.listdir(tmp_path / "small")) == ["losses.npy"]
+
+
 def test_per_rank_and_min_max_single_process():
     """the N = 1 forms of the per-rank helpers (the 2-rank forms run in tests/test_shard_gloo.py and, on the GPU, in
     tests/test_gpu_bench_ranks.py)"""

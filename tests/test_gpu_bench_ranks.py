@@ -28,7 +28,7 @@ def _free_port():
 @pytest.mark.parametrize("mode", ["fwd", "train"])
 def test_two_ranks_gloo_shared_device(gpu, mode, tmp_path):
     args = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
-            "--train-steps", "2", "--backend", "gloo", "--mode", mode, "--no-cpu-baseline"]
+            "--train-steps", "2", "--backend", "gloo", "--mode", mode, "--full", "--no-cpu-baseline"]
     if mode == "train":
         args.append("--no-stress")
     if mode == "fwd":
@@ -119,7 +119,7 @@ def test_four_ranks_gloo_shared_device_forward(gpu, tmp_path):
     per-N time budget.  (/root/reference train.py:88-89,120-121.)"""
     import time
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "2",
-           "--backend", "gloo", "--no-cpu-baseline", "--no-stress", "--no-train-leg"]
+           "--backend", "gloo", "--full", "--no-cpu-baseline", "--no-stress", "--no-train-leg"]
     env = dict(os.environ, TMPDIR=str(tmp_path))
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
@@ -155,7 +155,7 @@ def test_one_rank_over_rccl_runs_the_multi_rank_code_path(gpu, tmp_path):
     gloo rehearsals above cover world sizes 2 and 4).  The line must be the N = 1 line with a `collectives` record that
     names RCCL.  (/root/reference train.py:88-89,120-121.)"""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--train-steps", "2",
-           "--backend", "nccl", "--no-cpu-baseline", "--no-stress", "--no-dropin", "--no-next-rows", "--no-live-traffic",
+           "--backend", "nccl", "--full", "--no-cpu-baseline", "--no-stress", "--no-dropin", "--no-next-rows", "--no-live-traffic",
            "--no-fused"]
     env = dict(os.environ, TMPDIR=str(tmp_path), PP_FORCE_PROCESS_GROUP="1", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(_free_port()))

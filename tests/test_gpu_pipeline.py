@@ -62,7 +62,7 @@ def test_train_step_runs_and_is_finite(gpu):
 
 def test_bench_contract_line(gpu):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2",
-                          "--no-cpu-baseline", "--no-stress", "--no-train-leg"],
+                          "--full", "--no-cpu-baseline", "--no-stress", "--no-train-leg"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -110,6 +110,42 @@ def test_bench_contract_line(gpu):
     mi = dh["make_ious_call"]
     assert mi["anchors_changed_every_call_ms"] >= mi["hip_ms"] * 0.9
     assert abs(mi["anchors_changed_every_call_speedup"] - mi["cpu_ms"] / mi["anchors_changed_every_call_ms"]) < 0.02
+
+
+def test_bench_plain_line_and_dumped_outputs(gpu, tmp_path):
+    """A plain run (no --full): the contract line with the headline's roofline and none of the side legs; and
+    --dump-outputs writes the (cls, reg) the last timed step handed back, equal to a forward of that step's batch."""
+    import torch
+    from pp_amd import synth
+    from pp_amd.pipeline import PillarPipeline
+    from pp_amd.voxelizer import VoxelConfig
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    j = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+              "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
+        assert k in j, k
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["unit"] == "sweeps/s" and j["dtype"] == "f32"
+    assert abs(j["value"] - 3 * 4 / (j["ms_per_step"] * 3e-3)) < 1e-6 * j["value"]
+    assert j["roofline"]["kernel"].startswith("pp::k_step") and "three_launch" not in j["roofline"]
+    for k in ("overlapped", "voxelizer_only", "fused_feature_net", "train_c3", "stress_c5", "reference_default",
+              "next_rows", "dropin_host", "cpu_baseline"):
+        assert k not in j, k
+    assert sorted(os.listdir(d)) == ["cls.npy", "reg.npy"]
+    cl, rg = np.load(d / "cls.npy"), np.load(d / "reg.npy")
+    assert cl.dtype == rg.dtype == np.float32 and cl.shape == (4, 18, 250, 250) and rg.shape == (4, 16, 250, 250)
+    # the step's batch: the pipelined call k uses resident set k % 4 and returns the batch of call k - LAG; with
+    # warm-up 1 (+ LAG filling calls) and 3 timed steps the last timed step returns set (1 + 3) % 4 = 0, seeds 0..3
+    pipe = PillarPipeline(VoxelConfig.square(50.0, 0.2, 12000, 100), device=gpu, seed=0)
+    pipe.model.eval()
+    pts = torch.from_numpy(np.stack([synth.lidar_like(60000, 50.0, s) for s in range(4)])).to(gpu)
+    c_ref, r_ref = (t.cpu().numpy() for t in pipe.forward(pts))
+    for got, ref in ((cl, c_ref), (rg, r_ref)):
+        assert np.abs(got - ref).max() <= 2e-3 * max(1.0, float(np.abs(ref).max()))
 
 
 def test_fused_epilogue_equals_relu_batchnorm(gpu):

@@ -33,7 +33,7 @@ RD="--half 60 --P 24000 --N 200"
 SQ1="SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_LDS SQ_INSTS_VALU GRBM_GUI_ACTIVE"
 SQ2="SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VMEM SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT"
 # the driver's command and its headline loop alone (k_step's average there covers exactly the launches `roofline` times)
-stats bench python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-dropin
+stats bench python3 $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-dropin
 stats bench_headline python3 $R/bench.py --steps 50 --warmup 10 --headline-only
 pmc pmc_bench_headline_fetch FETCH_SIZE python3 $R/bench.py --steps 20 --warmup 5 --headline-only
 pmc pmc_bench_headline_write WRITE_SIZE python3 $R/bench.py --steps 20 --warmup 5 --headline-only

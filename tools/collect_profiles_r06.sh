@@ -31,7 +31,7 @@ C5="--n 200000 --half 100 --P 30000"
 C1="--step 1.0"
 RD="--half 60 --P 24000 --N 200"
 # the driver's command and its headline loop alone (k_step's average there covers exactly the launches `roofline` times)
-stats bench python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-dropin --no-live-traffic
+stats bench python3 $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-dropin --no-live-traffic
 stats bench_headline python3 $R/bench.py --steps 50 --warmup 10 --headline-only
 pmc pmc_bench_headline_fetch FETCH_SIZE python3 $R/bench.py --steps 20 --warmup 5 --headline-only
 pmc pmc_bench_headline_write WRITE_SIZE python3 $R/bench.py --steps 20 --warmup 5 --headline-only
