@@ -13,6 +13,7 @@ Layout (only what the hot path needs):
   model.py loss.py   PyTorch-ROCm counterpart of model/model.py, model/loss.py
   shard.py       one-process-per-GPU sweep sharding (torch.distributed / RCCL)
   synth.py       synthetic clouds and boxes
+  evaluate.py    device-resident validation mAP over 3D IoU thresholds (MapEvaluator)
 """
 from . import _lib  # noqa: F401
 from ._lib import ORDER_ROW_MAJOR, ORDER_SCRAMBLED, PPError, build  # noqa: F401

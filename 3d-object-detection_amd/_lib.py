@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("PP_HIP_LIB") or os.path.join(_HERE, "libpp_hip.so")
 SOURCES = [os.path.join(_HERE, "csrc", f)
-           for f in ("pp_runtime.hip", "pp_voxelize.hip", "pp_iou.hip", "pp_ingest.hip", "pp_decode.hip", "pp_epilogue.hip", "pp_pfn.hip", "pp_pfn_train.hip", "pp_bn_train.hip")]
+           for f in ("pp_runtime.hip", "pp_voxelize.hip", "pp_iou.hip", "pp_ingest.hip", "pp_decode.hip", "pp_epilogue.hip", "pp_pfn.hip", "pp_pfn_train.hip", "pp_bn_train.hip", "pp_eval.hip")]
 HEADERS = [os.path.join(_HERE, "csrc", "pp_common.h"), os.path.join(_ROOT, "include", "pp_hip.h")]
 
 PP_OK, PP_ERR_INDEX, PP_ERR_VALUE, PP_ERR_WINDING = 0, -2, -3, -4
@@ -28,6 +28,7 @@ EXPORTS = [
     "pp_voxelize_reserve", "pp_voxelize_dev", "pp_voxelize_step_dev", "pp_voxelize_step_pfn_canvas_dev", "pp_voxelize_step_kernel_name", "pp_voxelize_step_reset", "pp_subtract_mean_dev", "pp_voxelize_pfn_dev", "pp_voxelize_pfn_canvas_dev", "pp_voxelize_pfn_canvas_reuse_dev", "pp_pfn_dense_dev", "pp_scatter_canvas_dev", "pp_pfn_train_stats_dev", "pp_pfn_train_backward_dev", "pp_create_pillars_f64", "pp_make_ious_f64",
     "pp_iou_check", "pp_make_ious_dev", "pp_assign_targets_dev", "pp_assign_targets_grid_dev", "pp_assign_targets_batch_dev", "pp_assign_targets_grid_batch_dev", "pp_ingest_dev", "pp_ingest_sweeps_dev", "pp_decode_dev", "pp_decode_strided_dev", "pp_decode_batch_dev", "pp_bias_relu_bn_dev", "pp_bias_relu_bn_nhwc_dev", "pp_relu_bn_train_fwd_dev", "pp_relu_bn_train_bwd_dev", "pp_ctx_set_timing",
     "pp_ctx_read_emit_ms", "pp_ctx_read_kernel_ms", "pp_voxelize_check", "pp_host_pool_selftest",
+    "pp_box3d_iou_dev", "pp_eval_match_batch_dev",
 ]
 
 
@@ -56,6 +57,17 @@ class DecodeParams(ctypes.Structure):
 class TargetParams(ctypes.Structure):
     _fields_ = [("pos_thresh", ctypes.c_double), ("canvas_height", ctypes.c_double),
                 ("num_classes", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+MAX_EVAL_THRESHOLDS = 16    # pp_eval_params_t.thresholds
+
+
+class EvalParams(ctypes.Structure):
+    """pp_eval_params_t: classes, IoU thresholds and the frame of the (canvas-space) ground truth."""
+    _fields_ = [("num_classes", ctypes.c_int32), ("n_thresholds", ctypes.c_int32),
+                ("thresholds", ctypes.c_double * MAX_EVAL_THRESHOLDS),
+                ("x_step", ctypes.c_double), ("y_step", ctypes.c_double),
+                ("x_min", ctypes.c_double), ("y_min", ctypes.c_double)]
 
 
 def build(force=False, verbose=False):
@@ -240,6 +252,9 @@ def _load(path):
                                         ctypes.POINTER(c_int)]
     L.pp_voxelize_check.argtypes = [vp, vp]
     L.pp_host_pool_selftest.argtypes = [c_int, c_int, c_int]
+    L.pp_box3d_iou_dev.argtypes = [vp, vp, i64, vp, i64, vp, vp]
+    L.pp_eval_match_batch_dev.argtypes = [vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, pi32, vp, vp, vp, vp,
+                                          ctypes.POINTER(EvalParams), vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("pp_last_error", "pp_version", "pp_ctx_destroy"):

@@ -547,6 +547,58 @@ int pp_voxelize_check(pp_ctx_t *ctx, void *stream);
  * One context per HIP stream: calls on one context must be stream-ordered.
  */
 
+/*
+ * Validation mAP over 3D IoU thresholds: the matching step of the metric the
+ * reference takes from the lyft SDK (evaluate.py:247-278, get_average_precisions; train.py:175-196).
+ * The SDK is absent; its semantics are restated from recall, not pinned.
+ *
+ * pp_box3d_iou_dev: dense 3D IoU of car-space boxes, contiguous f64 device arrays
+ *   a_dev [Na][7], b_dev [Nb][7]: x,y,z (centre), w,l,h, yaw -- footprint a rectangle with length l
+ *   along the yaw direction and width w across it; out_dev [Na][Nb] f64:
+ *   clip(area(footprint_a ∩ footprint_b) * z-overlap / (w_a l_a h_a + w_b l_b h_b - that), 0, 1)
+ *   (Box3D.get_iou).  Limits (PP_ERR_VALUE beyond): 0 <= Na, Nb <= 2^24, Na*Nb <= 2^32.
+ *
+ * pp_eval_match_batch_dev: TP / FP flags of a batch of samples, two launches on `stream`, no host
+ * sync.  Per sample b:
+ *   boxes_dev [batch][max_out][9] f64   postprocess.Detector's rows x,y,z,w,l,h,yaw,score,class
+ *                                       (car space, pp_decode_batch_dev's boxes_out)
+ *   count_dev [batch] int32 (device)    valid rows per sample; rows >= count are written invalid
+ *   g_counts  [batch] int32 (HOST)      ground-truth boxes per sample
+ *   g_centers [T][3] g_wlh [T][3] g_yaw [T] f64, g_class [T] int32 (device, T = sum of g_counts,
+ *                                       the samples concatenated): CANVAS-space boxes, moved to car
+ *                                       space here as move_box_to_car_space(image=False) does
+ *                                       (evaluate.py:91-125) -- the slices at 11T / 14T / 17T / 18T
+ *                                       (f64 elements) of TargetAssigner.upload_batch's buffer
+ * Outputs [batch][max_out] (invalid rows: tp 0, max_iou -1, argmax -1):
+ *   max_iou_out f64, argmax_out int32   the best IoU over the sample's GT of the row's class and its
+ *                                       index in the sample's GT list (first index on ties); -1 / -1
+ *                                       when the sample has no GT of that class
+ *   tp_mask_out uint16                  bit t: the row is a TP at thresholds[t] -- in the order
+ *                                       (score desc, row asc), a row is a TP iff max_iou > t (strict)
+ *                                       and its argmax GT was not taken by an earlier TP; no fall-back
+ *                                       to the second-best GT (recall_precision)
+ *   gt_per_class_out [batch][num_classes] int32: the sample's GT per class
+ * Classes outside 0..num_classes-1 never match and are not counted.
+ * Limits (PP_ERR_VALUE beyond): 1 <= batch <= PP_MAX_BATCH, 1 <= max_out <= 1024,
+ *   1..32 classes, 1..16 thresholds, 0..65535 GT per sample.
+ */
+typedef struct pp_eval_params {
+  int32_t num_classes;     /* cfg.DATA.NUM_CLASSES, config.py:97                       */
+  int32_t n_thresholds;
+  double thresholds[16];   /* cfg.DATA.VAL_THRESH_LIST: np.arange(.5, 1., .05)         */
+  double x_step, y_step;   /* the GT frame: cfg.DATA.X_STEP / Y_STEP, X_MIN / Y_MIN    */
+  double x_min, y_min;
+} pp_eval_params_t;
+
+int pp_box3d_iou_dev(pp_ctx_t *ctx, void *stream, int64_t Na, const double *a_dev, int64_t Nb,
+                     const double *b_dev, double *out_dev);
+int pp_eval_match_batch_dev(pp_ctx_t *ctx, void *stream, int32_t batch, const double *boxes_dev,
+                            int32_t max_out, const int32_t *count_dev, const int32_t *g_counts,
+                            const double *g_centers, const double *g_wlh, const double *g_yaw,
+                            const int32_t *g_class, const pp_eval_params_t *prm,
+                            uint16_t *tp_mask_out, double *max_iou_out, int32_t *argmax_out,
+                            int32_t *gt_per_class_out);
+
 /* Timing hooks for bench.py: with a ring of `slots` HIP event pairs per kernel
  * (slots = 0 disables), every pp_voxelize*_dev call brackets each of its three launches
  * (PP_KERNEL_SPLIT, PP_KERNEL_TILE, PP_KERNEL_EMIT) with an event pair bound to the dispatch
