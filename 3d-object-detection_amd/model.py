@@ -112,6 +112,45 @@ def _weight_like(x, weight, cache):
     return cache.get((weight,), lambda: weight.detach().contiguous(memory_format=torch.channels_last))
 
 
+#: Winograd F(2x2,3x3) filter transform G (U = G g G^T)
+_WINO_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
+
+
+def _wino_filter(w):
+    """Conv weight [Cout,Cin,3,3] -> U = G g G^T in f64, rounded once to f32, in the layout of
+    pp_conv3x3_wino_nhwc_dev: [16][Cin/8][2][Cout][4] (a chunk of 8 input channels is one
+    contiguous copy into the kernel's LDS image)."""
+    co, ci = w.shape[:2]
+    G = torch.tensor(_WINO_G, dtype=torch.float64, device=w.device)
+    u = torch.einsum("ik,abkl,jl->ijba", G, w.detach().double(), G)        # [4,4,Cin,Cout]
+    return u.reshape(16, ci // 8, 2, 4, co).permute(0, 1, 2, 4, 3).float().contiguous()
+
+
+def _wino_ok(module, conv, x, transposed=False):
+    """The fused Winograd kernel takes this layer: 3x3, stride 1, padding 1 (ConvTranspose: no
+    output padding), a dense 16-byte aligned channels-last input, Cin % 8 == 0, Cout % 64 == 0."""
+    return (module.winograd and _is_nhwc(x) and x.data_ptr() % 16 == 0
+            and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1)
+            and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.groups == 1
+            and (not transposed or tuple(conv.output_padding) == (0, 0))
+            and x.shape[1] == conv.in_channels and conv.in_channels % 8 == 0 and conv.out_channels % 64 == 0)
+
+
+def _conv_wino(x, u, table, cout, out=None, channel_offset=0):
+    """pp_conv3x3_wino_nhwc_dev: conv + bias/ReLU/BatchNorm of ``x`` (NHWC) into a new channels-last
+    tensor, or into channels [channel_offset, +cout) of the channels-last ``out``."""
+    B, C, H, W = x.shape
+    dev = x.device
+    if out is None:
+        out = torch.empty((B, cout, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+    rc = _lib.lib().pp_conv3x3_wino_nhwc_dev(
+        _hip_ctx(dev).handle, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
+        ctypes.c_void_p(x.data_ptr()), B, H, W, C, ctypes.c_void_p(u.data_ptr()), cout,
+        ctypes.c_void_p(table.data_ptr()), ctypes.c_void_p(out.data_ptr()), out.shape[1], int(channel_offset))
+    _lib.check(rc, "pp_conv3x3_wino_nhwc_dev")
+    return out
+
+
 def _use_fused_epilogue(module, x):
     # the epilogue kernels work in place through raw pointers: autograd never sees them, so
     # they are for no-grad inference only (eval-mode fine-tuning / saliency take the modules)
@@ -401,6 +440,10 @@ class PPDownBlock(nn.Module):
         self.fused_train = True
         self._epi = [_Epilogue() for _ in range(num_layers)]
         self._wcl = [_LayoutCache() for _ in range(num_layers)]
+        #: ... and on that path the stride-1 layers as one fused Winograd F(2x2,3x3) kernel each
+        #: (csrc/pp_wino.hip: conv and epilogue in one pass, no MIOpen call)
+        self.winograd = True
+        self._wino = [_LayoutCache() for _ in range(num_layers)]
 
     def forward(self, x):
         if not _use_fused_epilogue(self, x):
@@ -413,6 +456,10 @@ class PPDownBlock(nn.Module):
             return self.block(x)
         for i, epi in enumerate(self._epi):
             conv, bn = self.block[3 * i], self.block[3 * i + 2]
+            if _wino_ok(self, conv, x):
+                u = self._wino[i].get((conv.weight,), lambda: _wino_filter(conv.weight))
+                x = _conv_wino(x, u, epi.table(conv.bias, bn), conv.out_channels)
+                continue
             x = F.conv2d(x, _weight_like(x, conv.weight, self._wcl[i]), None, conv.stride, conv.padding)
             x = epi(_dense(x), conv.bias, bn)
         return x
@@ -430,6 +477,8 @@ class PPUpBlock(nn.Module):
         self.fused_train = True
         self._epi = _Epilogue()
         self._wcl = _LayoutCache()
+        self.winograd = True
+        self._wino = _LayoutCache()
 
     def forward(self, x, out=None, channel_offset=0):
         if not _use_fused_epilogue(self, x):
@@ -439,6 +488,12 @@ class PPUpBlock(nn.Module):
                                 self.bn, conv_bias=ct.bias)
             return self.bn(F.relu(self.conv2d_t(x)))
         ct = self.conv2d_t
+        if _wino_ok(self, ct, x, transposed=True) and (
+                out is None or (_is_nhwc(out) and out.dtype == torch.float32 and out.shape[0] == x.shape[0]
+                                and out.shape[2:] == x.shape[2:])):
+            # stride 1: the transposed conv is a conv with w_conv[co][ci][kh][kw] = w_t[ci][co][2-kh][2-kw]
+            u = self._wino.get((ct.weight,), lambda: _wino_filter(ct.weight.transpose(0, 1).flip(2, 3)))
+            return _conv_wino(x, u, self._epi.table(ct.bias, self.bn), ct.out_channels, out, channel_offset)
         y = F.conv_transpose2d(x, _weight_like(x, ct.weight, self._wcl), None, ct.stride, ct.padding,
                                ct.output_padding)
         if out is not None and _is_nhwc(out) != _is_nhwc(y):

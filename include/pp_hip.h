@@ -498,6 +498,23 @@ int pp_bias_relu_bn_nhwc_dev(pp_ctx_t *ctx, void *stream, float *x_dev, int64_t 
                              int64_t y_channel_offset);
 
 /*
+ * A 3x3, stride-1, padding-1 convolution of NHWC f32 x[batch][height][width][in_channels] with
+ * the same epilogue as pp_bias_relu_bn_nhwc_dev (inference):
+ *   y = max(conv(x) + bias_c, 0) * scale_c + shift_c,   params_dev [out_channels][3]
+ * as Winograd F(2x2,3x3) on f32 MFMA.  u_dev is the transformed filter U = G g G^T in the
+ * layout [16][in_channels/8][2][out_channels][4]: U[4i+j][ci][co] (i, j = 0..3) at
+ * ((((4i+j)*(in_channels/8) + ci/8)*2 + (ci/4)%2)*out_channels + co)*4 + ci%4.
+ * y_dev: channels [y_channel_offset, +out_channels) of rows of y_channels floats per pixel, each
+ * written exactly once (no zero fill; other channels untouched).  in_channels a multiple of 8,
+ * out_channels a multiple of 64, x and u 16-byte aligned.  Launches only: no allocation, no
+ * synchronisation (graph-capturable); deterministic.
+ */
+int pp_conv3x3_wino_nhwc_dev(pp_ctx_t *ctx, void *stream, const float *x_dev, int batch, int height,
+                             int width, int in_channels, const float *u_dev, int out_channels,
+                             const float *params_dev, float *y_dev, int64_t y_channels,
+                             int64_t y_channel_offset);
+
+/*
  * The ReLU -> BatchNorm2d tail of the backbone blocks in TRAINING mode (model/model.py:76-84,
  * 105-109; BatchNorm with batch statistics), forward and backward, on NCHW f32 tensors:
  *   forward   y = gamma*(max(z,0) - mean)*invstd + beta with the batch mean / biased variance
