@@ -70,23 +70,29 @@ class EvalParams(ctypes.Structure):
                 ("x_min", ctypes.c_double), ("y_min", ctypes.c_double)]
 
 
-def build(force=False, verbose=False):
-    """Compile the HIP sources for gfx950 into libpp_hip.so (in-tree)."""
+def _compile(out, defines=(), force=False, verbose=False):
+    """hipcc the HIP sources for gfx950 into the shared library `out` unless it is newer than every source."""
     newest = max(os.path.getmtime(p) for p in SOURCES + HEADERS)
-    if not force and os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= newest:
-        return LIB_PATH
+    if not force and os.path.exists(out) and os.path.getmtime(out) >= newest:
+        return out
+    os.makedirs(os.path.dirname(out), exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     cmd = [hipcc, "-O3", "-std=c++17", "-fPIC", "-shared",
            "-ffp-contract=off",            # every f64 product/sum rounds separately
            "--offload-arch=gfx950",
            "-I" + os.path.join(_ROOT, "include"),
            "-Wl,-rpath,/opt/rocm/lib",
-           *SOURCES, "-o", LIB_PATH + ".tmp"]
+           *defines, *SOURCES, "-o", out + ".tmp"]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
-    os.replace(LIB_PATH + ".tmp", LIB_PATH)
-    return LIB_PATH
+    os.replace(out + ".tmp", out)
+    return out
+
+
+def build(force=False, verbose=False):
+    """Compile the HIP sources for gfx950 into libpp_hip.so (in-tree)."""
+    return _compile(LIB_PATH, force=force, verbose=verbose)
 
 
 VARIANTS = {
@@ -103,20 +109,7 @@ def variant_path(name):
 def build_variant(name, force=False, verbose=False):
     """Compile the whole library with the variant's defines into variants/libpp_hip_<name>.so (in-tree, git-ignored;
     travels to the GPU box like libpp_hip.so).  Never loaded by the product."""
-    out = variant_path(name)
-    newest = max(os.path.getmtime(p) for p in SOURCES + HEADERS)
-    if not force and os.path.exists(out) and os.path.getmtime(out) >= newest:
-        return out
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "--offload-arch=gfx950",
-           "-I" + os.path.join(_ROOT, "include"), "-Wl,-rpath,/opt/rocm/lib", *VARIANTS[name],
-           *SOURCES, "-o", out + ".tmp"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
-    os.replace(out + ".tmp", out)
-    return out
+    return _compile(variant_path(name), VARIANTS[name], force=force, verbose=verbose)
 
 
 def pybind_module_path():

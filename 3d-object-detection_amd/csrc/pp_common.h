@@ -166,8 +166,6 @@ struct pp_ctx {
   int step_next_slot = 1;
   hipStream_t step_stream = nullptr;  // the stream the batches in flight were submitted on
   bool sort_lds_armed = false;     // k_sort_runs' dynamic-LDS attribute set on this context's device
-  int force_tile_waves = 0;  // development knob: PP_TILE_WAVES in the environment
-  size_t dbg_stamps_off = 0, dbg_stamps_bytes = 0;  // PP_STAMPS builds (tools/lab)
   // host drop-in staging
   pp::DevBuf stage_in, stage_out, stage_out2;
   pp::PinBuf pin_in, pin_out, pin_meta;
@@ -179,8 +177,6 @@ struct pp_ctx {
   pp::DevBuf anchors_dev;
   int64_t anchors_A = -1;              // rows the mirror holds (-1: nothing)
   hipEvent_t chunk_ev[12] = {};        // one per chunk of the features' device-to-host copy (lazily created)
-  int dropin_last_n = 0;               // pp_create_pillars_f64: the previous call's point count and how many points
-  int64_t dropin_last_end = 0;         // it emitted -- sizes the feature copy that is sent ahead of the descriptors
   // IoU / target scratch
   pp::DevBuf iou_ws;
   // the layout the target scratch was last armed for: {A, gcap, batch, units, form, splits, cand_per_wg, off_best,

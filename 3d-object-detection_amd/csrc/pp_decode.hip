@@ -214,13 +214,6 @@ __device__ void decode_row(const DecodeArgs &d, int i, int a) {
   o[8] = (double)klass;
 }
 
-#ifdef PP_NMS_STAMPS
-__device__ unsigned long long g_nms_stamps[64 * 8];
-#define NMS_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.y == 0 && (c0 >> 8) < 64) g_nms_stamps[(c0 >> 8) * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define NMS_STAMP(k) do {} while (0)
-#endif
-
 // One workgroup per sample; chunks of kChunkN = 256 candidates in key order, four threads per candidate.
 __global__ __launch_bounds__(kNmsThreads) void k_nms(DecodeArgs d_) {
   const DecodeArgs d = sample_view(d_);
@@ -262,7 +255,6 @@ __global__ __launch_bounds__(kNmsThreads) void k_nms(DecodeArgs d_) {
   while (m2 < nruns * kChunkN) m2 <<= 1;
   for (int c0 = 0; c0 < M; c0 += kChunkN) {
     const int nk = s_nkept;
-    NMS_STAMP(0);
     u64 key;
     if (merging) {
       // the next 256 keys overall are among the next 256 of every run: sort those (run id
@@ -281,7 +273,6 @@ __global__ __launch_bounds__(kNmsThreads) void k_nms(DecodeArgs d_) {
     } else {
       key = (c0 + c < M) ? d.keys[c0 + c] : kSentinel;
     }
-    NMS_STAMP(1);
     const bool valid = key != kSentinel;
     const int a = (int)(key & 0xFFFFFull);
     NmsBox b = {0, 0, 0, 0, 0};
@@ -316,11 +307,9 @@ __global__ __launch_bounds__(kNmsThreads) void k_nms(DecodeArgs d_) {
         s_id[c] = a;
       }
     }
-    NMS_STAMP(2);
     s_mask[c][sub] = 0ull;
     if (t == kNmsThreads - 1) s_full = valid;       // the chunk's last candidate exists
     __syncthreads();
-    NMS_STAMP(3);
     // The members the kept list left alive, packed to the front (score order kept): the matrix and the
     // greedy pass then cost what the survivors cost -- 30 to 100 of 256 in all chunks but the first.
     int my_pos = -1;
@@ -374,9 +363,7 @@ __global__ __launch_bounds__(kNmsThreads) void k_nms(DecodeArgs d_) {
         }
       }
     }
-    NMS_STAMP(4);
     __syncthreads();
-    NMS_STAMP(5);
     if (t < 64) {
       // greedy pass in score order, by one wave: lane l holds the matrix row of member 64*w0 + l of
       // block w0; the walk over the block's alive members is a scalar loop (a row's own-block word
@@ -421,9 +408,7 @@ __global__ __launch_bounds__(kNmsThreads) void k_nms(DecodeArgs d_) {
         s_done = (n >= d.max_out) ? 1 : 0;
       }
     }
-    NMS_STAMP(6);
     __syncthreads();
-    NMS_STAMP(7);
     // enough boxes, or the candidates ran out inside this chunk.  Both flags go to registers and a
     // barrier follows: the next iteration's `s_full = valid` (thread 1023, before that iteration's
     // first barrier when nothing is merged) must not reach a wave that has not read this one yet --
@@ -567,10 +552,3 @@ extern "C" int pp_decode_dev(pp_ctx_t *ctx, void *stream_, const float *cls_dev,
   return pp_decode_strided_dev(ctx, stream_, cls_dev, reg_dev, hw, 1, hw, 1, a_centers, a_wlh, a_yaw,
                                a_xy, prm, boxes_out, kept_out, count_out);
 }
-
-#ifdef PP_NMS_STAMPS
-extern "C" int pp_debug_nms_stamps(unsigned long long *out, int n_words) {
-  if (hipDeviceSynchronize() != hipSuccess) return PP_ERR_HIP;
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(pp::g_nms_stamps), (size_t)n_words * 8) == hipSuccess ? PP_OK : PP_ERR_HIP;
-}
-#endif

@@ -23,7 +23,6 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
-#include <chrono>
 #include <cstdlib>
 
 namespace pp {
@@ -620,12 +619,6 @@ __device__ __forceinline__ void handoff_acquire_tail() {  // every wave of the l
 // reference's np.nonzero filter (box_utils.py:204-205).
 // IN_LDS: the column words live in LDS (G <= kForcedLds), else in the armed global scratch
 // (0 / all ones), which only this workgroup touches: atomics and sc1 loads meet in its XCD's L2.
-#ifdef PP_IOU_STAMPS
-__device__ unsigned long long g_iou_stamps[16 * 4096];
-#define IOU_STAMP(k) do { const unsigned wg_ = blockIdx.x * gridDim.y + blockIdx.y; if (threadIdx.x == 0 && wg_ < 4096) g_iou_stamps[wg_ * 16 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define IOU_STAMP(k) do {} while (0)
-#endif
 
 // n_fixed >= 0: the list has exactly that many slots, every one written by this launch (an unused one carries
 // the bits 0): the box-centric form, no counter to wait for
@@ -675,7 +668,6 @@ __device__ void targets_tail(const TargetArgs &t, TailLds &T, int n_fixed = -1) 
       e_bits[k] = ld_agent(&cand_at(t, e)->bits);
     }
   }
-  IOU_STAMP(11);
   if (gt_staged) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -704,7 +696,6 @@ __device__ void targets_tail(const TargetArgs &t, TailLds &T, int n_fixed = -1) 
     if (b != 0ull && b == cmax_ld(j)) atomicMin(cwin_at(j), (key & 0xFFFFFFFF00000000ull) | e);
   }
   sync();
-  IOU_STAMP(12);
   // colwin[j] <- {anchor ground truth j forces, entry}; anchor 0: none
   for (int j = tid; j < G; j += kTgtThreads) {
     const u64 w = (cmax_ld(j) != 0ull) ? cwin_ld(j) : 0ull;
@@ -718,7 +709,6 @@ __device__ void targets_tail(const TargetArgs &t, TailLds &T, int n_fixed = -1) 
     }
   }
   sync();
-  IOU_STAMP(13);
   // the regression row of the last ground truth forcing an anchor
   auto write_row = [&](int i, int j) {
     const Row9 row = make_target_dev(t, i, j);
@@ -857,7 +847,6 @@ __device__ void targets_tail(const TargetArgs &t, TailLds &T, int n_fixed = -1) 
     // Regression rows, one kind of value per wave (see target_quotient).  colmax[j] bit 63: a later
     // ground truth forces the same anchor and its row wins.
     __syncthreads();
-    IOU_STAMP(15);
     // wave 0: the three quotients of every row (lane = row * 3 + component), wave 1: the three
     // logarithms, wave 2: the sine, the orientation bit and the leading 1
     const int wv = tid >> 6, ln = tid & 63;
@@ -925,7 +914,6 @@ __device__ void targets_tail(const TargetArgs &t, TailLds &T, int n_fixed = -1) 
       if (!later) write_row(i, j);
     }
   }
-  IOU_STAMP(14);
   // re-arm the scratch words for the next call on this context
   __syncthreads();
   if (!IN_LDS)
@@ -942,13 +930,8 @@ __device__ void targets_tail(const TargetArgs &t, TailLds &T, int n_fixed = -1) 
 
 // MATRIX: make_ious (data/pillars.cpp:400-427) on the same gate / queue / clip machinery -- the
 // pairs past the gate are written into the host-zeroed [A][G] matrix, nothing else is computed.
-#ifdef PP_TGT_WAVES  // development knob (tools/lab): waves per SIMD the register allocation is held to
-#define PP_TGT_OCC __attribute__((amdgpu_waves_per_eu(PP_TGT_WAVES, PP_TGT_WAVES)))
-#else
-#define PP_TGT_OCC
-#endif
 template <bool MATRIX>
-__global__ __launch_bounds__(kTgtThreads) PP_TGT_OCC void k_targets(TargetArgs t, TargetBatch bt) {
+__global__ __launch_bounds__(kTgtThreads) void k_targets(TargetArgs t, TargetBatch bt) {
   // Batch launches are (sample, tile of 256 anchors): workgroups are dispatched x first, so the samples
   // advance side by side -- with the samples one after the other the last one's workgroups all started
   // late, its heavy ones last, and the launch ended ~10 us after everything else had drained.
@@ -974,7 +957,6 @@ __global__ __launch_bounds__(kTgtThreads) PP_TGT_OCC void k_targets(TargetArgs t
   const int64_t i0 = (int64_t)tile * kTgtThreads;
   const int64_t i = i0 + tid;
   const bool live = i < t.A;
-  IOU_STAMP(0);
   // The first chunk's ground truths and the type table are on their way while the arithmetic below
   // runs.  Every wave fetches the chunk's centres for itself (lane = ground truth): the "is any box
   // near this workgroup" decision below then needs no LDS and no barrier.
@@ -1107,7 +1089,6 @@ __global__ __launch_bounds__(kTgtThreads) PP_TGT_OCC void k_targets(TargetArgs t
     }
     if (tid < gn * 4) S.gk[tid >> 2][tid & 3] = pre_k;
     __syncthreads();
-    IOU_STAMP(1);
     // the chunk's ground truths near this workgroup (every wave works out the same mask)
     bool near = false;
     if (lane < gn) {
@@ -1144,7 +1125,6 @@ __global__ __launch_bounds__(kTgtThreads) PP_TGT_OCC void k_targets(TargetArgs t
       total += S.woff[w];
     }
     const int my_off = wave_base + inc - cnt;
-    IOU_STAMP(2);
     if (total == 0) continue;
     for (int wb = 0; wb < total; wb += kPairCap) {
       const int wn = min(kPairCap, total - wb);
@@ -1163,7 +1143,6 @@ __global__ __launch_bounds__(kTgtThreads) PP_TGT_OCC void k_targets(TargetArgs t
         }
       }
       __syncthreads();
-      IOU_STAMP(3);
       // clip: 32 groups of 8 lanes, one pair each per round
       // (a wave whose eight groups have no pair in this round sits it out: a round is ~500 instructions,
       // and a third of the wave-rounds were empty)
@@ -1171,7 +1150,6 @@ __global__ __launch_bounds__(kTgtThreads) PP_TGT_OCC void k_targets(TargetArgs t
       for (int r0 = 0; r0 < wn; r0 += kPairsPerRound)
         if (r0 + wv * (64 / kGroup) < wn) clip_round<1>(t, S, r0, wn, i0, tid, v, gbase, lds_types, bad);
       __syncthreads();
-      IOU_STAMP(4);
       if constexpr (MATRIX) {
         if (t.triples) {
           for (int q = tid; q < wn; q += kTgtThreads) {
@@ -1227,7 +1205,6 @@ __global__ __launch_bounds__(kTgtThreads) PP_TGT_OCC void k_targets(TargetArgs t
       last_gn = gn;
     }
   }
-  IOU_STAMP(5);
   if (bad) atomicOr(t.errflag, kErrWinding);
   if constexpr (MATRIX) return;
   // rows: positives of both targets, zero rows otherwise
@@ -1336,17 +1313,14 @@ __global__ __launch_bounds__(kTgtThreads) PP_TGT_OCC void k_targets(TargetArgs t
       for (int d = 0; d < 9; ++d) store_f32_sc1(&reg_dst[(int64_t)tid * 9 + d], S.rstage[tid * 9 + d]);
     }
   }
-  IOU_STAMP(6);
   if (t.G == 0) return;
   if (contrib || kStrictHandoff) {
     if (contrib && wv == 0) write_columns(last_j0, last_tb, last_base);
     // The last workgroup to get here finishes the job.  Every store above that the tail depends on
     // is write-through; drained per wave, then one agent-scope add per workgroup: the workgroup
     // whose add comes last reads the others' entries with sc1 loads and may overwrite their rows.
-    IOU_STAMP(7);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    IOU_STAMP(8);
     if (tid == 0) {
       handoff_release_lane0();
       tk = atomicAdd(my_ticket1, 1u);
@@ -1364,14 +1338,12 @@ __global__ __launch_bounds__(kTgtThreads) PP_TGT_OCC void k_targets(TargetArgs t
     S.is_last = last;
   }
   __syncthreads();
-  IOU_STAMP(9);
   if (!S.is_last) return;
   handoff_acquire_tail();
   if (t.G <= kForcedLds)
     targets_tail<true>(t, *reinterpret_cast<TailLds *>(smem));
   else
     targets_tail<false>(t, *reinterpret_cast<TailLds *>(smem));
-  IOU_STAMP(10);
 }
 
 // ------------------------------------------------------------------------- //
@@ -1399,10 +1371,7 @@ __global__ __launch_bounds__(kTgtThreads) PP_TGT_OCC void k_targets(TargetArgs t
 //               class and regression rows of the winners -- then k_targets' tail: column argmax, forced rows.
 // Results equal k_targets' bit for bit (same gate, same clip, same row expressions; tests run both forms
 // against each other and the oracle).
-#ifndef PP_CAND_PER_WG
-#define PP_CAND_PER_WG 64
-#endif
-constexpr int kCandPerWg = PP_CAND_PER_WG;   // candidate anchors per PAIR workgroup (<= 64): one wave gates, four clip
+constexpr int kCandPerWg = 64;  // candidate anchors per PAIR workgroup (<= 64): one wave gates, four clip
 static_assert(kCandPerWg >= 8 && kCandPerWg <= 64, "one lane of wave 0 per candidate");
 constexpr int kZeroWgs = 64;     // ZERO workgroups per sample (x 4 samples = a hipMemset-shaped grid)
 
@@ -1568,7 +1537,7 @@ __device__ void positives_tail(const TargetArgs &t, unsigned char *smem) {
 // The box-centric tail in its usual shape -- at most 64 boxes, 1024 list slots, 256 pairs above the threshold,
 // 63 classes -- which the caller knows BEFORE anything is loaded: the number of pairs above the threshold arrives with
 // the last ticket (the tickets count in 64 bits: workgroups done | the pairs they stored).
-// Round 5, what the stamps said about round 4's form at one sample per launch (tools/lab/gt_stamps.py): last ticket ->
+// Round 5, what the stamps said about round 4's form at one sample per launch (profiles/r05/NOTES.md): last ticket ->
 // entries in registers 2.0 us (18 dword loads per thread with the lanes 64 bytes apart: a wave-level load touched 64
 // lines and every line was asked for a dozen times), LDS phases 0.8, the forced rows' fetch and the drain in front of
 // it 1.2, end 0.4.  And what a first rebuild showed (every record's row kept in the registers of the lanes that
@@ -1637,7 +1606,6 @@ __device__ void tail_gt_fast(const TargetArgs &t, unsigned char *smem, int nslot
     F.colwin[tid] = ~0ull;
   }
   __syncthreads();
-  IOU_STAMP(11);
   // ---- phase 1: maxima (rows: per anchor through the hash table; columns: per box)
   const u64 pbits = (u64)pk[2] | ((u64)pk[3] << 32);
   int slot = -1;
@@ -1651,7 +1619,6 @@ __device__ void tail_gt_fast(const TargetArgs &t, unsigned char *smem, int nslot
     if (b != 0ull) atomicMax(&F.colmax[(int)ck[k][0]], b);
   }
   __syncthreads();
-  IOU_STAMP(12);
   // ---- phase 2: first box reaching a row's maximum; first anchor reaching a column's, and its list slot
   if (slot >= 0 && pbits == F.bits[slot]) atomicMin(&F.minj[slot], pk[1]);
 #pragma unroll
@@ -1661,7 +1628,6 @@ __device__ void tail_gt_fast(const TargetArgs &t, unsigned char *smem, int nslot
     if (b != 0ull && b == F.colmax[j]) atomicMin(&F.colwin[j], ((u64)ck[k][1] << 32) | (unsigned)(k * kTgtThreads + tid));
   }
   __syncthreads();
-  IOU_STAMP(13);
   // ---- forced rows (box_utils.py:199-205, 212-213, 223-228), wave 0, lane = box: the row is fetched from the slot the
   // column's argmax came in, and while it is on its way the boxes that force the same anchor meet in the hash table
   // (the classes of all of them, the last of them: its regression row wins) -- which also tells the positives
@@ -1682,7 +1648,6 @@ __device__ void tail_gt_fast(const TargetArgs &t, unsigned char *smem, int nslot
     }
   }
   __syncthreads();
-  IOU_STAMP(14);
   // ---- the positives' rows (box_utils.py:211, 219-221), from registers -- unless a box forces the anchor
   if (slot >= 0) {
     if (pbits == F.bits[slot] && pk[1] == F.minj[slot] && F.fmask[slot] == 0ull) {
@@ -1710,7 +1675,7 @@ __device__ void tail_gt_fast(const TargetArgs &t, unsigned char *smem, int nslot
   }
 }
 
-__global__ __launch_bounds__(kTgtThreads) PP_TGT_OCC void k_targets_gt(TargetArgs t, TargetBatch bt) {
+__global__ __launch_bounds__(kTgtThreads) void k_targets_gt(TargetArgs t, TargetBatch bt) {
   sample_view(t, bt, (int)blockIdx.x);
   __shared__ __align__(16) unsigned char smem[kTgtLdsBytes];
   TgtLds &S = *reinterpret_cast<TgtLds *>(smem);
@@ -1720,7 +1685,6 @@ __global__ __launch_bounds__(kTgtThreads) PP_TGT_OCC void k_targets_gt(TargetArg
   const unsigned u = blockIdx.y, n_units = (unsigned)kZeroWgs + (unsigned)G * (unsigned)nsp;
   if (u >= n_units) return;
   unsigned npos_wg = 0u;
-  IOU_STAMP(0);
   if (u < (unsigned)kZeroWgs) {
     zero_share(t.cls_targets, t.A * t.num_classes, (int)u, kZeroWgs, tid);
     zero_share(t.reg_targets, t.A * 9, (int)u, kZeroWgs, tid);
@@ -1787,7 +1751,6 @@ __global__ __launch_bounds__(kTgtThreads) PP_TGT_OCC void k_targets_gt(TargetArg
     unsigned col_anchor = ~0u;    // ... and the first anchor reaching it
     bool bad = false;
     const unsigned cpw = (unsigned)t.cand_per_wg;
-    IOU_STAMP(1);
     if (wv == 1) {  // the box into LDS slot 0 (the loads were issued at the top)
       if (lane < 8) reinterpret_cast<double *>(S.gk[0])[lane] = ld0;
       else if (lane < 15) S.gv7[lane - 8] = ld0;
@@ -1848,18 +1811,10 @@ __global__ __launch_bounds__(kTgtThreads) PP_TGT_OCC void k_targets_gt(TargetArg
       }
       __syncthreads();
       wn = S.woff[0];
-      IOU_STAMP(2);
       first = false;
       for (int r0 = 0; r0 < wn; r0 += kPairsPerRound)
         if (r0 + wv * (64 / kGroup) < wn) clip_round<1>(t, S, r0, wn, 0, tid, v, gbase, lds_types, bad);
       __syncthreads();
-      IOU_STAMP(4);
-#ifdef PP_IOU_CLIP_TWICE  // tools/lab: the clip once more (same result) -- what the SECOND pass through the same code takes
-      for (int r0 = 0; r0 < wn; r0 += kPairsPerRound)
-        if (r0 + wv * (64 / kGroup) < wn) clip_round<1>(t, S, r0, wn, 0, tid, v, gbase, lds_types, bad);
-      __syncthreads();
-      IOU_STAMP(5);
-#endif
       // wave 0, lane = pair: the column (maximum, then the lowest anchor index among the pairs that reach it)
       // and the pairs above the threshold
       double val = 0.0;
@@ -1961,10 +1916,8 @@ __global__ __launch_bounds__(kTgtThreads) PP_TGT_OCC void k_targets_gt(TargetArg
     }
   }
   // every store and atomic above is down before the ticket; the sample's last workgroup finishes the job
-  IOU_STAMP(6);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  IOU_STAMP(8);
   if (tid == 0) {
     handoff_release_lane0();
     // two-level ticket, 64 bits a word: low half = workgroups (groups) done, high half = the pairs above the threshold
@@ -1989,23 +1942,19 @@ __global__ __launch_bounds__(kTgtThreads) PP_TGT_OCC void k_targets_gt(TargetArg
     S.contrib = (int)ntot;
   }
   __syncthreads();
-  IOU_STAMP(9);
   if (!S.is_last) return;
   handoff_acquire_tail();
   const unsigned n_pairs = (unsigned)S.contrib;  // pairs above the threshold in the sample's list
   if (t.G <= 64 && t.G * nsp <= kFastSlots * kTgtThreads && t.num_classes <= 63 && n_pairs <= (unsigned)kFastPos &&
       n_pairs <= (unsigned)t.G * t.pos_per_gt) {
     tail_gt_fast(t, smem, t.G * nsp, n_pairs);
-    IOU_STAMP(10);
     return;
   }
   positives_tail(t, smem);
-  IOU_STAMP(15);
   if (t.G <= kForcedLds)
     targets_tail<true>(t, *reinterpret_cast<TailLds *>(smem), t.G * nsp);
   else
     targets_tail<false>(t, *reinterpret_cast<TailLds *>(smem), t.G * nsp);
-  IOU_STAMP(10);
 }
 
 
@@ -2182,15 +2131,6 @@ extern "C" int pp_make_ious_f64(pp_ctx_t *ctx, const void *a_corners, int64_t A,
   }
   DeviceGuard2 guard(ctx->device);
   hipStream_t stream = nullptr;
-  static const bool trace = getenv("PP_DROPIN_TRACE") != nullptr;  // development knob: where a call's time goes
-  auto t_prev = std::chrono::steady_clock::now();
-  double t_us[5] = {0, 0, 0, 0, 0};
-  auto lap = [&](int k) {
-    if (!trace) return;
-    const auto now = std::chrono::steady_clock::now();
-    t_us[k] += std::chrono::duration<double, std::micro>(now - t_prev).count();
-    t_prev = now;
-  };
   // pinned staging: the ground truths [G][8] + [G][2] (per call); the anchors [A][8] + [A][2] in a mirror of their own
   const size_t a_bytes = (size_t)A * 10 * 8, g_bytes = (size_t)G * 10 * 8;
   int rc = ctx->pin_in.ensure(g_bytes);
@@ -2252,7 +2192,6 @@ extern "C" int pp_make_ious_f64(pp_ctx_t *ctx, const void *a_corners, int64_t A,
     h_gn[j * 2] = rd(g_centers, j * gn[0]);
     h_gn[j * 2 + 1] = rd(g_centers, j * gn[0] + gn[1]);
   }
-  lap(0);
   double *d_a = static_cast<double *>(ctx->anchors_dev.ptr), *d_g = static_cast<double *>(ctx->stage_in.ptr);
   if (changed.load()) {
     ctx->anchors_A = -1;  // (the mirror is ahead of the device until the copy is enqueued: a failure here must not leave
@@ -2272,7 +2211,8 @@ extern "C" int pp_make_ious_f64(pp_ctx_t *ctx, const void *a_corners, int64_t A,
     unsigned *count_dev = reinterpret_cast<unsigned *>(so);
     IouTriple *triples_dev = reinterpret_cast<IouTriple *>(so + 256);
     unsigned *count_host = static_cast<unsigned *>(ctx->pin_meta.ptr);
-    // PP_DROPIN_DIRECT (any bit; pp_create_pillars_f64 shares the knob): the kernel appends its records straight into
+    // PP_DROPIN_DIRECT (any bit; pp_create_pillars_f64 reads the same variable; 0 = by copies, which the transport test
+    // compares): the kernel appends its records straight into
     // device-visible pinned memory -- each is one 16-byte store of one lane, ~8 000 of them -- and a one-thread kernel
     // behind it leaves the count and the error word there too: the call waits for the device ONCE (before: the count's
     // copy, the records' copy and pp_iou_check's copy, a wait each).  Lists beyond 16 MB keep the copies.
@@ -2307,7 +2247,6 @@ extern "C" int pp_make_ious_f64(pp_ctx_t *ctx, const void *a_corners, int64_t A,
     const hipError_t e_sync = hipStreamSynchronize(stream);
     pool->wait();
     PP_HIP_TRY(e_sync);
-    lap(1);
     const unsigned count = count_host[0];
     if (direct && count_host[1]) return iou_flag_result(ctx, (int)count_host[1]);  // (a wrong winding: the matrix is zeros)
     if (count <= cap) {
@@ -2322,10 +2261,6 @@ extern "C" int pp_make_ious_f64(pp_ctx_t *ctx, const void *a_corners, int64_t A,
         for (unsigned k = 0; k < count; ++k)
           std::memcpy(dst + (int64_t)tr[k].anchor * io[0] + (int64_t)tr[k].box * io[1], &tr[k].iou, 8);
       }
-      lap(2);
-      if (trace)
-        fprintf(stderr, "pp_make_ious_f64: gather + compare %.0f us (anchors %s) | H2D + kernel (host zero fill alongside, %d threads) %.0f | %u records back + written %.0f\n",
-                t_us[0], changed.load() ? "uploaded" : "resident", pool->size(), t_us[1], count, t_us[2]);
       return direct ? PP_OK : pp_iou_check(ctx, stream);
     }
     // the list overflowed: the anchors are on the device already, take the dense form
@@ -2396,11 +2331,7 @@ static int assign_targets_impl(pp_ctx_t *ctx, void *stream_, int batch, const in
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   DeviceGuard2 guard(ctx->device);
   // Which form: anchors on the fly -> the box-centric kernel (k_targets_gt); anchor arrays -> k_targets.
-  static const int form_env = [] {  // development knob: PP_TARGETS_FORM=anchors|boxes
-    const char *e = getenv("PP_TARGETS_FORM");
-    return !e ? 0 : (e[0] == 'a' ? 1 : 2);
-  }();
-  bool boxes_form = an.grid && form_env != 1 && an.per_cell <= kLdsTypes;  // (the box-centric kernel keeps the type table in LDS)
+  bool boxes_form = an.grid && an.per_cell <= kLdsTypes;  // (the box-centric kernel keeps the type table in LDS)
   // scratch: [0,8192) error flag + every sample's {list counter, ticket, pair counter} | col_max[Gcap] |
   // col_win[Gcap] | first-level tickets | cand[cand_per_gt * Gcap] | pos[pos_per_gt * Gcap] | best, bestj
   // [batch * A]; sample b owns the rows [g_off[b], g_off[b+1]) of each (Gcap = all samples' G)
@@ -2416,15 +2347,10 @@ static int assign_targets_impl(pp_ctx_t *ctx, void *stream_, int batch, const in
   if (boxes_form) {
     const double per_axis = std::min(std::floor(20.0 * an.fm_scale) + 3.0, 32768.0);
     const double cand = per_axis * per_axis * an.per_cell;
-    static const int cpw_env = [] {  // development knob: PP_TARGETS_CAND=<candidates per workgroup, 8..64>
-      const char *e = getenv("PP_TARGETS_CAND");
-      return e ? std::min(std::max(atoi(e), 8), kCandPerWg) : 0;
-    }();
     for (size_t c : {(size_t)32, (size_t)40, (size_t)48, (size_t)64}) {
       cand_per_wg = c;
       if ((double)g_total * std::ceil(cand / (double)c) + (double)batch * kZeroWgs <= 900.0) break;
     }
-    if (cpw_env) cand_per_wg = (size_t)cpw_env;
     splits = (size_t)std::min(std::max(std::ceil(cand / (double)cand_per_wg), 1.0), 64.0);
     // grid.y holds the zero-fill workgroups and every box's PAIR workgroups: a sample with more boxes than that
     // (eleven thousand at C3's six workgroups per box) goes through the anchor-centric kernel, which walks any
@@ -2654,11 +2580,3 @@ extern "C" int pp_assign_targets_grid_batch_dev(pp_ctx_t *ctx, void *stream_, in
                              g_corners, g_centers_img, g_centers, g_wlh, g_yaw, g_class, prm,
                              cls_targets, reg_targets);
 }
-
-#ifdef PP_IOU_STAMPS
-// development builds only (tools/lab): the phase stamps of the last k_targets launch, 16 per workgroup
-extern "C" int pp_debug_iou_stamps(unsigned long long *out, int n_words) {
-  if (hipDeviceSynchronize() != hipSuccess) return PP_ERR_HIP;
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(pp::g_iou_stamps), (size_t)n_words * 8) == hipSuccess ? PP_OK : PP_ERR_HIP;
-}
-#endif

@@ -47,7 +47,6 @@
 #include <climits>
 #include <cmath>
 #include <cstdlib>
-#include <chrono>
 #include <cstring>
 
 namespace pp {
@@ -56,10 +55,7 @@ namespace pp {
 // constants                                                                  //
 // ------------------------------------------------------------------------- //
 constexpr int kWave = 64;
-#ifndef PP_CHUNK
-#define PP_CHUNK 1024
-#endif
-constexpr int kChunk = PP_CHUNK;             // points per split workgroup, one per thread
+constexpr int kChunk = 1024;                 // points per split workgroup, one per thread
 constexpr int kSplitThreads = kChunk;
 constexpr int kSplitWaves = kSplitThreads / kWave;
 constexpr int kMinTileSlots = 256, kMaxTileSlots = 4096;  // a tile's cells live in LDS (20 B each)
@@ -67,14 +63,8 @@ constexpr int kTargetTiles = 256;            // tiles (= k_tile workgroups, spli
 constexpr int kMaxTiles = 4096;              // split bins: byte histograms [16][T] must fit LDS
 constexpr int kEmitWaves = 4;                // waves per emit workgroup
 constexpr int kEmitThreads = kEmitWaves * kWave;
-#ifndef PP_KW
-#define PP_KW 4
-#endif
-constexpr int KW = PP_KW;  // pillars per emit wave
-#ifndef PP_CAPW
-#define PP_CAPW (PP_KW >= 2 ? 32 * PP_KW : 64)
-#endif
-constexpr int CAPW = PP_CAPW;  // pooled bucket capacity (points, 4-padded per pillar) per emit wave
+constexpr int KW = 4;          // pillars per emit wave
+constexpr int CAPW = 32 * KW;  // pooled bucket capacity (points, 4-padded per pillar) per emit wave
 
 using u64 = unsigned long long;
 
@@ -156,20 +146,6 @@ __device__ __forceinline__ u64 wave_peers(unsigned key, int bits, bool valid) {
   return peers;
 }
 
-
-#ifdef PP_STAMPS  // tools/lab builds: PP_STAMPS=1 stamps k_tile, =2 k_split, =3 k_emit (8 stamps per wave)
-#define PP_STAMP_AT(which, k)                                                        \
-  do {                                                                               \
-    if (PP_STAMPS == (which) && stamps && lane == 0)                                  \
-      stamps[(((size_t)stamp_by * stamp_nx + stamp_bx) * 16 + w) * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); \
-  } while (0)
-#else
-#define PP_STAMP_AT(which, k) do {} while (0)
-#endif
-#define PP_STAMP(k) PP_STAMP_AT(1, k)
-#define PP_STAMP_S(k) PP_STAMP_AT(2, k)
-#define PP_STAMP_E(k) PP_STAMP_AT(3, k)
-
 // LDS of k_split: byte histograms [kSplitWaves][Tp], bin offsets u16 [Tp], wave totals.
 __host__ __device__ inline int split_tp(int ntiles) { return (ntiles + 3) & ~3; }
 __host__ __device__ inline size_t split_lds_bytes(int ntiles) {
@@ -181,7 +157,7 @@ template <typename T>
 __global__ __launch_bounds__(kSplitThreads) void k_split(
     const T *__restrict__ pts, int64_t sweep_stride, int64_t s0, int64_t s1, int contig,
     NPoints np, GridGeom g, int ncap, int nchunks_cap, int *__restrict__ kslot,
-    typename Rec4<T>::type *__restrict__ kpts, int2 *__restrict__ mat, u64 *stamps) {
+    typename Rec4<T>::type *__restrict__ kpts, int2 *__restrict__ mat) {
   extern __shared__ __attribute__((aligned(16))) unsigned char split_smem[];
   using Rec = typename Rec4<T>::type;
   const int b = blockIdx.y;
@@ -189,8 +165,6 @@ __global__ __launch_bounds__(kSplitThreads) void k_split(
   const int chunk = blockIdx.x;
   if (chunk * kChunk >= n) return;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  [[maybe_unused]] const int stamp_nx = gridDim.x, stamp_bx = blockIdx.x, stamp_by = blockIdx.y;
-  PP_STAMP_S(0);
   const int ntiles = g.ntiles;
   const int Tp = split_tp(ntiles);
   unsigned char *whist = split_smem;
@@ -212,12 +186,9 @@ __global__ __launch_bounds__(kSplitThreads) void k_split(
   const unsigned tile = valid ? (unsigned)slot >> g.tile_shift : 0u;
   const u64 peers = wave_peers(tile, g.tile_bits, valid);
   const int rank_w = __popcll(peers & lanes_below(lane));
-  PP_STAMP_S(1);
   __syncthreads();
-  PP_STAMP_S(2);
   if (valid && rank_w == 0) whist[w * Tp + tile] = (unsigned char)__popcll(peers);  // <= 64
   __syncthreads();
-  PP_STAMP_S(3);
   // bin totals over the 16 waves, exclusive scan over the bins (consecutive bins per thread)
   const int nb = (ntiles + kSplitThreads - 1) / kSplitThreads;  // <= kMaxTiles / 1024 = 4
   unsigned tot[4] = {0u, 0u, 0u, 0u};
@@ -235,7 +206,6 @@ __global__ __launch_bounds__(kSplitThreads) void k_split(
   }
   const int inc = (int)wave_scan_u32(mine);
   if (lane == kWave - 1) wtot[w] = (unsigned)inc;
-  PP_STAMP_S(4);
   __syncthreads();
   unsigned base = (unsigned)inc - mine;
 #pragma unroll
@@ -251,9 +221,7 @@ __global__ __launch_bounds__(kSplitThreads) void k_split(
       base += tot[e];
     }
   }
-  PP_STAMP_S(5);
   __syncthreads();
-  PP_STAMP_S(6);
   if (valid) {
     unsigned pos = binoff[tile] + (unsigned)rank_w;
     for (int ww = 0; ww < w; ++ww) pos += whist[ww * Tp + tile];
@@ -261,7 +229,6 @@ __global__ __launch_bounds__(kSplitThreads) void k_split(
     kslot[dst] = slot;
     kpts[dst] = rec;
   }
-  PP_STAMP_S(7);
 }
 
 // k_split's work for a workgroup of PW < 16 physical waves (k_step's split role): the chunk is still
@@ -436,7 +403,7 @@ __device__ __forceinline__ void tile_body(
     const NPoints &np, const GridGeom &g, int ncap, int nchunks_cap, const int *__restrict__ kslot,
     const typename Rec4<T>::type *__restrict__ kpts, const int2 *__restrict__ mat,
     typename Rec4<T>::type *__restrict__ sorted_pts, int4 *__restrict__ tile_meta,
-    u64 *__restrict__ tile_agg, u64 *stamps, unsigned *tile_smem, int tile, int b) {
+    u64 *__restrict__ tile_agg, unsigned *tile_smem, int tile, int b) {
   using Rec = typename Rec4<T>::type;
   constexpr int THREADS = WAVES * kWave;
   constexpr int HW = WAVES / 4;  // dwords of a cell's per-wave byte counts
@@ -444,8 +411,6 @@ __device__ __forceinline__ void tile_body(
   __shared__ unsigned s_before;  // points of all earlier tiles
   __shared__ u64 s_wave[WAVES];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  [[maybe_unused]] const int stamp_nx = g.ntiles, stamp_bx = tile, stamp_by = b;
-  PP_STAMP(0);
   const int TS = 1 << g.tile_shift;
   TileLds L;
   L.cur = tile_smem;
@@ -456,7 +421,6 @@ __device__ __forceinline__ void tile_body(
   L.cq = reinterpret_cast<unsigned short *>(L.csrc + kCapT);
   for (int q = tid; q < (1 + HW) * TS; q += THREADS) L.cur[q] = 0u;  // cur and hist
   if (tid == 0) s_before = 0u;
-  PP_STAMP(1);
   const int n = np.n[b];
   const int nch = (n + kChunk - 1) / kChunk;
   const int nwin = (nch + kWin - 1) / kWin;
@@ -519,7 +483,6 @@ __device__ __forceinline__ void tile_body(
     ntile += G;
   }
   __syncthreads();
-  PP_STAMP(2);
   // prefix sums over the tile's cells: thread owns cpt consecutive cells
   const int cpt = TS > THREADS ? TS / THREADS : 1;  // 1 .. 16
   u64 mine = 0;
@@ -530,9 +493,7 @@ __device__ __forceinline__ void tile_body(
     }
   const u64 inc = wave_scan_2x32(mine);  // {points, occupied cells}: two independent counts
   if (lane == kWave - 1) s_wave[w] = inc;
-  PP_STAMP(3);
   __syncthreads();
-  PP_STAMP(4);
   u64 wave_off = 0, agg = 0;
 #pragma unroll
   for (int k = 0; k < WAVES; ++k) {
@@ -555,7 +516,6 @@ __device__ __forceinline__ void tile_body(
       st += c;
     }
   }
-  PP_STAMP(5);
   // pass 2
   Rec *sp = sorted_pts + (int64_t)b * ncap;
   const u64 below = lanes_below(lane);
@@ -641,7 +601,6 @@ __device__ __forceinline__ void tile_body(
       });
     }
   }
-  PP_STAMP(7);
 }
 
 // The fused feature-net mode's canvas (PPScatter, model/model.py:53-62) must read zero wherever no pillar
@@ -691,12 +650,8 @@ __device__ __forceinline__ void unscatter_body(const UnscatterArgs &u, int blk, 
 // Blocks t, t + 8, t + 16, ... take CONSECUTIVE tiles instead: an eighth of the tile range per XCD.  (A permutation of
 // the tiles whatever the dispatch order is: placement changes the traffic, never the result.)
 __device__ __forceinline__ int tile_of_block(int t, int nt) {
-#ifdef PP_TILE_NO_XCD_MAP  // tools/lab: A/B
-  return t;
-#else
   const int k = t & 7, q = t >> 3;
   return k * (nt >> 3) + min(k, nt & 7) + q;
-#endif
 }
 
 template <typename T, int WAVES>
@@ -704,13 +659,13 @@ __global__ __launch_bounds__(WAVES * kWave) void k_tile(
     NPoints np, GridGeom g, int ncap, int nchunks_cap, const int *__restrict__ kslot,
     const typename Rec4<T>::type *__restrict__ kpts, const int2 *__restrict__ mat,
     typename Rec4<T>::type *__restrict__ sorted_pts, int4 *__restrict__ tile_meta,
-    u64 *__restrict__ tile_agg, u64 *stamps, UnscatterArgs un) {
+    u64 *__restrict__ tile_agg, UnscatterArgs un) {
   extern __shared__ __attribute__((aligned(16))) unsigned tile_smem[];
   if ((int)blockIdx.x >= g.ntiles) {  // (only launched when un.nblocks > 0)
     unscatter_body(un, (int)blockIdx.x - g.ntiles, (int)blockIdx.y, WAVES * kWave);
     return;
   }
-  tile_body<T, WAVES>(np, g, ncap, nchunks_cap, kslot, kpts, mat, sorted_pts, tile_meta, tile_agg, stamps,
+  tile_body<T, WAVES>(np, g, ncap, nchunks_cap, kslot, kpts, mat, sorted_pts, tile_meta, tile_agg,
                       tile_smem, tile_of_block((int)blockIdx.x, g.ntiles), (int)blockIdx.y);
 }
 
@@ -761,7 +716,6 @@ struct EmitArgs {
   // ... scattered straight into the BEV canvas (PPScatter, model/model.py:53-62)
   float *canvas;       // NULL, [B][H][W][64] (channels last) or [B][64][H][W]
   int canvas_h, canvas_w, canvas_nhwc;
-  u64 *stamps;         // tools/lab builds only
 };
 
 enum { kModeDenseVec4 = 0, kModeDenseScalar = 1, kModeCompact = 2, kModePfn = 3 };
@@ -837,12 +791,6 @@ __device__ __forceinline__ void point_features(double x, double y, double z, dou
 //     3-4 of them (CAP = 128) -- fewer rounds, hence fewer rounds of the operands' four f64 divisions per point,
 //     once the short buckets are through.
 // Results: L.mean[k].
-#ifdef PP_STAMPS  // tools/lab builds: where streamed_means' time goes (shader clocks, maxima over the launch's waves)
-__device__ unsigned long long g_means_prof[8];  // 0 total, 1 chains (asm loops), 2 staging (operands), 3 steps, 4 rounds
-#define PP_MEANS_CLK() __builtin_readcyclecounter()
-#else
-#define PP_MEANS_CLK() 0ull
-#endif
 template <typename TIn, int CAP>
 __device__ void streamed_means(WaveLds<TIn, CAP> &L, const EmitArgs &a, int b, unsigned mask, int lane) {
   using Rec = typename Rec4<TIn>::type;
@@ -897,7 +845,6 @@ __device__ void streamed_means(WaveLds<TIn, CAP> &L, const EmitArgs &a, int b, u
   };
   const int kq = lane / 3, cq_ = lane - 3 * kq;
   const bool chain = lane < 3 * KW && ((mask >> kq) & 1u);
-  [[maybe_unused]] unsigned long long pf_t0 = PP_MEANS_CLK(), pf_chain = 0, pf_stage = 0, pf_steps = 0, pf_rounds = 0, pf_fetch = 0;
   double m = -0.0;
   Rec rec[kPre];
   int ek[kPre], ei[kPre];
@@ -909,7 +856,6 @@ __device__ void streamed_means(WaveLds<TIn, CAP> &L, const EmitArgs &a, int b, u
 #pragma unroll
     for (int k = 0; k < KW; ++k) left = max(left, cnt[k] - base);
     const int steps = (min(left, slice) + 3) & ~3;
-    [[maybe_unused]] const unsigned long long pf_a = PP_MEANS_CLK();
 #pragma unroll
     for (int it = 0; it < kPre; ++it) {
       const int j = lane + it * kWave;
@@ -922,12 +868,10 @@ __device__ void streamed_means(WaveLds<TIn, CAP> &L, const EmitArgs &a, int b, u
       }
     }
     wave_sync();
-    [[maybe_unused]] const unsigned long long pf_c = PP_MEANS_CLK();
     // the next round's records travel while this round's chains run
     const int base_next = base + slice;
     const Plan nxt = plan_at(base_next);
     if (base_next < maxcnt) fetch(nxt, base_next, rec, ek, ei);
-    [[maybe_unused]] const unsigned long long pf_b = PP_MEANS_CLK();
     if (chain && ((cur.act >> kq) & 1u)) {
       const int qpos = __popc(cur.act & ((1u << kq) - 1u)) << cur.shift;
       // (the generic pointer's low 32 bits ARE the LDS byte address: aperture base in the high half + offset)
@@ -937,8 +881,8 @@ __device__ void streamed_means(WaveLds<TIn, CAP> &L, const EmitArgs &a, int b, u
       // Register sets A = v[32:47], B = v[48:63] (named in the clobber list: the reads are ds_read2_b64 -- two steps'
       // scales, or two steps' values, per instruction -- whose four-register destinations are used half by half, which
       // an asm operand cannot express).  Per group of four steps: four LDS instructions, eight dependent f64 operations,
-      // the next group's operands in flight.  Measured (tools/lab/emit_stamps.py, profiles/r06/NOTES.md): 31 clocks per
-      // step; the bare dependent pair is 15-17 (tools/lab/f64_rate.cpp).  A wave that is alone on its SIMD issues one
+      // the next group's operands in flight.  Measured (profiles/r06/NOTES.md): 31 clocks per
+      // step; the bare dependent pair is 15-17 (same notes).  A wave that is alone on its SIMD issues one
       // instruction every four clocks, whatever its kind, so every instruction of the loop counts: one ds_read_b64 per
       // operand (eight reads per group) gave 33.5, a third register set (operands two groups ahead) 35 and the first
       // spills -- the LDS round trip is covered, what is left is the loop's own instruction count.
@@ -992,30 +936,11 @@ __device__ void streamed_means(WaveLds<TIn, CAP> &L, const EmitArgs &a, int b, u
             "v61", "v62", "v63");
     }
     wave_sync();
-#ifdef PP_STAMPS
-    pf_stage += pf_c - pf_a;
-    pf_fetch += pf_b - pf_c;
-    pf_chain += PP_MEANS_CLK() - pf_b;
-    pf_steps += (unsigned long long)steps;
-    pf_rounds += 1;
-#endif
     base = base_next;
     cur = nxt;
   }
   if (chain) L.mean[kq][cq_] = m;
   wave_sync();
-#ifdef PP_STAMPS
-  if (lane == 0) {
-    const unsigned long long tot = PP_MEANS_CLK() - pf_t0;
-    if (tot > atomicMax(&g_means_prof[0], tot)) {  // (the slowest wave's breakdown, more or less)
-      g_means_prof[1] = pf_chain;
-      g_means_prof[2] = pf_stage;
-      g_means_prof[3] = pf_steps;
-      g_means_prof[4] = pf_rounds;
-      g_means_prof[5] = pf_fetch;
-    }
-  }
-#endif
 }
 
 // The features of a big pillar's first min(count, N) points (its mean is in L.mean[k]: streamed_means).
@@ -1369,9 +1294,6 @@ __device__ __forceinline__ void emit_body(const EmitArgs &a, WaveLds<TIn, CAP> *
   // derived from it (slab geometry, line masks, buffer offsets) in SGPRs
   const int p0 = __builtin_amdgcn_readfirstlane((bx * kEmitWaves + w) * KW);
   if (p0 >= P) return;
-  [[maybe_unused]] u64 *stamps = a.stamps;
-  [[maybe_unused]] const int stamp_nx = nbx, stamp_bx = bx, stamp_by = b;
-  PP_STAMP_E(0);
   const int kw_eff = min(KW, P - p0);
   // (1) pillar descriptors.  The pillar index of a cell = occupied cells of all earlier
   //     tiles + its place in its tile's list; k_tile left the former open, so every wave
@@ -1414,7 +1336,6 @@ __device__ __forceinline__ void emit_body(const EmitArgs &a, WaveLds<TIn, CAP> *
     if (MODE == kModeCompact && a.totals_host) a.totals_host[b] = make_int2((int)(tot & 0xFFFFFFFFull), (int)(tot >> 32));
   }
   const int npil = min((int)(tot & 0xFFFFFFFFull), P);
-  PP_STAMP_E(1);
 #pragma unroll
   for (int k = 0; k < KW; ++k) {
     const unsigned p = (unsigned)(p0 + k);
@@ -1517,7 +1438,6 @@ __device__ __forceinline__ void emit_body(const EmitArgs &a, WaveLds<TIn, CAP> *
     }
   }
   wave_sync();
-  PP_STAMP_E(2);
   // (3) scatter indices; dense modes: the zero padding that needs no point data
   float *outb = nullptr;
   if (MODE != kModeCompact) {
@@ -1652,10 +1572,8 @@ __device__ __forceinline__ void emit_body(const EmitArgs &a, WaveLds<TIn, CAP> *
     if constexpr (MODE == kModePfn) pfn_finish();
     return;
   }
-  PP_STAMP_E(3);
   if (pooled) {
     emit_group<TIn, MODE, CAP>(L, a, b, p0, 0, KW, lane, rec_r, segbeg, segpad, cnts, T);
-    PP_STAMP_E(4);
     if constexpr (MODE == kModeDenseVec4) store_slab<kPassAll, TIn, AUX>(L, sg, rs, lane, segpad);
     if constexpr (MODE == kModePfn) {
 #pragma unroll
@@ -1676,7 +1594,6 @@ __device__ __forceinline__ void emit_body(const EmitArgs &a, WaveLds<TIn, CAP> *
     for (int kk = 0; kk < KW; ++kk)
       if (cnts[kk] > 0) occ |= 1u << kk;
     streamed_means<TIn, CAP>(L, a, b, occ, lane);
-    PP_STAMP_E(4);
     int k = 0;
 #pragma unroll 1
     while (k < KW) {
@@ -1742,19 +1659,11 @@ __device__ __forceinline__ void emit_body(const EmitArgs &a, WaveLds<TIn, CAP> *
       }
     }
   }
-  PP_STAMP_E(5);
   if constexpr (MODE == kModePfn) pfn_finish();
-  PP_STAMP_E(6);
 }
 
-#ifndef PP_EMIT_MINWAVES
-#define PP_EMIT_MINWAVES 4
-#endif
 constexpr int emit_cap(int mode) { return mode == kModePfn ? 64 : CAPW; }
-#ifndef PP_PFN_MINWAVES
-#define PP_PFN_MINWAVES 6
-#endif
-constexpr int emit_minwaves(int mode) { return mode == kModePfn ? PP_PFN_MINWAVES : PP_EMIT_MINWAVES; }
+constexpr int emit_minwaves(int mode) { return mode == kModePfn ? 6 : 4; }  // waves per SIMD
 template <typename TIn, int MODE, int AUX = 0>
 __global__ __launch_bounds__(kEmitThreads, emit_minwaves(MODE)) void k_emit(EmitArgs a) {
   __shared__ WaveLds<TIn, emit_cap(MODE)> lds[kEmitWaves];
@@ -1800,13 +1709,13 @@ struct TileRole {
 // PREVIOUS launch; when other work ran in between (the network's activations: a GiB per step) they are in HBM
 // again, and the role is a chain of dependent loads -- every hop would pay an HBM miss under a full store
 // load.  A few workgroups at the head of the grid read those arrays once, front to back, with many loads in
-// flight: the lines land in the memory-side Infinity Cache before most of the chains ask for them.  (The list
-// can also hold the binning roles' inputs -- PP_STEP_PREFETCH_SETS -- which paid while binning and emit blocks
-// alternated; with the binning blocks first they fetch for themselves at the same moment: see step_impl.)
+// flight: the lines land in the memory-side Infinity Cache before most of the chains ask for them.  (The binning
+// roles' inputs were in the list while binning and emit blocks alternated; with the binning blocks first they fetch for
+// themselves at the same moment: see step_impl.)
 struct PrefetchRole {
   const void *ptr[7];
   unsigned n16[7];       // 16-byte units
-  const u64 *tile_agg;   // [nlists] {points << 32 | occupied cells}: how much of each tile's list is in use
+  const u64 *tile_agg;   // [nlists] {points << 32 | occupied cells}: how much of each tile's list is in use (nlists = 0 today)
   const int4 *tile_meta;
   int nlists, list_stride;
 };
@@ -1868,24 +1777,24 @@ struct StepArgs {
   SplitRole s;
   EmitArgs e;
 };
+constexpr int kStepPrefetchBlocks = 128;  // workgroups of the prefetch role at the head of the grid
 constexpr int kStepChipSlots = 5 * 256;  // k_step workgroups the chip holds at once (LDS and VGPRs: 5 per CU)
 constexpr int kStepWaves = 4;
 constexpr int kStepThreads = kStepWaves * kWave;
 static_assert(kStepWaves == kEmitWaves, "the emit role is k_emit's workgroup");
 
-#ifndef PP_STEP_PFN_MINWAVES
-#define PP_STEP_PFN_MINWAVES 5
-#endif
-constexpr int step_minwaves(int mode) { return mode == kModePfn ? PP_STEP_PFN_MINWAVES : 5; }
+constexpr int kStepMinWaves = 5;  // waves per SIMD the register budget allows, every mode
 template <int MODE, int AUX>
-__global__ __launch_bounds__(kStepThreads, step_minwaves(MODE)) void k_step(StepArgs a) {   // five waves per SIMD: <= 96 VGPRs
+__global__ __launch_bounds__(kStepThreads, kStepMinWaves) void k_step(StepArgs a) {   // five waves per SIMD: <= 96 VGPRs
   extern __shared__ __attribute__((aligned(32))) unsigned char step_smem[];
   int id = (int)blockIdx.x;
   if (id < a.n_pref_blocks) {
     // prefetch role: stream the previous launch's arrays into the cache hierarchy (values unused)
     const unsigned worker = (unsigned)id * kStepThreads + threadIdx.x, nworkers = (unsigned)a.n_pref_blocks * kStepThreads;
     unsigned acc = 0;
-    // the occupied heads of the tiles' descriptor lists: one wave per list
+    // the occupied heads of the tiles' descriptor lists: one wave per list.  The host leaves nlists at 0 (only the emit
+    // role's arrays are prefetched, see step_impl); the walk stays because taking it out made the compiler lay out the
+    // dense modes' basic blocks differently, which is more than a deletion (profiles/r08/NOTES.md)
     for (int t = (int)(worker >> 6); t < a.pf.nlists; t += (int)(nworkers >> 6)) {
       const unsigned c = (unsigned)(a.pf.tile_agg[t] & 0xFFFFFFFFull);
       const int4 *lst = a.pf.tile_meta + (int64_t)t * a.pf.list_stride;
@@ -1923,8 +1832,8 @@ __global__ __launch_bounds__(kStepThreads, step_minwaves(MODE)) void k_step(Step
   // Block order.  Workgroups are dispatched in id order.  The binning roles' (tile, order, split) are few and
   // latency-bound, the emit role's many and store-bound; a binning chain that starts late is the launch's
   // tail.  mix_groups = 0 (host side: the binning blocks fit the chip at once): all binning blocks first,
-  // then the emit blocks.  mix_groups > 0 (more binning blocks than that, or PP_STEP_MIX = m >= 2): the grid
-  // starts with groups of one binning block and m-1 emit blocks, so that the stores also flow from the first
+  // then the emit blocks.  mix_groups > 0 (more binning blocks than that): the grid
+  // starts with groups of one binning block and mix-1 emit blocks, so that the stores also flow from the first
   // microsecond; what is left of either kind follows.
   {
     const int nbin = a.n_tile_blocks + a.n_order_blocks + a.n_split_blocks;
@@ -1948,7 +1857,7 @@ __global__ __launch_bounds__(kStepThreads, step_minwaves(MODE)) void k_step(Step
     tile_body<float, kStepWaves>(a.t.np, a.t.g, a.t.ncap, a.t.nchunks_cap, a.t.kslot,
                                  reinterpret_cast<const float4 *>(a.t.kpts), a.t.mat,
                                  reinterpret_cast<float4 *>(a.t.sorted_pts), a.t.tile_meta, a.t.tile_agg,
-                                 nullptr, reinterpret_cast<unsigned *>(step_smem), tile, b);
+                                 reinterpret_cast<unsigned *>(step_smem), tile, b);
     return;
   }
   id -= a.n_tile_blocks;
@@ -2036,11 +1945,6 @@ int make_grid(const pp_voxel_params_t *prm, GridGeom *g, int step_mode) {
   // tiles: the smallest power-of-two run of slots that keeps the split at <= kTargetTiles bins;
   // a k_tile workgroup holds its tile's cells in LDS, a k_split workgroup a byte histogram per bin
   int ts = kMinTileSlots;
-  static const int forced_tiles = [] {  // development knob
-    const char *e = getenv("PP_TARGET_TILES");
-    const int v = e ? atoi(e) : 0;
-    return v >= 16 && v <= kMaxTiles ? v : 0;
-  }();
   // row-major tiles are strips of the plane and lidar clouds are centre-heavy: finer tiles
   // (at most 2048 slots) bound the crowded ones; scrambled tiles are uniform and fewer, larger
   // ones cost less.  Beyond kMaxTiles of them the tiles grow to their LDS limit either way.
@@ -2049,12 +1953,11 @@ int make_grid(const pp_voxel_params_t *prm, GridGeom *g, int step_mode) {
   // tile workgroups hold fewer of the chip's workgroup slots while they wait out their latency chains:
   // 123 tiles of 2048 slots beat 245 of 1024 (C2: 13.1 / 33.6 us per step against 14.7 / 36.8, B = 1 / 4).
   // Round 5, k_step with the row-major order: tiles of 512 slots (489 at C2) -- its crowded strips were the launch
-  // (C2: 53.0 -> 41.9 us at 4 sweeps per launch, 26.6 -> 14.0 us at one; tools/lab/sweep_rowmajor.sh); the scrambled
+  // (C2: 53.0 -> 41.9 us at 4 sweeps per launch, 26.6 -> 14.0 us at one; profiles/r05/NOTES.md); the scrambled
   // order's uniform tiles stay at 2048 slots (38.5 us; 39.9 with 512).
-  const int target_tiles = forced_tiles ? forced_tiles
-                         : prm->order == PP_ORDER_ROW_MAJOR ? (step_mode ? 2 * kTargetTiles : kTargetTiles)
+  const int target_tiles = prm->order == PP_ORDER_ROW_MAJOR ? (step_mode ? 2 * kTargetTiles : kTargetTiles)
                                                             : kTargetTiles / 2;
-  const int soft_cap = ((prm->order == PP_ORDER_ROW_MAJOR && !forced_tiles) || step_mode) ? 2048 : kMaxTileSlots;
+  const int soft_cap = (prm->order == PP_ORDER_ROW_MAJOR || step_mode) ? 2048 : kMaxTileSlots;
   while ((nc + ts - 1) / ts > target_tiles && ts < soft_cap) ts *= 2;
   while ((nc + ts - 1) / ts > kMaxTiles && ts < kMaxTileSlots) ts *= 2;
   const long long nt = (nc + ts - 1) / ts;
@@ -2086,7 +1989,7 @@ int make_grid(const pp_voxel_params_t *prm, GridGeom *g, int step_mode) {
 namespace {
 
 struct VoxLayout {
-  size_t kslot, kpts, mat, sorted_pts, tile_meta, tile_agg, meta, totals, otot, stamps, bytes;
+  size_t kslot, kpts, mat, sorted_pts, tile_meta, tile_agg, meta, totals, otot, bytes;
   int ncap;         // point capacity per sweep, a multiple of the split chunk
   int nchunks_cap;  // split chunks per sweep at capacity
 };
@@ -2117,10 +2020,6 @@ VoxLayout vox_layout(int B, int64_t max_points, const GridGeom &g, int P, int re
   off = align_up(off + (size_t)B * 8, 256);
   l.otot = off;       // k_step: {cells, points} per sweep, left by the order role for the emit role
   off = align_up(off + (size_t)B * 8, 256);
-  l.stamps = off;
-#ifdef PP_STAMPS
-  off = align_up(off + (size_t)B * std::max(std::max(g.ntiles, l.nchunks_cap), (P + KW * kEmitWaves - 1) / (KW * kEmitWaves)) * 16 * 64, 256);
-#endif
   l.bytes = off;
   return l;
 }
@@ -2184,9 +2083,7 @@ int launch_pipeline(pp_ctx *ctx, hipStream_t stream, const TIn *pts, int64_t swe
 
   // k_tile geometry: waves per tile from the mean population of a tile
   const long long per_tile = ((long long)maxn + g.ntiles - 1) / g.ntiles;
-  const int tw = ctx->force_tile_waves ? ctx->force_tile_waves
-               : per_tile <= 96 ? 4
-               : per_tile <= (g.order == PP_ORDER_ROW_MAJOR ? 640 : 1024) ? 8 : 16;
+  const int tw = per_tile <= 96 ? 4 : per_tile <= (g.order == PP_ORDER_ROW_MAJOR ? 640 : 1024) ? 8 : 16;
   const int wi = tw == 4 ? 0 : tw == 8 ? 1 : 2;
   const size_t lds_split = split_lds_bytes(g.ntiles);
   const size_t lds_tile = tile_lds_bytes(1 << g.tile_shift, tw);
@@ -2214,12 +2111,6 @@ int launch_pipeline(pp_ctx *ctx, hipStream_t stream, const TIn *pts, int64_t swe
     }
   }
   const int nchunks = std::max(1, (maxn + kChunk - 1) / kChunk);
-  u64 *stamps = nullptr;
-#ifdef PP_STAMPS
-  stamps = reinterpret_cast<u64 *>(ws + l.stamps);
-  ctx->dbg_stamps_off = l.stamps;
-  ctx->dbg_stamps_bytes = (size_t)B * (PP_STAMPS == 2 ? nchunks : PP_STAMPS == 3 ? (P + KW * kEmitWaves - 1) / (KW * kEmitWaves) : g.ntiles) * 16 * 64;
-#endif
   // When the timing ring is armed every launch carries its own start/stop events
   // (hipExtLaunchKernelGGL binds them to the dispatch packet, so a pair brackets the
   // kernel alone, like a profiler's kernel trace, not the gaps around it).
@@ -2236,8 +2127,7 @@ int launch_pipeline(pp_ctx *ctx, hipStream_t stream, const TIn *pts, int64_t swe
   }
   hipExtLaunchKernelGGL((k_split<TIn>), dim3((unsigned)nchunks, (unsigned)B), dim3(kSplitThreads),
                         lds_split, stream, ev0[PP_KERNEL_SPLIT], ev1[PP_KERNEL_SPLIT], 0, pts,
-                        sweep_stride, s0, s1, contig, np, g, l.ncap, l.nchunks_cap, kslot, kpts, mat,
-                        stamps);
+                        sweep_stride, s0, s1, contig, np, g, l.ncap, l.nchunks_cap, kslot, kpts, mat);
   UnscatterArgs un;
   std::memset(&un, 0, sizeof un);
   if (canvas && prev_idx) {
@@ -2252,7 +2142,7 @@ int launch_pipeline(pp_ctx *ctx, hipStream_t stream, const TIn *pts, int64_t swe
   auto launch_tile = [&](auto kern) {
     hipExtLaunchKernelGGL(kern, dim3((unsigned)(g.ntiles + un.nblocks), (unsigned)B), dim3(tw * kWave), lds_tile,
                           stream, ev0[PP_KERNEL_TILE], ev1[PP_KERNEL_TILE], 0, np, g, l.ncap,
-                          l.nchunks_cap, kslot, kpts, mat, sorted_pts, tile_meta, tile_agg, stamps, un);
+                          l.nchunks_cap, kslot, kpts, mat, sorted_pts, tile_meta, tile_agg, un);
   };
   if (tw == 4) launch_tile(&k_tile<TIn, 4>);
   else if (tw == 8) launch_tile(&k_tile<TIn, 8>);
@@ -2282,20 +2172,15 @@ int launch_pipeline(pp_ctx *ctx, hipStream_t stream, const TIn *pts, int64_t swe
   a.canvas_h = canvas_h;
   a.canvas_w = canvas_w;
   a.canvas_nhwc = canvas_nhwc;
-  a.stamps = stamps;
   const dim3 grid_emit((unsigned)((P + KW * kEmitWaves - 1) / (KW * kEmitWaves)), (unsigned)B);
   switch (mode) {
     case kModeDenseVec4: {
       // Store policy of the dense tensor.  Write-through (sc1) stores leave no dirty lines for the
-      // end-of-kernel write-back: on k_emit's store pattern alone (tools/lab/fill_pattern.cpp) 43.2 MB take
+      // end-of-kernel write-back: on k_emit's store pattern alone (profiles/r02/NOTES.md) 43.2 MB take
       // 6.3 us against 7.4 us plain, 172.8 MB 20.8 / 22.6 us, 432 MB (beyond the Infinity Cache) 84 / 80 us.
       // In k_emit itself: 43.2 MB 10.4 / 11.5 us, 108 MB 21.5 / 22.0 us, 172.8 MB 29.3 / 29.0 us -- the
       // larger launches are not bound by their tail.  Write-through up to 128 MB.
-      static const int forced = [] {  // development knob: PP_EMIT_SC1=0/1
-        const char *e = getenv("PP_EMIT_SC1");
-        return e ? (atoi(e) ? 1 : 0) : -1;
-      }();
-      const bool sc1 = forced >= 0 ? forced == 1 : (size_t)B * 36u * (size_t)P * (size_t)N <= kSc1MaxBytes;
+      const bool sc1 = (size_t)B * 36u * (size_t)P * (size_t)N <= kSc1MaxBytes;
       if (sc1)
         hipExtLaunchKernelGGL((k_emit<TIn, kModeDenseVec4, kAuxSc1>), grid_emit, dim3(kEmitThreads), 0, stream,
                               ev0[PP_KERNEL_EMIT], ev1[PP_KERNEL_EMIT], 0, a);
@@ -2362,26 +2247,6 @@ __global__ __launch_bounds__(kCopyThreads) void k_records_to_host(const int2 *to
 }  // namespace pp
 
 using namespace pp;
-
-#ifdef PP_STAMPS
-// development builds only (tools/lab): streamed_means' slowest wave {total, chains, staging (shader clocks), steps, rounds}
-extern "C" int pp_debug_means_prof(unsigned long long *host, int reset) {
-  if (hipMemcpyFromSymbol(host, HIP_SYMBOL(pp::g_means_prof), sizeof pp::g_means_prof) != hipSuccess) return -1;
-  if (reset) {
-    unsigned long long z[8] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(pp::g_means_prof), z, sizeof z) != hipSuccess) return -1;
-  }
-  return 0;
-}
-// development builds only (tools/lab): k_tile's phase stamps of sweep 0, 8 per wave
-extern "C" int pp_debug_stamps(pp_ctx_t *ctx, unsigned long long *host, int cap) {
-  const size_t n = std::min((size_t)cap * 8, ctx->dbg_stamps_bytes);
-  if (hipMemcpy(host, static_cast<char *>(ctx->vox_ws[0].ptr) + ctx->dbg_stamps_off, n,
-                hipMemcpyDeviceToHost) != hipSuccess)
-    return -1;
-  return (int)(n / 8);
-}
-#endif
 
 extern "C" int pp_voxelize_check(pp_ctx_t *ctx, void *stream_) {
   if (!ctx) {
@@ -2729,30 +2594,17 @@ static int step_impl(pp_ctx_t *ctx, void *stream_, const float *points_dev, int6
   if (a.emit_nbx == 0) a.emit_nbx = 1;
   // The tile role takes its tiles XCD by XCD (tile_of_block) once its gathers are beyond what the L2s keep anyway: at
   // BASELINE config 5 (800k points per launch: 16 MB of split records) k_step's FETCH_SIZE halves, 56.9 -> 29.0 MiB, and the
-  // launch is 1.5-4 us shorter (five alternations on two boxes, tools/lab/knobs_c5.sh / knobs_shapes.sh); at configs[1]'s
+  // launch is 1.5-4 us shorter (five alternations on two boxes, profiles/r06/NOTES.md section 5); at configs[1]'s
   // 240k points (4.8 MB, which every XCD's 4 MB L2 nearly holds) it measures the same to 0.2-0.4 us worse: tile = block.
-  static const int tile_xcd = [] {  // development knob: PP_STEP_TILE_XCD=0/1 (unset: by size)
-    const char *e = getenv("PP_STEP_TILE_XCD");
-    return e ? (atoi(e) ? 1 : 0) : -1;
-  }();
-  a.tile_xcd_map = tile_xcd >= 0 ? tile_xcd
-                                 : (sb_tile.valid && (size_t)sb_tile.batch * (size_t)sb_tile.maxn * 20u > kTileXcdMapBytes);
-  static const int pref_blocks = [] {  // development knob: PP_STEP_PREFETCH=<workgroups> (0 = off)
-    const char *e = getenv("PP_STEP_PREFETCH");
-    return e ? std::max(0, atoi(e)) : 128;
-  }();
-  static const int mix_env = [] {  // development knob: PP_STEP_MIX=m (1 = binning blocks first)
-    const char *e = getenv("PP_STEP_MIX");
-    return e ? std::max(1, atoi(e)) : 0;
-  }();
+  a.tile_xcd_map = sb_tile.valid && (size_t)sb_tile.batch * (size_t)sb_tile.maxn * 20u > kTileXcdMapBytes;
   // A call CAN go out as several launches of a few sweeps each (sweeps are independent, so every role's
   // batch splits the same way).  Round 3's driver line suggested it should when the dense output exceeds the
   // 256 MB Infinity Cache: per sweep, one 172.8 MB sweep per launch ran at 0.73 of the roofline, four in
-  // one launch at 0.64.  Measured in round 4 (tools/lab/sweep_sub.sh): four launches of one sweep each take
+  // one launch at 0.64.  Measured in round 4 (profiles/r04/NOTES.md): four launches of one sweep each take
   // 154 us against 146 us for the one launch -- the one-sweep figure came from re-writing the SAME 172.8 MB
   // buffer call after call, which the memory-side cache absorbs; four launches writing four different
   // regions go to HBM like the single launch does, and pay three more launch ramps.  Default: one launch.
-  static const size_t sub_bytes = [] {  // development knob: PP_STEP_SUB_MB (dense MB per launch; 0 = never split)
+  static const size_t sub_bytes = [] {  // PP_STEP_SUB_MB: dense MB per launch (0 = never split); the test of the split form sets it
     const char *e = getenv("PP_STEP_SUB_MB");
     return e ? (size_t)std::max(0, atoi(e)) << 20 : kStepLaunchBytes;
   }();
@@ -2784,28 +2636,8 @@ static int step_impl(pp_ctx_t *ctx, void *stream_, const float *points_dev, int6
     a.split_b0 = sb;
     a.n_split_blocks = sb_new.valid ? whole.s.nchunks * sn : 0;
     a.emit_b0 = eb;
-#ifdef PP_STEP_SKIP_KNOB  // tools/lab timing builds only (results are garbage): PP_STEP_SKIP = bit mask of roles left out
-    {
-      static const int skip_all = [] { const char *e = getenv("PP_STEP_SKIP"); return e ? atoi(e) : 0; }();
-      // PP_STEP_SKIP_AFTER=n: the first n launches run every role (the slots then hold real lists of the SAME cloud)
-      static const int skip_after = [] { const char *e = getenv("PP_STEP_SKIP_AFTER"); return e ? atoi(e) : 0; }();
-      static int launches = 0;
-      const int skip = ++launches > skip_after ? skip_all : 0;
-      if (skip & 1) a.n_tile_blocks = 0;
-      if (skip & 2) a.n_order_blocks = 0;
-      if (skip & 4) a.n_split_blocks = 0;
-      if (skip & 8) a.n_unscatter_blocks = 0;   // the fused form's clear role
-      if (skip & 16) en = 0;                    // the emit role: what the binning (and clear) roles take by themselves
-    }
-#endif
     const int n_emit = whole.emit_nbx * en;
-    if (sb_emit.valid && !pfn) {
-      static const int forced = [] {  // development knob: PP_EMIT_SC1=0/1
-        const char *e = getenv("PP_EMIT_SC1");
-        return e ? (atoi(e) ? 1 : 0) : -1;
-      }();
-      sc1 = forced >= 0 ? forced == 1 : (size_t)en * 36u * (size_t)a.e.P * (size_t)a.e.N <= kSc1MaxBytes;
-    }
+    if (sb_emit.valid && !pfn) sc1 = (size_t)en * 36u * (size_t)a.e.P * (size_t)a.e.N <= kSc1MaxBytes;
     {
       int r = 0;
       auto add = [&](const void *ptr, size_t per_sweep, int lo, int n) {
@@ -2814,38 +2646,17 @@ static int step_impl(pp_ctx_t *ctx, void *stream_, const float *points_dev, int6
         ++r;
       };
       std::memset(&a.pf, 0, sizeof a.pf);
-      // Only the EMIT role's arrays are worth it (tools/lab/prefetch_sets.sh, round 4): its blocks start after the
+      // Only the EMIT role's arrays are worth it (round 4, profiles/r04/NOTES.md): its blocks start after the
       // binning blocks, so the lines are there when they ask.  The binning roles' own inputs (the order role's
       // lists, the tile role's split arrays, the split role's points) were in this list while binning and emit
       // blocks alternated; with the binning blocks FIRST they start in the same microsecond as the prefetch
       // blocks and fetch for themselves -- the prefetch only doubled that traffic (headline 34.9 -> 33.7 us
       // without, C5 B=4 111-118 -> 104-109 us).
-      static const int pref_sets = [] {  // development knob: PP_STEP_PREFETCH_SETS = mask {1 emit, 2 order, 4 tile} arrays
-        const char *e = getenv("PP_STEP_PREFETCH_SETS");
-        return e ? atoi(e) : 1;
-      }();
-      if (pref_blocks > 0 && en > 0 && (pref_sets & 1)) {   // what the emit role reads
+      if (en > 0) {   // what the emit role reads
         add(a.e.ordered_meta, (size_t)a.e.P * 16, eb, en);
         add(a.e.sorted_pts, (size_t)a.e.ncap * 16, eb, en);
       }
-      if (pref_blocks > 0 && on > 0 && (pref_sets & 2)) {  // ... the order role: the occupied heads of the tiles' lists
-        a.pf.tile_agg = a.o.tile_agg + (size_t)ob * nt_o;
-        a.pf.tile_meta = a.o.tile_meta + ((size_t)ob * nt_o << a.o.g.tile_shift);
-        a.pf.nlists = on * nt_o;
-        a.pf.list_stride = 1 << a.o.g.tile_shift;
-      }
-      if (pref_blocks > 0 && tn > 0 && (pref_sets & 4)) {   // what the tile role reads
-        add(a.t.mat, (size_t)nt_t * a.t.nchunks_cap * 8, tb, tn);
-        add(a.t.kslot, (size_t)a.t.ncap * 4, tb, tn);
-        add(a.t.kpts, (size_t)a.t.ncap * 16, tb, tn);
-      }
-      static const int pref_points = [] {  // development knob: PP_STEP_PREFETCH_POINTS=0/1
-        const char *e = getenv("PP_STEP_PREFETCH_POINTS");
-        return e ? atoi(e) : 0;
-      }();
-      if (pref_blocks > 0 && sn > 0 && pref_points)   // ... and the split role: the caller's points
-        add(a.s.pts, (size_t)a.s.sweep_stride * 16, sb, sn);
-      a.n_pref_blocks = r > 0 || a.pf.nlists > 0 ? pref_blocks : 0;
+      a.n_pref_blocks = r > 0 ? kStepPrefetchBlocks : 0;
     }
     if (mode != kModePfn) a.n_unscatter_blocks = 0;
     const long long nblocks = (long long)a.n_pref_blocks + a.n_unscatter_blocks + a.n_tile_blocks + a.n_order_blocks +
@@ -2861,7 +2672,7 @@ static int step_impl(pp_ctx_t *ctx, void *stream_, const float *points_dev, int6
       // n_emit / nbin emit blocks (C5 B=4, 3 400 binning blocks against 7 500: one per two, 117-121 -> 104-109 us;
       // one per one and one per three are both worse).
       const int mix_auto = nbin > kStepChipSlots && n_emit > 0 ? std::max(2, n_emit / nbin + 1) : 1;
-      a.mix = mix_env ? mix_env : mix_auto;
+      a.mix = mix_auto;
       a.mix_groups = a.mix > 1 ? std::min(nbin, n_emit / (a.mix - 1)) : 0;
       if (a.mix < 2) a.mix = 2, a.mix_groups = 0;
     }
@@ -2972,7 +2783,7 @@ extern "C" int pp_voxelize_step_kernel_name(const pp_voxel_params_t *prm, int ba
   }
   const int N = prm->max_points_per_pillar;
   const int mode = (N % 4 == 0 && N <= 4096) ? kModeDenseVec4 : kModeDenseScalar;
-  // the same rule as step_impl's (one launch per call: the development knobs PP_EMIT_SC1 / PP_STEP_SUB_MB aside)
+  // the same rule as step_impl's (one launch per call, PP_STEP_SUB_MB aside)
   const bool sc1 = mode == kModeDenseVec4 &&
                    (size_t)batch * 36u * (size_t)prm->max_pillars * (size_t)N <= kSc1MaxBytes;
   std::snprintf(name, (size_t)cap, "pp::k_step<%d, %d>", mode, sc1 ? kAuxSc1 : kAuxPlain);
@@ -3141,16 +2952,6 @@ extern "C" int pp_create_pillars_f64(pp_ctx_t *ctx, const void *points, int64_t 
   if (rc) return rc;
   if (num_cells) *num_cells = 0;
   if (n_points == 0) return PP_OK;
-  static const bool trace = getenv("PP_DROPIN_TRACE") != nullptr;  // development knob: where a call's time goes
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto t_prev = now();
-  double t_sec[6] = {0, 0, 0, 0, 0, 0};
-  auto lap = [&](int k) {
-    if (!trace) return;
-    const auto t = now();
-    t_sec[k] += std::chrono::duration<double, std::micro>(t - t_prev).count();
-    t_prev = t;
-  };
   const int n = (int)n_points;
   const int max_pillars = std::max(prm->max_pillars, 0);
   const int N = std::max(prm->max_points_per_pillar, 0);
@@ -3162,17 +2963,13 @@ extern "C" int pp_create_pillars_f64(pp_ctx_t *ctx, const void *points, int64_t 
   rc = ctx->pin_in.ensure((size_t)n * 32);
   if (rc) return rc;
   HostPool *pool = host_pool(ctx);
-  // development knobs of the host path (defaults: what tools/lab/dropin_trace.py measured best -- profiles/r06/NOTES.md:
-  // 8 threads, one host-to-device copy, the features back in two chunks, polled waits, f32 transport of f32-valued
-  // clouds: 0.36 -> 0.19 ms per call; sending the features AHEAD of the descriptors, PP_DROPIN_SPEC=1, measured no gain)
-  static const int k_h2d_parts = [] { const char *e = getenv("PP_DROPIN_H2D_PARTS"); return e ? std::max(1, std::min(8, atoi(e))) : 1; }();
-  static const int k_chunks = [] { const char *e = getenv("PP_DROPIN_CHUNKS"); return e ? std::max(1, std::min(8, atoi(e))) : 2; }();
-  static const bool k_spec = [] { const char *e = getenv("PP_DROPIN_SPEC"); return e ? atoi(e) != 0 : false; }();
-  static const bool k_spin = [] { const char *e = getenv("PP_DROPIN_SPIN"); return e ? atoi(e) != 0 : true; }();
+  // The shape of the host path is what measured best (profiles/r06/NOTES.md: 8 threads, one host-to-device copy, the
+  // features back in two chunks, polled waits, f32 transport of f32-valued clouds: 0.36 -> 0.19 ms per call; sending the
+  // features AHEAD of the descriptors, sized by the previous call's count, measured no gain).
+  constexpr int kChunks = 2;  // pieces the features come back in: one is scattered while the next is on its way
   // A call waits for the device two or three times, for tens of microseconds each: polled, not slept on (an interrupt-driven
   // wake-up costs about as much as the wait itself).
   auto wait_event = [&](hipEvent_t ev) -> hipError_t {
-    if (!k_spin) return hipEventSynchronize(ev);
     for (;;) {
       const hipError_t e = hipEventQuery(ev);
       if (e != hipErrorNotReady) return e;
@@ -3189,13 +2986,13 @@ extern "C" int pp_create_pillars_f64(pp_ctx_t *ctx, const void *points, int64_t 
   // test rides on the gather; one value that does not survive (or a first gather that found one) and the call takes
   // the f64-input kernels as before.  (NaN compares unequal to itself and counts as surviving: both kernel families
   // drop the point.)
-  static const bool k_try_f32 = [] { const char *e = getenv("PP_DROPIN_F32"); return e ? atoi(e) != 0 : true; }();
   // ... and on the way back such a cloud's x, y, z, intensity columns travel as the floats they are (56 bytes a point
-  // instead of 72; the scatter widens them): store_compact_features.  PP_DROPIN_PACK=0: nine doubles as before.
+  // instead of 72; the scatter widens them): store_compact_features.  PP_DROPIN_PACK=0: nine doubles (the transport test
+  // compares both).
   static const bool k_pack = [] { const char *e = getenv("PP_DROPIN_PACK"); return e ? atoi(e) != 0 : true; }();
   const char *src_pts = static_cast<const char *>(points);
-  bool as_f32 = k_try_f32;
-  if (as_f32) {
+  bool as_f32;
+  {
     float *dst = static_cast<float *>(ctx->pin_in.ptr);
     std::atomic<int> lossy{0};
     pool->run([&](int part, int parts) {
@@ -3239,7 +3036,6 @@ extern "C" int pp_create_pillars_f64(pp_ctx_t *ctx, const void *points, int64_t 
   std::memset(&np, 0, sizeof np);
   np.n[0] = n;
   if (as_f32) {
-    lap(0);
     const float *pts_dev = static_cast<const float *>(ctx->stage_in.ptr);
     void *mapped = nullptr;
     if ((k_direct & 1) && hipHostGetDevicePointer(&mapped, ctx->pin_in.ptr, 0) == hipSuccess && mapped)
@@ -3253,22 +3049,15 @@ extern "C" int pp_create_pillars_f64(pp_ctx_t *ctx, const void *points, int64_t 
     if (rc) return rc;
   } else {
     // the caller's points are a strided view (data/dataset.py:88 passes the transpose of a [4, n] array): rows split
-    // across the pool's threads; a part's host-to-device copy runs under the next part's gather
+    // across the pool's threads, then one host-to-device copy
     double *dst = static_cast<double *>(ctx->pin_in.ptr);
-    const int parts_h2d = n >= 8192 ? k_h2d_parts : 1;
-    for (int h = 0; h < parts_h2d; ++h) {
-      const int64_t r0 = (int64_t)n * h / parts_h2d, r1 = (int64_t)n * (h + 1) / parts_h2d;
-      pool->run([&](int part, int parts) {
-        const int64_t i0 = r0 + (r1 - r0) * part / parts, i1 = r0 + (r1 - r0) * (part + 1) / parts;
-        for (int64_t i = i0; i < i1; ++i)
-          for (int c = 0; c < 4; ++c)
-            std::memcpy(&dst[i * 4 + c], src_pts + i * ps0 + c * ps1, 8);
-      });
-      if (r1 > r0)
-        PP_HIP_TRY(hipMemcpyAsync(static_cast<char *>(ctx->stage_in.ptr) + r0 * 32, dst + r0 * 4, (size_t)(r1 - r0) * 32,
-                                  hipMemcpyHostToDevice, stream));
-    }
-    lap(0);
+    pool->run([&](int part, int parts) {
+      const int64_t i0 = (int64_t)n * part / parts, i1 = (int64_t)n * (part + 1) / parts;
+      for (int64_t i = i0; i < i1; ++i)
+        for (int c = 0; c < 4; ++c)
+          std::memcpy(&dst[i * 4 + c], src_pts + i * ps0 + c * ps1, 8);
+    });
+    PP_HIP_TRY(hipMemcpyAsync(ctx->stage_in.ptr, dst, (size_t)n * 32, hipMemcpyHostToDevice, stream));
     rc = launch_pipeline<double>(ctx, stream, static_cast<const double *>(ctx->stage_in.ptr),
                                  l.ncap, 4, 1, 1, np, 1, n, g, P, N, l, kModeCompact, nullptr,
                                  nullptr, static_cast<double *>(ctx->stage_out.ptr), false,
@@ -3283,9 +3072,9 @@ extern "C" int pp_create_pillars_f64(pp_ctx_t *ctx, const void *points, int64_t 
   if (!meta_direct) PP_HIP_TRY(hipMemcpyAsync(pm, ws + l.meta, meta_bytes, hipMemcpyDeviceToHost, stream));
   hipEvent_t ev_meta = ctx->chunk_ev[kMaxEv - 1];
   PP_HIP_TRY(hipEventRecord(ev_meta, stream));
-  // The features follow WITHOUT waiting for the descriptors: how many points the call emits is only known from them, so
-  // the copy is sized by what the previous call of this shape emitted (consecutive sweeps are alike) plus an eighth,
-  // and topped up below when that was short.  In chunks: chunk k is scattered while chunk k + 1 is on its way.
+  // The features follow in chunks: chunk k is scattered while chunk k + 1 is on its way.  How many points the call emits
+  // is only known from the descriptors: the device reads them itself (the direct pieces), or the copies are issued once
+  // the host has them.
   const bool packed = as_f32 && k_pack;
   const int64_t rec = packed ? kPackedFeat : 72;  // bytes of a point's features on the way back
   int64_t cb[kMaxEv + 1];  // chunk c = compact points [cb[c], cb[c + 1])
@@ -3296,7 +3085,7 @@ extern "C" int pp_create_pillars_f64(pp_ctx_t *ctx, const void *points, int64_t 
   {
     void *out_dev = nullptr;
     if ((k_direct & 4) && N > 0 && hipHostGetDevicePointer(&out_dev, ctx->pin_out.ptr, 0) == hipSuccess && out_dev) {
-      direct_pieces = (int64_t)n * rec >= (256 << 10) ? k_chunks : 1;
+      direct_pieces = (int64_t)n * rec >= (256 << 10) ? kChunks : 1;
       const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(256, ((int64_t)n * rec / direct_pieces + 16 * kCopyThreads - 1) /
                                                                                (16 * kCopyThreads)));
       for (int c = 0; c < direct_pieces; ++c) {
@@ -3323,25 +3112,17 @@ extern "C" int pp_create_pillars_f64(pp_ctx_t *ctx, const void *points, int64_t 
     }
     return PP_OK;
   };
-  if (!direct_pieces && k_spec && N > 0 && ctx->dropin_last_n == n && ctx->dropin_last_end > 0) {
-    const int64_t guess = std::min<int64_t>(n, ctx->dropin_last_end + ctx->dropin_last_end / 8);
-    rc = issue_chunks(guess, guess * rec >= (256 << 10) ? k_chunks : 1);
-    if (rc) return rc;
-  }
   PP_HIP_TRY(wait_event(ev_meta));
-  lap(1);
   int tot[2];
   std::memcpy(tot, pm + (l.totals - l.meta), 8);
   if (num_cells) *num_cells = tot[0];
   const int npil = std::min(tot[0], std::min(P, max_pillars));
   if (npil == 0) {
-    if (nch || direct_pieces) PP_HIP_TRY(hipStreamSynchronize(stream));  // copies sent ahead still target the pinned buffer
+    if (direct_pieces) PP_HIP_TRY(hipStreamSynchronize(stream));  // the pieces sent ahead still target the pinned buffer
     return PP_OK;
   }
   const int4 *meta = reinterpret_cast<const int4 *>(pm);
   const int64_t end = (int64_t)meta[npil - 1].y + meta[npil - 1].z;
-  ctx->dropin_last_n = n;
-  ctx->dropin_last_end = end;
   const char *feat = static_cast<const char *>(ctx->pin_out.ptr);
   // `live` points' features from compact position `at` into a dense [live][9] run of doubles
   auto copy_rows = [&](char *dst, int64_t at, int live) {
@@ -3383,13 +3164,9 @@ extern "C" int pp_create_pillars_f64(pp_ctx_t *ctx, const void *points, int64_t 
   if (direct_pieces) {  // the device cut [0, end) at the same places
     nch = direct_pieces;
     for (int c = 0; c <= nch; ++c) cb[c] = piece_begin(end, c, nch);
-  } else if (N > 0 && cb[nch] < end) {  // nothing sent ahead, or the guess was short: the rest
-    rc = issue_chunks(end, (dense_all && (end - cb[nch]) * rec >= (256 << 10)) ? k_chunks : 1);
+  } else if (N > 0 && end > 0) {
+    rc = issue_chunks(end, (dense_all && end * rec >= (256 << 10)) ? kChunks : 1);
     if (rc) return rc;
-    if (cb[nch] < end) {  // (out of events: cannot happen with k_chunks <= 8 / 2)
-      set_error("create_pillars: internal: chunk events exhausted");
-      return PP_ERR_INTERNAL;
-    }
   }
   if (dense_all) {
     int p_done = 0;
@@ -3426,15 +3203,10 @@ extern "C" int pp_create_pillars_f64(pp_ctx_t *ctx, const void *points, int64_t 
         }
       });
     }
-    if (nch) PP_HIP_TRY(wait_event(ctx->chunk_ev[nch - 1]));  // (a copy sent ahead may reach beyond `end`)
-    lap(2);
-    if (trace)
-      fprintf(stderr, "pp_create_pillars_f64: gather + H2D issue (%d parts) %.0f us | kernels + descriptors back %.0f | features back in %d chunks + scatter on %d threads %.0f\n",
-              n >= 8192 ? k_h2d_parts : 1, t_sec[0], t_sec[1], nch, pool->size(), t_sec[2]);
+    if (nch) PP_HIP_TRY(wait_event(ctx->chunk_ev[nch - 1]));  // (the loop may have skipped the later events)
     return PP_OK;
   }
   if (nch) PP_HIP_TRY(hipStreamSynchronize(stream));
-  lap(2);
   // any other layout (strided views, undersized arrays): one thread, element by element with pybind11 .mutable_at()'s
   // bounds checks, pillar by pillar like pillars.cpp:335-396 -- the writes made before an IndexError persist, nothing
   // behind it is touched
@@ -3460,9 +3232,5 @@ extern "C" int pp_create_pillars_f64(pp_ctx_t *ctx, const void *points, int64_t 
     }
     write_index_row(p);
   }
-  lap(3);
-  if (trace)
-    fprintf(stderr, "pp_create_pillars_f64: gather %.0f us | H2D + kernels + descriptors back %.0f | features back %.0f | scatter %.0f\n",
-            t_sec[0], t_sec[1], t_sec[2], t_sec[3]);
   return PP_OK;
 }
