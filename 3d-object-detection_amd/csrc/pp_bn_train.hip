@@ -5,9 +5,9 @@
 // backward 180 us on a 64 MB activation) + a ReLU-backward kernel, and keeps both the conv
 // output and the ReLU output for the backward.  Here:
 //
-//   forward   pass 1  per-channel sum / sum of squares of r = max(z + b, 0), taken about the
-//                     channel's first activation (shifted data: no cancellation)  (k_rbn_stats)
-//             pass 2  y = s*r + t with s = gamma*invstd, t = beta - mean*s; the first slice
+//   forward   pass 1  per-channel sum / sum of squares of r = max(z + b, 0), taken about the mean
+//                     of a 64-element sample of the channel (shifted data: no cancellation)  (k_rbn_stats)
+//             pass 2  y = s*(r - mean) + beta with s = gamma*invstd; the first slice
 //                     of every channel also updates the running statistics   (k_rbn_apply)
 //   backward  pass 1  dbeta = sum dy, dgamma = sum dy*xhat (+ three sums for db)  (k_rbn_bwd_stats)
 //             pass 2  dz = [z > 0] * s * (dy - dbeta/M - xhat*dgamma/M)     (k_rbn_bwd_apply)
@@ -86,11 +86,28 @@ __device__ __forceinline__ void rbn_store_partials(double *__restrict__ part, in
   }
 }
 
-// The statistics are summed about a provisional value of the channel (shifted data): the
-// activation of its first element.  On the sparse BEV canvas most of a plane sits at exactly
-// that value, and E[r^2] - E[r]^2 would otherwise cancel.
+// The statistics are summed about a provisional value of the channel (shifted data), or
+// E[r^2] - E[r]^2 would cancel: the mean of up to 64 activations spread evenly over the channel's
+// batch*HW elements (the first one among them).  One element alone can be an outlier -- clamped to
+// 0 by the ReLU while the bulk sits at 50 +- 0.05 -- and the sums cancel again; a sample mean lies
+// within a fraction of the channel's spread of its mean.  On the sparse BEV canvas the sampled
+// pixels are mostly (often all) empty, and 64 equal values average to exactly that value.
+// Every wave loads the same 64 elements and adds them in the same butterfly: the value is
+// identical in all waves, all workgroups and both kernels of a call.  y must not alias z: k_rbn_apply
+// reads the sampled elements of z again while other workgroups already write y.
 __device__ __forceinline__ float rbn_shift(const float *__restrict__ z, float bc, int c, const RbnGeom &g) {
-  return fmaxf(z[(int64_t)c * g.HW] + bc, 0.0f);
+  const int64_t M = (int64_t)g.B * g.HW;
+  const int n = (int)(M < 64 ? M : 64);
+  const int lane = threadIdx.x & 63;
+  float v = 0.0f;
+  if (lane < n) {
+    const int64_t j = M * lane / n;  // < 2^46
+    const int64_t b = j / g.HW;
+    v = fmaxf(z[(b * g.C + c) * g.HW + (j - b * g.HW)] + bc, 0.0f);
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  return v / (float)n;
 }
 
 // f(offset in z / y / dz, offset in dy, elements)
@@ -152,8 +169,12 @@ __global__ __launch_bounds__(kRbnThreads) void k_rbn_apply(
   double var = v[1] / M - dm * dm;  // biased: what BatchNorm normalises with
   var = var > 0.0 ? var : 0.0;
   const double invstd = 1.0 / sqrt(var + eps);
+  // y = (r - mu)*sc + sh with mu the f32 mean and sh = beta - (mean - mu)*gamma*invstd: the form s*r + t
+  // loses ulp(mean*gamma*invstd), which is large against y where the spread of a channel is small against
+  // its mean (a constant channel has invstd = 1/sqrt(eps))
+  const float mu = (float)mean;
   const float sc = (float)((double)gamma[c] * invstd);
-  const float sh = (float)((double)beta[c] - mean * (double)gamma[c] * invstd);
+  const float sh = (float)((double)beta[c] - (mean - (double)mu) * (double)gamma[c] * invstd);
   if (s == 0 && threadIdx.x == 0) {
     mean_out[c] = (float)mean;
     invstd_out[c] = (float)invstd;
@@ -166,13 +187,13 @@ __global__ __launch_bounds__(kRbnThreads) void k_rbn_apply(
   rbn_foreach(g, c, s, [&](int64_t o, int64_t od, int n) {
     if (n == 4) {
       float4 q = *reinterpret_cast<const float4 *>(z + o);
-      q.x = fmaf(fmaxf(q.x + bc, 0.0f), sc, sh);
-      q.y = fmaf(fmaxf(q.y + bc, 0.0f), sc, sh);
-      q.z = fmaf(fmaxf(q.z + bc, 0.0f), sc, sh);
-      q.w = fmaf(fmaxf(q.w + bc, 0.0f), sc, sh);
+      q.x = fmaf(fmaxf(q.x + bc, 0.0f) - mu, sc, sh);
+      q.y = fmaf(fmaxf(q.y + bc, 0.0f) - mu, sc, sh);
+      q.z = fmaf(fmaxf(q.z + bc, 0.0f) - mu, sc, sh);
+      q.w = fmaf(fmaxf(q.w + bc, 0.0f) - mu, sc, sh);
       *reinterpret_cast<float4 *>(y + o) = q;
     } else {
-      y[o] = fmaf(fmaxf(z[o] + bc, 0.0f), sc, sh);
+      y[o] = fmaf(fmaxf(z[o] + bc, 0.0f) - mu, sc, sh);
     }
   });
 }

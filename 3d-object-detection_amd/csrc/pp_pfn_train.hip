@@ -67,13 +67,19 @@ __device__ __forceinline__ void tr_flush(const float (&acc)[K], float (*s_red)[K
   }
 }
 
-// x [B][9][P][N]; wb [64][10] {w[0..8], bias}; part [gridDim.x][21][64]
+// x [B][9][P][N]; wb [64][10] {w[0..8], bias}; part [gridDim.x][21][64]; part_d [gridDim.x][2][64]
+// The two sums the variance comes from, sum (r-c0) and sum (r-c0)^2, are carried in f64 from the lane to
+// the result (part_d; their rows of part are not read): on a dense cloud far from the origin r - c0 is
+// large against its spread, E[(r-c0)^2] - E[r-c0]^2 cancels two hundredfold, and f32 accumulators (or
+// f32 partials: batch*P*N == 1 has one term) left invstd wrong by 5e-4 .. 1.4e-3.
 __global__ __launch_bounds__(kTrWaves * 64) void k_pfn_train_stats(const float *__restrict__ x,
                                                                    const float *__restrict__ wb,
-                                                                   float *__restrict__ part, int B,
+                                                                   float *__restrict__ part,
+                                                                   double *__restrict__ part_d, int B,
                                                                    int P, int N) {
   __shared__ float s_x[kTrWaves][9][kTrChunk];
   __shared__ float s_red[kTrWaves][kTrStats][kTrC];
+  __shared__ double s_red_d[kTrWaves][2][kTrC];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float(*sx)[kTrChunk] = s_x[wave];
@@ -88,6 +94,7 @@ __global__ __launch_bounds__(kTrWaves * 64) void k_pfn_train_stats(const float *
   float acc[kTrStats];
 #pragma unroll
   for (int k = 0; k < kTrStats; ++k) acc[k] = 0.0f;
+  double sum_d = 0.0, sq_d = 0.0;
   const int64_t plane = (int64_t)P * N;
   // the points of one sweep are one contiguous span of P*N floats in every feature row
   const int64_t span = plane;
@@ -111,10 +118,10 @@ __global__ __launch_bounds__(kTrWaves * 64) void k_pfn_train_stats(const float *
       const float z = tr_z(A, xv);
       const float r = fmaxf(z, 0.0f);
       const float mk = z > 0.0f ? 1.0f : 0.0f;
-      const float rs = r - c0;  // exactly 0 on a zero-padded slot
+      const double rs = (double)r - (double)c0;  // exactly 0 on a zero-padded slot
       acc[0] += mk;
-      acc[1] += rs;
-      acc[2] = fmaf(rs, rs, acc[2]);
+      sum_d += rs;
+      sq_d = fma(rs, rs, sq_d);
 #pragma unroll
       for (int d = 0; d < 9; ++d) {
         acc[3 + d] = fmaf(mk, xv[d], acc[3 + d]);
@@ -123,15 +130,39 @@ __global__ __launch_bounds__(kTrWaves * 64) void k_pfn_train_stats(const float *
     }
     tr_wave_sync();
   }
-  tr_flush<kTrStats>(acc, s_red, wave, lane, part);
+  s_red_d[wave][0][lane] = sum_d;
+  s_red_d[wave][1][lane] = sq_d;
+  tr_flush<kTrStats>(acc, s_red, wave, lane, part);  // its barrier orders s_red_d too
+  if (threadIdx.x < 2 * kTrC) {
+    const int k = threadIdx.x / kTrC, c = threadIdx.x - k * kTrC;
+    double v = 0.0;
+#pragma unroll
+    for (int w = 0; w < kTrWaves; ++w) v += s_red_d[w][k][c];
+    part_d[((int64_t)blockIdx.x * 2 + k) * kTrC + c] = v;
+  }
 }
 
 // part [nwg][K][64] f32 -> sums [K][64] f64; one workgroup per k: 16 row groups x 64 channels,
-// four independent accumulators per thread (the loads are a latency chain otherwise)
+// four independent accumulators per thread (the loads are a latency chain otherwise).  With part_d
+// (the statistics) rows 1 and 2 come from the f64 partials part_d [nwg][2][64] instead.
 __global__ __launch_bounds__(1024) void k_pfn_train_reduce(const float *__restrict__ part, int nwg, int K,
-                                                           double *__restrict__ sums) {
+                                                           double *__restrict__ sums,
+                                                           const double *__restrict__ part_d) {
   __shared__ double s[16][kTrC];
   const int k = blockIdx.x, c = threadIdx.x & 63, q = threadIdx.x >> 6;
+  if (part_d && (k == 1 || k == 2)) {
+    double v = 0.0;
+    for (int w = q; w < nwg; w += 16) v += part_d[((int64_t)w * 2 + (k - 1)) * kTrC + c];
+    s[q][c] = v;
+    __syncthreads();
+    if (q == 0) {
+      double t = 0.0;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) t += s[i][c];
+      sums[k * kTrC + c] = t;
+    }
+    return;
+  }
   double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
   const float *p = part + (int64_t)k * kTrC + c;
   const int64_t stride = (int64_t)K * kTrC;
@@ -258,12 +289,15 @@ extern "C" int pp_pfn_train_stats_dev(pp_ctx_t *ctx, void *stream_, const float 
   hipStream_t st = static_cast<hipStream_t>(stream_);
   const int64_t span = (int64_t)max_pillars * max_points_per_pillar;
   const int nwg = tr_grid(((span + kTrChunk - 1) / kTrChunk) * batch);
-  rc = ctx->pfn_ws.ensure((size_t)kTrMaxWg * kTrStats * kTrC * sizeof(float));
+  const size_t part_bytes = (size_t)kTrMaxWg * kTrStats * kTrC * sizeof(float);  // a multiple of 8
+  rc = ctx->pfn_ws.ensure(part_bytes + (size_t)kTrMaxWg * 2 * kTrC * sizeof(double));
   if (rc) return rc;
   float *part = static_cast<float *>(ctx->pfn_ws.ptr);
+  double *part_d = reinterpret_cast<double *>(static_cast<char *>(ctx->pfn_ws.ptr) + part_bytes);
   hipLaunchKernelGGL(k_pfn_train_stats, dim3(nwg), dim3(kTrWaves * 64), 0, st, pillars_dev,
-                     weight_bias_dev, part, batch, max_pillars, max_points_per_pillar);
-  hipLaunchKernelGGL(k_pfn_train_reduce, dim3(kTrStats), dim3(1024), 0, st, part, nwg, kTrStats, sums_dev);
+                     weight_bias_dev, part, part_d, batch, max_pillars, max_points_per_pillar);
+  hipLaunchKernelGGL(k_pfn_train_reduce, dim3(kTrStats), dim3(1024), 0, st, part, nwg, kTrStats, sums_dev,
+                     static_cast<const double *>(part_d));
   PP_HIP_TRY(hipGetLastError());
   return PP_OK;
 }
@@ -301,7 +335,8 @@ extern "C" int pp_pfn_train_backward_dev(pp_ctx_t *ctx, void *stream_, const flo
   hipLaunchKernelGGL(k_pfn_train_bwd, dim3(nwg), dim3(kTrWaves * 64), 0, st, pillars_dev, pfn_params_dev,
                      mean_dev, invstd_dev, grad_out_dev, part, batch, max_pillars,
                      max_points_per_pillar);
-  hipLaunchKernelGGL(k_pfn_train_reduce, dim3(kTrBwd), dim3(1024), 0, st, part, nwg, kTrBwd, sums_dev);
+  hipLaunchKernelGGL(k_pfn_train_reduce, dim3(kTrBwd), dim3(1024), 0, st, part, nwg, kTrBwd, sums_dev,
+                     static_cast<const double *>(nullptr));
   PP_HIP_TRY(hipGetLastError());
   return PP_OK;
 }

@@ -2,7 +2,9 @@
 (tests/eval_restatement.py): the IoU kernel within 1e-12, the per-row match flags bit for bit on
 seeded scenes (redrawn when an IoU lies within 1e-9 of a threshold or of a different best IoU),
 the documented quirks of the recalled SDK semantics, compute() within 1e-12, and feed-form
-independence (batch sizes, dict list vs upload_batch)."""
+independence (batch sizes, dict list vs upload_batch).  The last section calls
+pp_eval_match_batch_dev through ctypes at its limits: up to 1024 rows, 16 thresholds, 32 classes,
+counts outside 0..max_out, NaN scores, classes outside 0..C-1."""
 import ctypes
 import math
 
@@ -261,3 +263,113 @@ def test_detector_to_evaluator_end_to_end(gpu):
     assert got["classes"] == ref["classes"] and len(ref["classes"]) >= 2
     assert np.nanmax(np.abs(got["ap"] - ref["ap"])) <= 1e-12
     assert abs(got["map"] - ref["map"]) <= 1e-12 and got["map"] > 0
+
+
+# ------------------------------------------------------------------------ the kernel's limits, at the C ABI
+THR16 = np.linspace(0.2, 0.95, 16)
+
+
+def _match_dev(gpu, boxes, counts, gts, thresholds=THR16, classes=32):
+    """pp_eval_match_batch_dev through ctypes: ``boxes [B,max_out,9]``, ``counts [B]`` (any int32), canvas-space GT
+    dicts.  Returns (tp_mask, max_iou, argmax, gt_per_class) as numpy arrays."""
+    import torch
+    from pp_amd import _lib
+    from util import Abi, vp
+    A = Abi(gpu)
+    B, M = boxes.shape[:2]
+    cat = lambda k, w, dt: np.concatenate([np.asarray(g[k], dt).reshape(-1, w) for g in gts]).ravel()   # noqa: E731
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(gpu)   # noqa: E731
+    cen, wlh, yaw = dev(cat("centers", 3, np.float64)), dev(cat("wlh", 3, np.float64)), dev(cat("yaw", 1, np.float64))
+    cls = dev(cat("classes", 1, np.int32))
+    g_counts = (ctypes.c_int32 * B)(*[len(np.asarray(g["yaw"]).reshape(-1)) for g in gts])
+    thr = np.asarray(thresholds, np.float64)
+    prm = _lib.EvalParams(classes, thr.size, (ctypes.c_double * 16)(*thr.tolist()), X_STEP, Y_STEP, X_MIN, Y_MIN)
+    bx, cnt = dev(np.asarray(boxes, np.float64)), dev(np.asarray(counts, np.int32))
+    tp = torch.full((B, M), -1, dtype=torch.int16, device=gpu)
+    iou = torch.full((B, M), 7.0, dtype=torch.float64, device=gpu)
+    arg = torch.full((B, M), 7, dtype=torch.int32, device=gpu)
+    gpc = torch.full((B, classes), -7, dtype=torch.int32, device=gpu)
+    none = lambda t: vp(t) if t.numel() else None   # noqa: E731
+    A.ok(A.L.pp_eval_match_batch_dev(A.h, A.stream, B, vp(bx), M, vp(cnt), g_counts, none(cen), none(wlh), none(yaw),
+                                     none(cls), ctypes.byref(prm), vp(tp), vp(iou), vp(arg), vp(gpc)),
+         "pp_eval_match_batch_dev")
+    torch.cuda.synchronize()
+    return tp.cpu().numpy().astype(np.int64) & 0xFFFF, iou.cpu().numpy(), arg.cpu().numpy(), gpc.cpu().numpy()
+
+
+def _check_rows(got, b, pred, gt, car, n=None, thresholds=THR16):
+    """Rows [0, n) of sample b equal the restatement on ``pred``; the rows behind them are invalid."""
+    tp, iou, arg, _ = got
+    n = len(pred) if n is None else n
+    m, best, a = R.match_sample(pred, car, gt["classes"], thresholds)
+    assert np.array_equal(tp[b, :n], m[:n]), b
+    assert np.array_equal(arg[b, :n], a[:n]), b
+    assert np.abs(iou[b, :n] - best[:n]).max(initial=0) <= 1e-12
+    assert (tp[b, n:] == 0).all() and (arg[b, n:] == -1).all() and (iou[b, n:] == -1).all()
+    return m
+
+
+@pytest.fixture(scope="module")
+def big_scenes():
+    rng = np.random.default_rng(23)
+    return (_scene(rng, 600, 160, classes=32, thresholds=THR16),
+            _scene(rng, 240, 60, classes=32, thresholds=THR16))
+
+
+def test_match_rows_beyond_128_sixteen_thresholds_32_classes(gpu, big_scenes):
+    """max_out 1024 with about 700 valid rows and max_out 300: rows >= 128 (the second and later entries of the
+    per-lane rank arrays, words >= 4 of the taken-bitmaps), mask bits 10..15, classes up to 31."""
+    for (pred, gt, car), max_out in zip(big_scenes, (1024, 300)):
+        assert (600 if max_out == 1024 else 250) <= len(pred) <= max_out and gt["classes"].max() > 9
+        boxes = np.zeros((2, max_out, 9))
+        boxes[0, :len(pred)] = pred
+        boxes[1, :50] = pred[:50]                    # a second sample: its own bitmaps and counters
+        got = _match_dev(gpu, boxes, [len(pred), 50], [gt, gt])
+        m = _check_rows(got, 0, pred, gt, car)
+        _check_rows(got, 1, pred[:50], gt, car)
+        assert (m[128:] != 0).any() and (m >> 10).any(), "the case does not reach the code it is for"
+        assert ((m[128:] != 0) & (m[128:] != 0xFFFF)).any()
+        want = np.bincount(gt["classes"], minlength=32)
+        assert np.array_equal(got[3], np.stack([want, want]))
+
+
+def test_match_count_is_clamped(gpu, big_scenes):
+    pred, gt, car = big_scenes[0]
+    max_out = 300
+    boxes = np.stack([pred[:max_out]] * 3)
+    got = _match_dev(gpu, boxes, [max_out + 50, -3, max_out], [gt, gt, gt])
+    _check_rows(got, 0, pred[:max_out], gt, car)
+    _check_rows(got, 1, pred[:max_out], gt, car, n=0)
+    for k in range(3):
+        assert np.array_equal(got[k][0], got[k][2])
+
+
+def test_match_nan_scores_rank_last_and_foreign_classes_never_match(gpu, scenes):
+    pred, gt, car = scenes[0]
+    rng = np.random.default_rng(2)
+    m0, _, _ = R.match_sample(pred, car, gt["classes"], THR16)
+    hit = np.nonzero(m0)[0]
+    nan_rows = hit[rng.permutation(len(hit))[:5]]
+    assert len(nan_rows) == 5
+    # NaN scores on rows that were TPs, and a copy of each with the lowest finite score: the copy is ranked
+    # before its NaN original, so whatever the original could take the copy has taken
+    dup = pred[nan_rows].copy()
+    dup[:, 7] = 0.01
+    pred = np.concatenate([pred, dup])
+    pred[nan_rows, 7] = np.nan
+    # rows of a class outside 0..31 exactly on a GT box with the highest score of all, and behind them a valid
+    # copy of the same box with the lowest score
+    rows = [[*car[j], 2.0, c] for c, j in ((-1, 0), (32, 1), (1e9, 2))]
+    rows += [[*car[j], 0.02, gt["classes"][j]] for j in (0, 1, 2)]
+    pred = np.concatenate([pred, rows])
+    foreign = np.arange(len(pred) - 6, len(pred) - 3)
+    boxes = np.zeros((1, 128, 9))
+    boxes[0, :len(pred)] = pred
+    got = _match_dev(gpu, boxes, [len(pred)], [gt])
+    moved = pred.copy()
+    moved[nan_rows, 7] = -np.inf             # the restatement's order with the NaN rows moved last
+    m = _check_rows(got, 0, moved, gt, car)
+    assert (m[nan_rows] == 0).all()
+    assert (got[0][0, foreign] == 0).all() and (got[2][0, foreign] == -1).all() and (got[1][0, foreign] == -1).all()
+    for j in (0, 1, 2):                      # GT j is still there for a valid row to take
+        assert (m[got[2][0, :len(pred)] == j] != 0).any(), j

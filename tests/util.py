@@ -96,3 +96,41 @@ class SideTraffic:
 
     def close(self):
         self.side.synchronize()
+
+
+# --------------------------------------------------------------------------- the C ABI through ctypes
+def vp(t, offset_elems=0):
+    """A tensor's device pointer (plus ``offset_elems`` of its elements) as a ctypes void pointer; None -> NULL."""
+    import ctypes
+    if t is None:
+        return None
+    return ctypes.c_void_p(t.data_ptr() + offset_elems * t.element_size())
+
+
+def Abi(gpu):
+    """The library, one context and the current stream of ``gpu``: what a direct call of the C ABI needs, so that no
+    Python wrapper stands between a test and the kernel it checks.  One per device for the whole run."""
+    key = (gpu.type, gpu.index)
+    if key not in _abis:
+        _abis[key] = _Abi(gpu)
+    return _abis[key]
+
+
+_abis = {}
+
+
+class _Abi:
+
+    def __init__(self, gpu):
+        import ctypes
+        import torch
+        from pp_amd import _lib
+        self.L = _lib.lib()
+        self._lib = _lib
+        self.ctx = _lib.Context(gpu.index)
+        self.h = self.ctx.handle
+        self.stream = ctypes.c_void_p(torch.cuda.current_stream(gpu).cuda_stream)
+        self.VALUE = _lib.PP_ERR_VALUE
+
+    def ok(self, rc, what):
+        self._lib.check(rc, what)
