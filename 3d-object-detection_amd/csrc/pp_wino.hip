@@ -33,6 +33,8 @@ constexpr int kCo = 64;             // output channels per workgroup
 constexpr int kVFloats = 16 * 2 * kTiles * 4;
 constexpr int kUFloats = 16 * 2 * kCo * 4;
 constexpr int kBufFloats = kVFloats + kUFloats;
+// s_waitcnt immediate (gfx9 encoding): vmcnt(0), expcnt and lgkmcnt left at their maxima
+constexpr int kWaitVm0 = 0x0F70;
 
 }  // namespace
 
@@ -184,6 +186,10 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
   // channel co0 + 32wc + l32, tiles 32wt + (r&3) + 8(r>>2) + 4h for accumulator register r
   const int co = co0 + 32 * wc + l32;
   const float eb = prm[co * 3 + 0], es = prm[co * 3 + 1], et = prm[co * 3 + 2];
+  // wait for the three constants here, once.  Every store below sits behind a bounds check of its
+  // own; left to the first use, the wait is repeated inside each of those branches, and as stores
+  // count in vmcnt too, each store then waits for the one before it to complete
+  __builtin_amdgcn_s_waitcnt(kWaitVm0);
   float *yb = y + (int64_t)b * H * W * y_stride + co;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
