@@ -1,0 +1,292 @@
+// pp_stem.hip -- the backbone's first layer driven by the pillars instead of the canvas:
+//   PPScatter (model/model.py:53-62) -> Conv2d(3x3, stride 2, padding 1) -> max(. + b, 0) * s + t
+// (model/model.py:76-84, inference) without ever building the [B][H][W][Cin] canvas, of which at
+// most P of H*W pixels per sweep are non-zero.  An input pixel reaches 1.5 outputs per axis, so
+// the useful products are 2.25 * P * Cin * Cout per sweep instead of 9/4 * H * W * Cin * Cout.
+//
+//   k_stem_prepare   features [B][Cin][P] -> pillar-major rows [B][P][Cin] (64x64 LDS transpose)
+//                    and map[b][row][col] = p for every pillar that counts (flag != 0, cell inside
+//                    the canvas).  The map is NOT cleared: a reader trusts an entry p only when
+//                    indices[b][p] names that very cell, so whatever the scratch held before --
+//                    an earlier call's map included -- cannot reach the output.
+//   k_stem_conv      one workgroup per 8x16 output pixels x 64 output channels: the tile's 17x33
+//                    map cells -> nine per-tap lists of (pillar, local output) pairs (an output
+//                    has at most one pair per tap, so a list holds at most 128 pairs: the lists
+//                    are sized for a fully occupied tile) -> per tap, blocks of 16 pairs: gather
+//                    the pairs' feature rows (L2 resident), multiply by W[tap] on
+//                    v_mfma_f32_16x16x4_f32, add the 16 result rows to the f32 accumulator tile in
+//                    LDS -> epilogue, one 16-byte store per thread and 4 channels.
+//
+// Summation order.  Wave w owns output channels [16w, 16w+16) of the accumulator tile for ALL
+// outputs and walks the taps 0..8 in order, so an accumulator element is only ever touched by one
+// wave, tap after tap; inside a tap an output has at most one pair, and that pair's 16 sums over
+// Cin are one fixed MFMA chain whatever row of the block the pair sits in.  No floating-point
+// atomics.  The result does not depend on the order of the pillars along P, on the launch, or on
+// the scratch's previous contents.
+#include "pp_common.h"
+
+namespace pp {
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kTH = 8, kTW = 16;                      // output pixels per workgroup
+constexpr int kOut = kTH * kTW;                       // 128: also the longest per-tap list
+constexpr int kMH = 2 * kTH + 1, kMW = 2 * kTW + 1;   // 17 x 33 map cells feed them
+constexpr int kAcc = 68;                              // floats per accumulator row (64 + 16-byte pad)
+
+// one wave per 64 pillars x 64 channels (k_scatter_canvas's transpose); the waves of channel block 0
+// also enter the pillars into the cell map
+__global__ __launch_bounds__(256) void k_stem_prepare(const float *__restrict__ x,
+                                                      const long long *__restrict__ idx,
+                                                      int *__restrict__ map, float *__restrict__ rows,
+                                                      int C, int P, int H, int W) {
+  __shared__ float s_t[4][64][65];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = blockIdx.z;
+  const int p0 = (blockIdx.x * 4 + wave) * 64;
+  const int c0 = blockIdx.y * 64;
+  if (p0 >= P) return;  // whole wave; no workgroup barrier below
+  float(*t)[65] = s_t[wave];
+  const int np = min(64, P - p0), nc = min(64, C - c0);
+  const float *xr = x + ((int64_t)b * C + c0) * P + p0 + lane;
+#pragma unroll 1
+  for (int cb = 0; cb < nc; cb += 16) {  // 16 row loads in flight at a time
+    float rr[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) rr[k] = (cb + k < nc && lane < np) ? xr[(int64_t)(cb + k) * P] : 0.0f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (cb + k < nc) t[cb + k][lane] = rr[k];
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  if (c0 == 0 && lane < np) {
+    const long long *io = idx + ((int64_t)b * P + p0 + lane) * 3;
+    const long long flag = io[0], col = io[1], row = io[2];  // {1, canvas_x, canvas_y}, pillars.cpp:390-392
+    if (flag != 0 && row >= 0 && row < H && col >= 0 && col < W)
+      map[(int64_t)b * H * W + row * W + col] = p0 + lane;
+  }
+  float *rp = rows + ((int64_t)b * P + p0) * C + c0 + lane;
+  if (lane < nc)
+    for (int q = 0; q < np; ++q) rp[(int64_t)q * C] = t[lane][q];
+}
+
+// CIN: the input channels at compile time (the reduction fully unrolled: every load of a block is
+// in flight before its first MFMA), or 0: cin_rt, any multiple of 8
+template <int CIN>
+__global__ __launch_bounds__(256) void k_stem_conv(const int *__restrict__ map,
+                                                   const long long *__restrict__ idx,
+                                                   const float *__restrict__ rows,
+                                                   const float *__restrict__ w,
+                                                   const float *__restrict__ params,
+                                                   float *__restrict__ y, int P, int H, int W, int OH,
+                                                   int OW, int cin_rt, int Cout, int tiles_x,
+                                                   int tiles_y) {
+  __shared__ __attribute__((aligned(16))) float s_acc[kOut * kAcc];
+  __shared__ int s_map[kMH * kMW];
+  __shared__ int s_lp[9][kOut];            // per tap: the pairs' pillars ...
+  __shared__ unsigned char s_lo[9][kOut];  // ... and local outputs
+  __shared__ int s_cnt[9];
+  const int Cin = CIN ? CIN : cin_rt;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y;
+  const int b = blockIdx.x / (tiles_x * tiles_y);
+  const int oy0 = ty * kTH, ox0 = tx * kTW;
+
+  // the tile's cells: input rows 2*oy0-1 .. 2*oy0+15, columns 2*ox0-1 .. 2*ox0+31.  An entry counts
+  // only if the pillar it names is flagged and sits in this cell (the map is never cleared).
+  {
+    const int *mb = map + (int64_t)b * H * W;
+    const long long *ib = idx + (int64_t)b * P * 3;
+    for (int i = tid; i < kMH * kMW; i += 256) {
+      const int r = i / kMW, c = i - r * kMW;
+      const int iy = 2 * oy0 - 1 + r, ix = 2 * ox0 - 1 + c;
+      int p = -1;
+      if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
+        p = mb[(int64_t)iy * W + ix];
+        if (p >= 0 && p < P) {
+          const long long *io = ib + (int64_t)p * 3;
+          if (io[0] == 0 || io[1] != ix || io[2] != iy) p = -1;
+        } else {
+          p = -1;
+        }
+      }
+      s_map[i] = p;
+    }
+    const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (int i = tid; i < kOut * kAcc / 4; i += 256) reinterpret_cast<float4 *>(s_acc)[i] = z;
+  }
+  __syncthreads();
+
+  // nine lists, in output order (ballot + prefix count): tap (ky,kx) pairs output (oy,ox) with
+  // cell (2*oy + ky - 1, 2*ox + kx - 1)
+  for (int t = wave; t < 9; t += 4) {
+    const int ky = t / 3, kx = t - 3 * ky;
+    int n = 0;
+#pragma unroll
+    for (int ch = 0; ch < kOut / 64; ++ch) {
+      const int o = ch * 64 + lane, oy = o / kTW, ox = o % kTW;
+      int p = -1;
+      if (oy0 + oy < OH && ox0 + ox < OW) p = s_map[(2 * oy + ky) * kMW + 2 * ox + kx];
+      const unsigned long long m = __ballot(p >= 0);
+      if (p >= 0) {
+        const int pos = n + __popcll(m & ((1ull << lane) - 1ull));
+        s_lp[t][pos] = p;
+        s_lo[t][pos] = (unsigned char)o;
+      }
+      n += __popcll(m);
+    }
+    if (lane == 0) s_cnt[t] = n;
+  }
+  __syncthreads();
+
+  // wave `wave`: output channels [16*wave, +16) of this workgroup's 64, every tap in order.
+  // v_mfma_f32_16x16x4_f32: lane l holds A[row l&15][k l>>4] and B[k l>>4][column l&15]; the 8 input
+  // channels of step pair j are assigned k = 0..3 as channel 8j + 2k + e (e = 0, 1: one 8-byte load
+  // of the row per lane).  D: lane l, register r = row 4*(l>>4) + r, column l&15.
+  {
+    const int i16 = lane & 15, kq = lane >> 4;
+    const float *rb = rows + (int64_t)b * P * Cin + 2 * kq;
+    const float *wc = w + (int64_t)(2 * kq) * Cout + blockIdx.y * 64 + wave * 16 + i16;
+    float *acc = s_acc + wave * 16 + i16;
+#pragma unroll 1
+    for (int t = 0; t < 9; ++t) {
+      const int n = __builtin_amdgcn_readfirstlane(s_cnt[t]);
+      const float *wt = wc + (int64_t)t * Cin * Cout;
+#pragma unroll 1
+      for (int r0 = 0; r0 < n; r0 += 16) {
+        // rows past the list's end repeat its first pair; their results are dropped below
+        const int p = s_lp[t][r0 + i16 < n ? r0 + i16 : r0];
+        const float *ar = rb + (int64_t)p * Cin;
+        f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
+        if constexpr (CIN != 0) {
+          float2 a[CIN / 8];
+          float b0[CIN / 8], b1[CIN / 8];
+#pragma unroll
+          for (int j = 0; j < CIN / 8; ++j) {
+            a[j] = *reinterpret_cast<const float2 *>(ar + 8 * j);
+            b0[j] = wt[(int64_t)(8 * j) * Cout];
+            b1[j] = wt[(int64_t)(8 * j + 1) * Cout];
+          }
+#pragma unroll
+          for (int j = 0; j < CIN / 8; ++j) {
+            c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j].x, b0[j], c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j].y, b1[j], c, 0, 0, 0);
+          }
+        } else {
+          for (int j = 0; j < Cin / 8; ++j) {
+            const float2 a = *reinterpret_cast<const float2 *>(ar + 8 * j);
+            const float b0 = wt[(int64_t)(8 * j) * Cout], b1 = wt[(int64_t)(8 * j + 1) * Cout];
+            c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b0, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b1, c, 0, 0, 0);
+          }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int q = r0 + 4 * kq + r;
+          if (q < n) acc[(int)s_lo[t][q] * kAcc] += c[r];
+        }
+        // another lane of this wave may own the same accumulator element in the next tap
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+      }
+    }
+  }
+  __syncthreads();
+
+  // epilogue: thread = 4 channels of one pixel per pass; a pass writes one tile row (16 whole pixels)
+  {
+    const int c4 = (tid & 15) * 4, ox = tid >> 4;
+    const int cg = blockIdx.y * 64 + c4;
+    float eb[4], es[4], et[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      eb[e] = params[(cg + e) * 3];
+      es[e] = params[(cg + e) * 3 + 1];
+      et[e] = params[(cg + e) * 3 + 2];
+    }
+    if (ox0 + ox < OW) {
+#pragma unroll
+      for (int oy = 0; oy < kTH; ++oy) {
+        if (oy0 + oy >= OH) continue;
+        float4 v = *reinterpret_cast<const float4 *>(s_acc + (oy * kTW + ox) * kAcc + c4);
+        v.x = fmaxf(v.x + eb[0], 0.0f) * es[0] + et[0];
+        v.y = fmaxf(v.y + eb[1], 0.0f) * es[1] + et[1];
+        v.z = fmaxf(v.z + eb[2], 0.0f) * es[2] + et[2];
+        v.w = fmaxf(v.w + eb[3], 0.0f) * es[3] + et[3];
+        *reinterpret_cast<float4 *>(y + (((int64_t)b * OH + oy0 + oy) * OW + ox0 + ox) * Cout + cg) = v;
+      }
+    }
+  }
+}
+
+}  // namespace
+}  // namespace pp
+
+using namespace pp;
+
+extern "C" int pp_conv3x3_s2_pillars_nhwc_dev(pp_ctx_t *ctx, void *stream_, const float *features_dev,
+                                              const int64_t *indices_dev, int batch, int in_channels,
+                                              int max_pillars, int canvas_h, int canvas_w,
+                                              const float *w_taps_dev, int out_channels,
+                                              const float *params_dev, void *scratch_dev,
+                                              size_t scratch_bytes, float *y_dev) {
+  if (!ctx || !features_dev || !indices_dev || !w_taps_dev || !params_dev || !scratch_dev || !y_dev) {
+    set_error("pp_conv3x3_s2_pillars_nhwc_dev: NULL argument");
+    return PP_ERR_VALUE;
+  }
+  if (batch < 1 || batch > 65535 || in_channels < 8 || in_channels % 8 || out_channels < 64 ||
+      out_channels % 64 || out_channels / 64 > 65535 || max_pillars < 1 || canvas_h < 1 || canvas_w < 1 ||
+      ((reinterpret_cast<uintptr_t>(scratch_dev) | reinterpret_cast<uintptr_t>(y_dev)) & 15)) {
+    set_error("pp_conv3x3_s2_pillars_nhwc_dev: need in_channels a multiple of 8, out_channels a multiple of "
+              "64, 16-byte aligned scratch and y (batch=%d in=%d out=%d P=%d canvas %dx%d)", batch,
+              in_channels, out_channels, max_pillars, canvas_h, canvas_w);
+    return PP_ERR_VALUE;
+  }
+  const int oh = (canvas_h + 1) / 2, ow = (canvas_w + 1) / 2;
+  const int64_t tiles_x = (ow + kTW - 1) / kTW, tiles_y = (oh + kTH - 1) / kTH;
+  const int64_t blocks = (int64_t)batch * tiles_x * tiles_y;
+  const int64_t cells = (int64_t)batch * canvas_h * canvas_w;
+  const int64_t row_floats = (int64_t)batch * max_pillars * in_channels;
+  if (blocks > 0x7fffffff || cells > ((int64_t)1 << 36) || row_floats > ((int64_t)1 << 36) ||
+      (int64_t)batch * oh * ow * out_channels > ((int64_t)1 << 40)) {
+    set_error("pp_conv3x3_s2_pillars_nhwc_dev: tensor too large");
+    return PP_ERR_VALUE;
+  }
+  const size_t map_bytes = ((size_t)cells * sizeof(int) + 255) & ~(size_t)255;
+  const size_t need = map_bytes + (size_t)row_floats * sizeof(float);
+  if (scratch_bytes < need) {
+    set_error("pp_conv3x3_s2_pillars_nhwc_dev: scratch of %zu bytes, %zu needed", scratch_bytes, need);
+    return PP_ERR_VALUE;
+  }
+  int *map = static_cast<int *>(scratch_dev);
+  float *rows = reinterpret_cast<float *>(static_cast<char *>(scratch_dev) + map_bytes);
+  const long long *idx = reinterpret_cast<const long long *>(indices_dev);
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  if (prev != ctx->device) (void)hipSetDevice(ctx->device);
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  const dim3 pgrid((unsigned)((max_pillars + 255) / 256), (unsigned)((in_channels + 63) / 64), (unsigned)batch);
+  hipLaunchKernelGGL(k_stem_prepare, pgrid, dim3(256), 0, st, features_dev, idx, map, rows, in_channels,
+                     max_pillars, canvas_h, canvas_w);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) {
+    const dim3 grid((unsigned)blocks, (unsigned)(out_channels / 64));
+    if (in_channels == 64)
+      hipLaunchKernelGGL(k_stem_conv<64>, grid, dim3(256), 0, st, map, idx, rows, w_taps_dev, params_dev, y_dev,
+                         max_pillars, canvas_h, canvas_w, oh, ow, in_channels, out_channels, (int)tiles_x,
+                         (int)tiles_y);
+    else
+      hipLaunchKernelGGL(k_stem_conv<0>, grid, dim3(256), 0, st, map, idx, rows, w_taps_dev, params_dev, y_dev,
+                         max_pillars, canvas_h, canvas_w, oh, ow, in_channels, out_channels, (int)tiles_x,
+                         (int)tiles_y);
+    e = hipGetLastError();
+  }
+  if (prev >= 0 && prev != ctx->device) (void)hipSetDevice(prev);
+  if (e != hipSuccess) {
+    set_error("pp_conv3x3_s2_pillars_nhwc_dev launch failed: %s", hipGetErrorString(e));
+    return PP_ERR_HIP;
+  }
+  return PP_OK;
+}

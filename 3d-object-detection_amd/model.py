@@ -151,6 +151,48 @@ def _conv_wino(x, u, table, cout, out=None, channel_offset=0):
     return out
 
 
+def _stem_filter(w):
+    """Conv weight [Cout,Cin,3,3] -> [9][Cin][Cout], tap 3*kh + kw: pp_conv3x3_s2_pillars_nhwc_dev's layout."""
+    co, ci = w.shape[:2]
+    return w.detach().permute(2, 3, 1, 0).reshape(9, ci, co).contiguous()
+
+
+def _stem_ok(backbone, scatter, feats, inds):
+    """The pillar-driven kernel takes the backbone's first layer: no-grad f32 inference on the GPU with a
+    channels-last canvas, int64 indices, a 3x3 / stride-2 / padding-1 conv, Cin % 8 == 0, Cout % 64 == 0."""
+    d1 = backbone.down1
+    conv = d1.block[0]
+    return (backbone.sparse_stem and _use_fused_epilogue(d1, feats) and not scatter.training
+            and scatter.channels_last_inference and feats.dim() == 3 and inds.dtype == torch.int64
+            and inds.is_cuda and tuple(inds.shape) == (feats.shape[0], feats.shape[2], 3) and feats.shape[2] > 0
+            and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (2, 2)
+            and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.groups == 1
+            and feats.shape[1] == conv.in_channels and conv.in_channels % 8 == 0
+            and conv.out_channels % 64 == 0)
+
+
+def _conv_stem(feats, inds, h, w, w_taps, table, cout):
+    """pp_conv3x3_s2_pillars_nhwc_dev: PPScatter -> conv(3x3, stride 2, padding 1) -> bias/ReLU/BatchNorm of
+    ``feats`` [B,C,P] at the cells ``inds`` [B,P,3] names on an h x w canvas that is never built, into a
+    new channels-last tensor [B,cout,ceil(h/2),ceil(w/2)]."""
+    B, C, P = feats.shape
+    dev = feats.device
+    feats = feats if feats.is_contiguous() else feats.contiguous()
+    inds = inds if inds.is_contiguous() else inds.contiguous()
+    # the cell -> pillar map, then the features pillar-major (the kernel trusts neither's old contents)
+    nbytes = ((B * h * w * 4 + 255) & ~255) + B * P * C * 4
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    out = torch.empty((B, cout, (h + 1) // 2, (w + 1) // 2), dtype=torch.float32, device=dev,
+                      memory_format=torch.channels_last)
+    rc = _lib.lib().pp_conv3x3_s2_pillars_nhwc_dev(
+        _hip_ctx(dev).handle, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
+        ctypes.c_void_p(feats.data_ptr()), ctypes.c_void_p(inds.data_ptr()), B, C, P, int(h), int(w),
+        ctypes.c_void_p(w_taps.data_ptr()), cout, ctypes.c_void_p(table.data_ptr()),
+        ctypes.c_void_p(scratch.data_ptr()), nbytes, ctypes.c_void_p(out.data_ptr()))
+    _lib.check(rc, "pp_conv3x3_s2_pillars_nhwc_dev")
+    return out
+
+
 def _use_fused_epilogue(module, x):
     # the epilogue kernels work in place through raw pointers: autograd never sees them, so
     # they are for no-grad inference only (eval-mode fine-tuning / saliency take the modules)
@@ -398,8 +440,8 @@ class PPScatter(nn.Module):
     def forward(self, x, inds):            # x [B,C,P], inds [B,P,3] int64
         B, C, P = x.shape
         hw = self.h * self.w
-        lin = inds[:, :, 2] * self.w + inds[:, :, 1]
-        if (not self.training) and self.channels_last_inference and x.is_cuda and not torch.is_grad_enabled():
+        nhwc = (not self.training) and self.channels_last_inference and x.is_cuda and not torch.is_grad_enabled()
+        if nhwc:
             if x.dtype == torch.float32 and inds.dtype == torch.int64:
                 # one memset + one HIP kernel (64x64 tile transpose, a 256-byte pixel per pillar)
                 x = x if x.is_contiguous() else x.contiguous()
@@ -412,6 +454,8 @@ class PPScatter(nn.Module):
                     ctypes.c_void_p(out.data_ptr()), self.h, self.w, 1)
                 _lib.check(rc, "pp_scatter_canvas_dev")
                 return out
+        lin = inds[:, :, 2] * self.w + inds[:, :, 1]
+        if nhwc:
             base = torch.arange(B, device=x.device, dtype=lin.dtype).unsqueeze(1) * hw
             lin = torch.where(inds[:, :, 0] != 0, lin + base, torch.full_like(lin, B * hw))
             flat = x.new_zeros((B * hw + 1, C))
@@ -444,9 +488,20 @@ class PPDownBlock(nn.Module):
         #: (csrc/pp_wino.hip: conv and epilogue in one pass, no MIOpen call)
         self.winograd = True
         self._wino = [_LayoutCache() for _ in range(num_layers)]
+        self._stem = _LayoutCache()
 
-    def forward(self, x):
+    def stem(self, feats, inds, h, w):
+        """Layer 0 on the pillars themselves (``_stem_ok`` holds): what ``forward`` makes of PPScatter's
+        canvas in its first layer, as one fused kernel pair that never builds the canvas."""
+        conv, bn = self.block[0], self.block[2]
+        w_taps = self._stem.get((conv.weight,), lambda: _stem_filter(conv.weight))
+        return _conv_stem(feats, inds, h, w, w_taps, self._epi[0].table(conv.bias, bn), conv.out_channels)
+
+    def forward(self, x, first=0):
+        """``first`` = 1: ``x`` is ``stem``'s output and has passed layer 0 already."""
         if not _use_fused_epilogue(self, x):
+            if first:
+                raise RuntimeError("PPDownBlock: a tensor past layer 0 needs the fused inference path")
             if self.training and self.fused_train and x.is_cuda:
                 for i in range(len(self._epi)):
                     conv, bn = self.block[3 * i], self.block[3 * i + 2]
@@ -454,8 +509,8 @@ class PPDownBlock(nn.Module):
                                  conv_bias=conv.bias)
                 return x
             return self.block(x)
-        for i, epi in enumerate(self._epi):
-            conv, bn = self.block[3 * i], self.block[3 * i + 2]
+        for i in range(first, len(self._epi)):
+            epi, conv, bn = self._epi[i], self.block[3 * i], self.block[3 * i + 2]
             if _wino_ok(self, conv, x):
                 u = self._wino[i].get((conv.weight,), lambda: _wino_filter(conv.weight))
                 x = _conv_wino(x, u, epi.table(conv.bias, bn), conv.out_channels)
@@ -525,13 +580,19 @@ class PPBackbone(nn.Module):
         self.up2 = PPUpBlock(2 * c, 2 * c, 2, 1, 1)
         self.down3 = PPDownBlock(6, 2 * c, 4 * c)
         self.up3 = PPUpBlock(4 * c, 2 * c, 4, 1, up3_op)
+        #: inference from the feature net's output (PPModel.forward / forward_features): down1's first
+        #: layer reads the pillars, not the canvas (csrc/pp_stem.hip: the scatter, the stride-2 conv and
+        #: its epilogue in one kernel pair; the 95 % empty canvas is never built)
+        self.sparse_stem = True
 
-    def forward(self, x):
+    def forward(self, x, after_stem=False):
+        """``after_stem``: ``x`` is ``down1.stem``'s output instead of the canvas."""
+        first = 1 if after_stem else 0
         if _use_fused_epilogue(self.up1, x):
             # inference: the three up blocks write their channel slices of the concatenated
             # output directly (no torch.cat copy)
             c = self.up1.conv2d_t.out_channels
-            x = self.down1(x)
+            x = self.down1(x, first)
             out = torch.empty((x.shape[0], 3 * c, x.shape[2], x.shape[3]), dtype=x.dtype, device=x.device,
                               memory_format=torch.channels_last if _is_nhwc(x) else torch.contiguous_format)
             self.up1(x, out, 0)
@@ -540,7 +601,7 @@ class PPBackbone(nn.Module):
             x = self.down3(x)
             self.up3(x, out, 2 * c)
             return out
-        x = self.down1(x)
+        x = self.down1(x, first)
         out1 = self.up1(x)
         x = self.down2(x)
         out2 = self.up2(x)
@@ -590,10 +651,7 @@ class PPModel(nn.Module):
                                         reg_layer_channels)
 
     def forward(self, x, inds):
-        x = self.feature_net(x)
-        x = self.scatter(x, inds)
-        x = self.backbone(x)
-        return self.det_head(x)
+        return self.forward_features(self.feature_net(x), inds)
 
     def forward_canvas(self, canvas):
         """The network from PPScatter's output on: ``canvas[B,C,H,W]`` in either memory
@@ -603,6 +661,9 @@ class PPModel(nn.Module):
     def forward_features(self, feats, inds):
         """Same network from PPFeatureNet's output ``feats[B,C,P]`` on (the fused
         HIP voxelizer + feature net produces it directly)."""
+        if _stem_ok(self.backbone, self.scatter, feats, inds):
+            x = self.backbone.down1.stem(feats, inds, self.scatter.h, self.scatter.w)
+            return self.det_head(self.backbone(x, after_stem=True))
         x = self.scatter(feats, inds)
         x = self.backbone(x)
         return self.det_head(x)

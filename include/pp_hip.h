@@ -16,6 +16,7 @@
 #ifndef PP_HIP_H
 #define PP_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -513,6 +514,32 @@ int pp_conv3x3_wino_nhwc_dev(pp_ctx_t *ctx, void *stream, const float *x_dev, in
                              int width, int in_channels, const float *u_dev, int out_channels,
                              const float *params_dev, float *y_dev, int64_t y_channels,
                              int64_t y_channel_offset);
+
+/*
+ * The backbone's first layer straight from the pillars (inference): PPScatter (model/model.py:53-62)
+ * -> 3x3, stride-2, padding-1 convolution -> the epilogue of pp_bias_relu_bn_nhwc_dev,
+ *   y = max(conv(canvas) + bias_c, 0) * scale_c + shift_c,
+ * without building the canvas: only the (pillar, filter tap) pairs that exist are multiplied.
+ *   features_dev [batch][in_channels][P] f32, indices_dev [batch][P][3] int64 {flag, col, row}; a
+ *                pillar counts as in pp_scatter_canvas_dev (flag != 0, 0 <= row < canvas_h,
+ *                0 <= col < canvas_w); two counting pillars in one cell are undefined there and here
+ *   w_taps_dev   [9][in_channels][out_channels] f32: tap 3*kh + kw of the Conv2d weight
+ *                [out][in][kh][kw]
+ *   params_dev   [out_channels][3] f32 {bias, scale, shift}
+ *   scratch_dev  16-byte aligned, scratch_bytes >= round_up(batch*canvas_h*canvas_w*4, 256) +
+ *                batch*P*in_channels*4 (a cell -> pillar map and the features pillar-major).  Its
+ *                contents on entry do not matter and it may be reused from call to call.
+ *   y_dev        NHWC [batch][ceil(canvas_h/2)][ceil(canvas_w/2)][out_channels] f32, 16-byte aligned,
+ *                every element written exactly once
+ * in_channels a multiple of 8, out_channels a multiple of 64.  Two launches, no allocation, no
+ * synchronisation (graph-capturable).  No floating-point atomics and a fixed summation order: the
+ * result is bit-identical from call to call and under any permutation of the pillars along P.
+ */
+int pp_conv3x3_s2_pillars_nhwc_dev(pp_ctx_t *ctx, void *stream, const float *features_dev,
+                                   const int64_t *indices_dev, int batch, int in_channels,
+                                   int max_pillars, int canvas_h, int canvas_w,
+                                   const float *w_taps_dev, int out_channels, const float *params_dev,
+                                   void *scratch_dev, size_t scratch_bytes, float *y_dev);
 
 /*
  * The ReLU -> BatchNorm2d tail of the backbone blocks in TRAINING mode (model/model.py:76-84,
