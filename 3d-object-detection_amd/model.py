@@ -151,6 +151,39 @@ def _conv_wino(x, u, table, cout, out=None, channel_offset=0):
     return out
 
 
+def _f16_filter(w):
+    """Conv weight [Cout,Cin,3,3] -> fp16 (``w.half()``: round to nearest even) in the layout of
+    pp_conv3x3_f16_nhwc_dev: [Cout/64][Cin/16][9][2][64][8], tap 3*kh + kw (16 input channels x 64 output
+    channels are one contiguous copy into the kernel's LDS image)."""
+    co, ci = w.shape[:2]
+    return w.detach().half().reshape(co // 64, 64, ci // 16, 2, 8, 9).permute(0, 2, 5, 3, 1, 4).contiguous()
+
+
+def _f16_ok(module, conv, x, transposed=False):
+    """The fp16-operand MFMA kernel takes this layer: the module's ``half_mma`` flag and ``_wino_ok``'s
+    conditions on the layer and its input, with Cin % 16 == 0."""
+    return (module.half_mma and _is_nhwc(x) and x.data_ptr() % 16 == 0
+            and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1)
+            and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.groups == 1
+            and (not transposed or tuple(conv.output_padding) == (0, 0))
+            and x.shape[1] == conv.in_channels and conv.in_channels % 16 == 0 and conv.out_channels % 64 == 0)
+
+
+def _conv_f16(x, w16, table, cout, out=None, channel_offset=0):
+    """pp_conv3x3_f16_nhwc_dev: ``_conv_wino``'s layer with fp16 operands (``w16`` from ``_f16_filter``) and
+    f32 accumulation; f32 activations in and out."""
+    B, C, H, W = x.shape
+    dev = x.device
+    if out is None:
+        out = torch.empty((B, cout, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+    rc = _lib.lib().pp_conv3x3_f16_nhwc_dev(
+        _hip_ctx(dev).handle, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
+        ctypes.c_void_p(x.data_ptr()), B, H, W, C, ctypes.c_void_p(w16.data_ptr()), cout,
+        ctypes.c_void_p(table.data_ptr()), ctypes.c_void_p(out.data_ptr()), out.shape[1], int(channel_offset))
+    _lib.check(rc, "pp_conv3x3_f16_nhwc_dev")
+    return out
+
+
 def _stem_filter(w):
     """Conv weight [Cout,Cin,3,3] -> [9][Cin][Cout], tap 3*kh + kw: pp_conv3x3_s2_pillars_nhwc_dev's layout."""
     co, ci = w.shape[:2]
@@ -488,6 +521,10 @@ class PPDownBlock(nn.Module):
         #: (csrc/pp_wino.hip: conv and epilogue in one pass, no MIOpen call)
         self.winograd = True
         self._wino = [_LayoutCache() for _ in range(num_layers)]
+        #: opt-in "fp16 inference" (PPModel.set_inference_precision): those layers with fp16 operands and
+        #: f32 accumulation instead (csrc/pp_conv_f16.hip); changes results at the 1e-4 level
+        self.half_mma = False
+        self._f16 = [_LayoutCache() for _ in range(num_layers)]
         self._stem = _LayoutCache()
 
     def stem(self, feats, inds, h, w):
@@ -511,6 +548,10 @@ class PPDownBlock(nn.Module):
             return self.block(x)
         for i in range(first, len(self._epi)):
             epi, conv, bn = self._epi[i], self.block[3 * i], self.block[3 * i + 2]
+            if _f16_ok(self, conv, x):
+                w16 = self._f16[i].get((conv.weight,), lambda: _f16_filter(conv.weight))
+                x = _conv_f16(x, w16, epi.table(conv.bias, bn), conv.out_channels)
+                continue
             if _wino_ok(self, conv, x):
                 u = self._wino[i].get((conv.weight,), lambda: _wino_filter(conv.weight))
                 x = _conv_wino(x, u, epi.table(conv.bias, bn), conv.out_channels)
@@ -534,6 +575,8 @@ class PPUpBlock(nn.Module):
         self._wcl = _LayoutCache()
         self.winograd = True
         self._wino = _LayoutCache()
+        self.half_mma = False
+        self._f16 = _LayoutCache()
 
     def forward(self, x, out=None, channel_offset=0):
         if not _use_fused_epilogue(self, x):
@@ -543,10 +586,13 @@ class PPUpBlock(nn.Module):
                                 self.bn, conv_bias=ct.bias)
             return self.bn(F.relu(self.conv2d_t(x)))
         ct = self.conv2d_t
-        if _wino_ok(self, ct, x, transposed=True) and (
-                out is None or (_is_nhwc(out) and out.dtype == torch.float32 and out.shape[0] == x.shape[0]
-                                and out.shape[2:] == x.shape[2:])):
-            # stride 1: the transposed conv is a conv with w_conv[co][ci][kh][kw] = w_t[ci][co][2-kh][2-kw]
+        out_ok = out is None or (_is_nhwc(out) and out.dtype == torch.float32 and out.shape[0] == x.shape[0]
+                                 and out.shape[2:] == x.shape[2:])
+        # stride 1: the transposed conv is a conv with w_conv[co][ci][kh][kw] = w_t[ci][co][2-kh][2-kw]
+        if _f16_ok(self, ct, x, transposed=True) and out_ok and (out is None or out.data_ptr() % 16 == 0):
+            w16 = self._f16.get((ct.weight,), lambda: _f16_filter(ct.weight.transpose(0, 1).flip(2, 3)))
+            return _conv_f16(x, w16, self._epi.table(ct.bias, self.bn), ct.out_channels, out, channel_offset)
+        if _wino_ok(self, ct, x, transposed=True) and out_ok:
             u = self._wino.get((ct.weight,), lambda: _wino_filter(ct.weight.transpose(0, 1).flip(2, 3)))
             return _conv_wino(x, u, self._epi.table(ct.bias, self.bn), ct.out_channels, out, channel_offset)
         y = F.conv_transpose2d(x, _weight_like(x, ct.weight, self._wcl), None, ct.stride, ct.padding,
@@ -635,6 +681,16 @@ class PPDetectionHead(nn.Module):
         return y[:, :n], y[:, n:]
 
 
+#: what PPModel.set_inference_precision takes
+INFERENCE_PRECISIONS = ("f32", "fp16")
+
+
+def check_inference_precision(precision):
+    if precision not in INFERENCE_PRECISIONS:
+        raise ValueError(f"precision must be one of {INFERENCE_PRECISIONS}, not {precision!r}")
+    return precision
+
+
 class PPModel(nn.Module):
     """model/model.py:162-180.  ``forward(x[B,9,P,N], inds[B,P,3]) ->
     (cls[B,A*9,H/2,W/2], reg[B,A*8,H/2,W/2])``."""
@@ -649,6 +705,15 @@ class PPModel(nn.Module):
         self.backbone = PPBackbone(feature_net_out_channels, up3_op)
         self.det_head = PPDetectionHead(6 * feature_net_out_channels, class_layer_channels,
                                         reg_layer_channels)
+
+    def set_inference_precision(self, precision):
+        """``"fp16"``: the backbone's stride-1 3x3 layers (down1-3, up1) multiply fp16-rounded operands and
+        accumulate in f32 (csrc/pp_conv_f16.hip) in no-grad channels-last inference on the GPU; results move
+        at the 1e-4 level.  ``"f32"`` (the default): every path in f32.  Activations are f32 either way."""
+        check_inference_precision(precision)
+        bb = self.backbone
+        for m in (bb.down1, bb.down2, bb.down3, bb.up1):
+            m.half_mma = precision == "fp16"
 
     def forward(self, x, inds):
         return self.forward_features(self.feature_net(x), inds)

@@ -10,7 +10,7 @@ import torch
 
 from . import boxes
 from .loss import PPLoss
-from .model import PPModel
+from .model import PPModel, check_inference_precision
 from .targets import TargetAssigner
 from .voxelizer import PillarVoxelizer, VoxelConfig
 
@@ -18,7 +18,10 @@ from .voxelizer import PillarVoxelizer, VoxelConfig
 class PillarPipeline:
     def __init__(self, vox_cfg: VoxelConfig, anchor_cfg: boxes.AnchorConfig = None,
                  feature_channels=64, num_classes=9, reg_dims=8, device=None, seed=0,
-                 pos_thresh=0.6, with_targets=False, data_mean=None):
+                 pos_thresh=0.6, with_targets=False, data_mean=None, precision="f32"):
+        """``precision``: ``PPModel.set_inference_precision`` ("f32", or "fp16" for fp16-operand MFMA in the
+        backbone's stride-1 layers at inference)."""
+        check_inference_precision(precision)      # before anything is built
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.vox_cfg = vox_cfg
         h, w = vox_cfg.canvas_height, vox_cfg.canvas_width
@@ -30,6 +33,7 @@ class PillarPipeline:
         torch.manual_seed(seed)  # model/model.py:9
         self.model = PPModel(9, feature_channels, anchor_cfg.per_cell * num_classes,
                              anchor_cfg.per_cell * reg_dims, h, w).to(self.device)
+        self.model.set_inference_precision(precision)
         self.loss = PPLoss()
         self.assigner = None
         if with_targets:

@@ -516,6 +516,39 @@ int pp_conv3x3_wino_nhwc_dev(pp_ctx_t *ctx, void *stream, const float *x_dev, in
                              int64_t y_channel_offset);
 
 /*
+ * The same layer as pp_conv3x3_wino_nhwc_dev -- a 3x3, stride-1, padding-1 convolution of NHWC f32
+ * x[batch][height][width][in_channels] with the epilogue
+ *   y = max(conv(x) + bias_c, 0) * scale_c + shift_c,   params_dev [out_channels][3] f32
+ * -- with fp16 operands: the opt-in "fp16 inference" mode.  Activations are f32 in memory on both
+ * sides.  Arithmetic:
+ *   - Each x value and each weight is rounded once to IEEE binary16, round to nearest even (not the
+ *     round-toward-zero pkrtz conversion).  x is rounded by the kernel; w_f16_dev holds the weights
+ *     already rounded (torch.Tensor.half()).
+ *   - Values beyond the fp16 range become +-inf, as torch.Tensor.half() makes them.  The caller opts
+ *     in; the layer inputs here are BatchNorm outputs.
+ *   - fp16-subnormal values are kept by both conversions (neither flushes); the products are formed
+ *     by the matrix unit from the operands as stored, and what it makes of subnormal operands is not
+ *     part of this contract: it moves a result by less than 1e-6 * sum|w||x|.
+ *   - Products are accumulated in f32 on v_mfma_f32_32x32x16_f16: a direct implicit GEMM (M = pixels,
+ *     N = out_channels, K = 9 * in_channels), not Winograd.
+ *   - The bias, ReLU and BatchNorm epilogue runs in f32.
+ *   - The schedule is fixed: no split-K and no atomics.  Results are bit-identical from call to call.
+ * w_f16_dev is the conv weight w[co][ci][kh][kw] as fp16 in the layout
+ * [out_channels/64][in_channels/16][9][2][64][8]: w[co][ci][kh][kw] at element
+ *   (((((co/64)*(in_channels/16) + ci/16)*9 + 3*kh + kw)*2 + (ci/8)%2)*64 + co%64)*8 + ci%8
+ * (16 input channels x 64 output channels are one contiguous 18 KB piece; a lane's MFMA B fragment,
+ * 8 consecutive input channels of one output channel and tap, is 16 contiguous bytes).
+ * y_dev: channels [y_channel_offset, +out_channels) of rows of y_channels floats per pixel, each
+ * written exactly once (no zero fill; other channels untouched).  in_channels a multiple of 16,
+ * out_channels a multiple of 64, x, w and y 16-byte aligned, height*width*in_channels < 2^31.
+ * Launches only: no allocation, no synchronisation (graph-capturable).
+ */
+int pp_conv3x3_f16_nhwc_dev(pp_ctx_t *ctx, void *stream, const float *x_dev, int batch, int height,
+                            int width, int in_channels, const void *w_f16_dev, int out_channels,
+                            const float *params_dev, float *y_dev, int64_t y_channels,
+                            int64_t y_channel_offset);
+
+/*
  * The backbone's first layer straight from the pillars (inference): PPScatter (model/model.py:53-62)
  * -> 3x3, stride-2, padding-1 convolution -> the epilogue of pp_bias_relu_bn_nhwc_dev,
  *   y = max(conv(canvas) + bias_c, 0) * scale_c + shift_c,

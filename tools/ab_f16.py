@@ -1,0 +1,102 @@
+"""Dev tool: A/B of the opt-in fp16-operand MFMA layers (``PPModel.set_inference_precision("fp16")``,
+csrc/pp_conv_f16.hip) against the f32 default at bench.py's headline shapes (500x500 canvas, B=4,
+the pipelined step), both legs in one process, alternating; the ``cls``/``reg`` difference of the two
+modes on the same input; then per-layer kernel times of the fp16 kernel and of the Winograd kernel.
+
+usage: ab_f16.py [rounds] [steps]      (default 3 x 50 steps each way)"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench  # noqa: E402
+import pp_amd.model as M  # noqa: E402
+from pp_amd import synth  # noqa: E402
+from pp_amd.pipeline import PillarPipeline  # noqa: E402
+from pp_amd.voxelizer import VoxelConfig  # noqa: E402
+
+rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 3
+steps = int(sys.argv[2]) if len(sys.argv) > 2 else 50
+B = 4
+dev = torch.device("cuda", 0)
+torch.backends.cudnn.benchmark = True
+pipe = PillarPipeline(VoxelConfig.square(bench.HALF, bench.STEP, bench.P, bench.N), device=dev, seed=0)
+pipe.model.eval()
+sets = [torch.from_numpy(np.stack([synth.lidar_like(bench.N_POINTS, bench.HALF, 1000 * r + s)
+                                   for s in range(B)])).to(dev) for r in range(4)]
+
+
+def run(n):
+    k = 0
+    for _ in range(n):
+        k += 1
+        pipe.forward_pipelined(sets[k % 4])
+
+
+legs = {"fp16": [], "f32": []}
+for name in legs:
+    pipe.model.set_inference_precision(name)
+    run(20)                                  # warm-up: MIOpen's find, the filter packing
+torch.cuda.synchronize()
+for r in range(rounds):
+    for name in (("fp16", "f32") if r % 2 == 0 else ("f32", "fp16")):
+        pipe.model.set_inference_precision(name)
+        run(5)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        run(steps)
+        torch.cuda.synchronize()
+        legs[name].append((time.perf_counter() - t) * 1e3 / steps)
+res = {k: {"ms_per_step": v, "median": float(np.median(v)), "spread": max(v) - min(v)} for k, v in legs.items()}
+res["speedup"] = res["f32"]["median"] / res["fp16"]["median"]
+# the bar: the slowest fp16 leg ahead of the fastest f32 leg by 10x the larger within-leg spread
+res["margin_ms"] = min(legs["f32"]) - max(legs["fp16"])
+res["margin_over_spread"] = res["margin_ms"] / max(res["fp16"]["spread"], res["f32"]["spread"], 1e-9)
+print(json.dumps({"ab_f16": res}))
+
+# both modes on the same input
+out = {}
+for name in ("f32", "fp16"):
+    pipe.model.set_inference_precision(name)
+    out[name] = tuple(t.clone() for t in pipe.forward(sets[0]))
+pipe.model.set_inference_precision("f32")
+torch.cuda.synchronize()
+print(json.dumps({"fp16_vs_f32": {
+    k: {"max_abs_diff": float((a - b).abs().max()), "max_abs_f32": float(b.abs().max()),
+        "rel": float((a - b).abs().max()) / float(b.abs().max()), "finite": bool(torch.isfinite(a).all())}
+    for k, a, b in zip(("cls", "reg"), out["fp16"], out["f32"])}}))
+
+
+def timeit(fn, n=30):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(n):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / n * 1e3
+
+
+rows = []
+for name, cin, cout, h, count in (("down1.k", 64, 64, 250, 3), ("down2.k", 128, 128, 125, 5),
+                                  ("down3.k", 256, 256, 63, 5), ("up1", 64, 128, 250, 1)):
+    x = torch.randn(B, cin, h, h, device=dev).contiguous(memory_format=torch.channels_last)
+    w = torch.randn(cout, cin, 3, 3, device=dev) * 0.05
+    tab = torch.stack([torch.zeros(cout), torch.ones(cout), torch.zeros(cout)], 1).to(dev).contiguous()
+    u, w16 = M._wino_filter(w), M._f16_filter(w)
+    with torch.no_grad():
+        t_w = timeit(lambda: M._conv_wino(x, u, tab, cout))
+        t_h = timeit(lambda: M._conv_f16(x, w16, tab, cout))
+    xy_bytes = 4.0 * B * h * h * (cin + cout)            # x read once + y written once, f32
+    df = 2.0 * B * h * h * cin * cout * 9
+    rows.append({"layer": name, "count": count, "f16_us": t_h, "wino_us": t_w, "speedup": t_w / t_h,
+                 "f16_xy_GBs": xy_bytes / t_h / 1e3, "f16_direct_TFs": df / t_h / 1e6,
+                 "wino_direct_equiv_TFs": df / t_w / 1e6})
+print(json.dumps({"per_layer": rows}))
