@@ -20,59 +20,51 @@ import torch.nn.functional as F
 from . import _lib
 
 
-class _Epilogue:
-    """Inference-only fused ``ReLU -> BatchNorm2d(eval)`` (+ conv bias) in place, one HIP
-    kernel (csrc/pp_epilogue.hip).  The per-channel table is rebuilt only when a
-    parameter / running statistic of the (conv, bn) pair changed."""
+_ctx = {}   # device index -> _lib.Context
 
-    _ctx = {}
 
-    def __init__(self):
-        self._key = None
-        self._table = None
+def _hip_ctx(dev):
+    ctx = _ctx.get(dev.index)
+    if ctx is None:
+        ctx = _ctx[dev.index] = _lib.Context(dev.index)
+    return ctx
 
-    def table(self, bias, bn):
-        # num_batches_tracked: the fused training kernels update running_mean / running_var
-        # through raw pointers (no version bump), but every such step bumps the counter
-        ts = (bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked)
-        key = tuple((t.data_ptr(), t._version) for t in ts if t is not None)
-        if key != self._key:
-            with torch.no_grad():
-                scale = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
-                shift = bn.bias.double() - bn.running_mean.double() * scale
-                b = bias.double() if bias is not None else torch.zeros_like(scale)
-                self._table = torch.stack([b, scale, shift], 1).float().contiguous()
-            self._key = key
-        return self._table
 
-    def __call__(self, y, bias, bn, out=None, channel_offset=0):
-        """In place on ``y`` [B,C,H,W], or into channels [channel_offset, +C) of ``out``.
-        ``y`` (and ``out``) may be NCHW-contiguous or channels-last."""
-        dev = y.device
-        ctx = _Epilogue._ctx.get(dev.index)
-        if ctx is None:
-            ctx = _Epilogue._ctx[dev.index] = _lib.Context(dev.index)
-        tab = self.table(bias, bn)
-        B, C, H, W = y.shape
-        nhwc = _is_nhwc(y)
-        if out is not None and (out.shape[0] != B or out.shape[2:] != y.shape[2:] or out.dtype != y.dtype
-                                or (_is_nhwc(out) if nhwc else out.is_contiguous()) is not True):
-            raise ValueError("epilogue destination does not match the source")
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        dst = ctypes.c_void_p(out.data_ptr()) if out is not None else None
-        if nhwc:
-            rc = _lib.lib().pp_bias_relu_bn_nhwc_dev(
-                ctx.handle, stream, ctypes.c_void_p(y.data_ptr()), B * H * W, C,
-                ctypes.c_void_p(tab.data_ptr()), dst, out.shape[1] if out is not None else C,
-                int(channel_offset))
-            _lib.check(rc, "pp_bias_relu_bn_nhwc_dev")
-        else:
-            rc = _lib.lib().pp_bias_relu_bn_dev(
-                ctx.handle, stream, ctypes.c_void_p(y.data_ptr()), B, C, H * W,
-                ctypes.c_void_p(tab.data_ptr()), dst, out.shape[1] if out is not None else C,
-                int(channel_offset))
-            _lib.check(rc, "pp_bias_relu_bn_dev")
-        return y if out is None else out
+def _vp(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _call(name, dev, *args):
+    """The library's entry point ``name`` on ``dev``'s context and current stream; raises unless it succeeds."""
+    rc = getattr(_lib.lib(), name)(_hip_ctx(dev).handle,
+                                   ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), *args)
+    _lib.check(rc, name)
+
+
+def _bn_affine(bn):
+    """Eval-mode BatchNorm as the per-channel map ``scale * x + shift``, in f64."""
+    scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.double() + bn.eps)
+    shift = bn.bias.detach().double() - bn.running_mean.double() * scale
+    return scale, shift
+
+
+def _epilogue(y, table, out=None, channel_offset=0):
+    """Inference-only fused ``ReLU -> BatchNorm2d(eval)`` (+ conv bias), one HIP kernel (csrc/pp_epilogue.hip):
+    in place on ``y`` [B,C,H,W], or into channels [channel_offset, +C) of ``out``.  ``y`` (and ``out``) may be
+    NCHW-contiguous or channels-last; ``table`` is ``_FusedConv.table``'s."""
+    B, C, H, W = y.shape
+    nhwc = _is_nhwc(y)
+    if out is not None and (out.shape[0] != B or out.shape[2:] != y.shape[2:] or out.dtype != y.dtype
+                            or (_is_nhwc(out) if nhwc else out.is_contiguous()) is not True):
+        raise ValueError("epilogue destination does not match the source")
+    width = out.shape[1] if out is not None else C
+    if nhwc:
+        _call("pp_bias_relu_bn_nhwc_dev", y.device, _vp(y), B * H * W, C, _vp(table), _vp(out), width,
+              int(channel_offset))
+    else:
+        _call("pp_bias_relu_bn_dev", y.device, _vp(y), B, C, H * W, _vp(table), _vp(out), width,
+              int(channel_offset))
+    return y if out is None else out
 
 
 def _is_nhwc(t):
@@ -105,13 +97,6 @@ class _LayoutCache:
         return self._val
 
 
-def _weight_like(x, weight, cache):
-    """The conv weight in the memory format of the activation ``x``."""
-    if not _is_nhwc(x):
-        return weight
-    return cache.get((weight,), lambda: weight.detach().contiguous(memory_format=torch.channels_last))
-
-
 #: Winograd F(2x2,3x3) filter transform G (U = G g G^T)
 _WINO_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
 
@@ -126,29 +111,39 @@ def _wino_filter(w):
     return u.reshape(16, ci // 8, 2, 4, co).permute(0, 1, 2, 4, 3).float().contiguous()
 
 
-def _wino_ok(module, conv, x, transposed=False):
-    """The fused Winograd kernel takes this layer: 3x3, stride 1, padding 1 (ConvTranspose: no
-    output padding), a dense 16-byte aligned channels-last input, Cin % 8 == 0, Cout % 64 == 0."""
-    return (module.winograd and _is_nhwc(x) and x.data_ptr() % 16 == 0
-            and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1)
+def _is_conv3x3(conv, stride, transposed=False):
+    """3x3, the given stride, padding 1, no dilation, no groups (ConvTranspose: no output padding)."""
+    return (tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (stride, stride)
             and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.groups == 1
-            and (not transposed or tuple(conv.output_padding) == (0, 0))
-            and x.shape[1] == conv.in_channels and conv.in_channels % 8 == 0 and conv.out_channels % 64 == 0)
+            and (not transposed or tuple(conv.output_padding) == (0, 0)))
+
+
+def _conv3x3_s1_ok(conv, x, cin_multiple, transposed):
+    """What both fused stride-1 kernels ask of a layer and its input: ``_is_conv3x3`` at stride 1, a dense
+    16-byte aligned channels-last input, Cin a multiple of ``cin_multiple``, Cout % 64 == 0."""
+    return (_is_nhwc(x) and x.data_ptr() % 16 == 0 and _is_conv3x3(conv, 1, transposed)
+            and x.shape[1] == conv.in_channels and conv.in_channels % cin_multiple == 0
+            and conv.out_channels % 64 == 0)
+
+
+def _wino_ok(module, conv, x, transposed=False):
+    """The fused Winograd kernel takes this layer: the module's ``winograd`` flag, Cin % 8 == 0."""
+    return module.winograd and _conv3x3_s1_ok(conv, x, 8, transposed)
+
+
+def _conv3x3_nhwc(name, x, w, table, cout, out, channel_offset):
+    """A fused stride-1 conv entry point: conv + bias/ReLU/BatchNorm of ``x`` (NHWC) into a new channels-last
+    tensor, or into channels [channel_offset, +cout) of the channels-last ``out``."""
+    B, C, H, W = x.shape
+    if out is None:
+        out = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    _call(name, x.device, _vp(x), B, H, W, C, _vp(w), cout, _vp(table), _vp(out), out.shape[1], int(channel_offset))
+    return out
 
 
 def _conv_wino(x, u, table, cout, out=None, channel_offset=0):
-    """pp_conv3x3_wino_nhwc_dev: conv + bias/ReLU/BatchNorm of ``x`` (NHWC) into a new channels-last
-    tensor, or into channels [channel_offset, +cout) of the channels-last ``out``."""
-    B, C, H, W = x.shape
-    dev = x.device
-    if out is None:
-        out = torch.empty((B, cout, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-    rc = _lib.lib().pp_conv3x3_wino_nhwc_dev(
-        _hip_ctx(dev).handle, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
-        ctypes.c_void_p(x.data_ptr()), B, H, W, C, ctypes.c_void_p(u.data_ptr()), cout,
-        ctypes.c_void_p(table.data_ptr()), ctypes.c_void_p(out.data_ptr()), out.shape[1], int(channel_offset))
-    _lib.check(rc, "pp_conv3x3_wino_nhwc_dev")
-    return out
+    """pp_conv3x3_wino_nhwc_dev (``u`` from ``_wino_filter``), f32 throughout."""
+    return _conv3x3_nhwc("pp_conv3x3_wino_nhwc_dev", x, u, table, cout, out, channel_offset)
 
 
 def _f16_filter(w):
@@ -160,28 +155,14 @@ def _f16_filter(w):
 
 
 def _f16_ok(module, conv, x, transposed=False):
-    """The fp16-operand MFMA kernel takes this layer: the module's ``half_mma`` flag and ``_wino_ok``'s
-    conditions on the layer and its input, with Cin % 16 == 0."""
-    return (module.half_mma and _is_nhwc(x) and x.data_ptr() % 16 == 0
-            and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1)
-            and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.groups == 1
-            and (not transposed or tuple(conv.output_padding) == (0, 0))
-            and x.shape[1] == conv.in_channels and conv.in_channels % 16 == 0 and conv.out_channels % 64 == 0)
+    """The fp16-operand MFMA kernel takes this layer: the module's ``half_mma`` flag, Cin % 16 == 0."""
+    return module.half_mma and _conv3x3_s1_ok(conv, x, 16, transposed)
 
 
 def _conv_f16(x, w16, table, cout, out=None, channel_offset=0):
     """pp_conv3x3_f16_nhwc_dev: ``_conv_wino``'s layer with fp16 operands (``w16`` from ``_f16_filter``) and
     f32 accumulation; f32 activations in and out."""
-    B, C, H, W = x.shape
-    dev = x.device
-    if out is None:
-        out = torch.empty((B, cout, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-    rc = _lib.lib().pp_conv3x3_f16_nhwc_dev(
-        _hip_ctx(dev).handle, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
-        ctypes.c_void_p(x.data_ptr()), B, H, W, C, ctypes.c_void_p(w16.data_ptr()), cout,
-        ctypes.c_void_p(table.data_ptr()), ctypes.c_void_p(out.data_ptr()), out.shape[1], int(channel_offset))
-    _lib.check(rc, "pp_conv3x3_f16_nhwc_dev")
-    return out
+    return _conv3x3_nhwc("pp_conv3x3_f16_nhwc_dev", x, w16, table, cout, out, channel_offset)
 
 
 def _stem_filter(w):
@@ -198,9 +179,7 @@ def _stem_ok(backbone, scatter, feats, inds):
     return (backbone.sparse_stem and _use_fused_epilogue(d1, feats) and not scatter.training
             and scatter.channels_last_inference and feats.dim() == 3 and inds.dtype == torch.int64
             and inds.is_cuda and tuple(inds.shape) == (feats.shape[0], feats.shape[2], 3) and feats.shape[2] > 0
-            and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (2, 2)
-            and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.groups == 1
-            and feats.shape[1] == conv.in_channels and conv.in_channels % 8 == 0
+            and _is_conv3x3(conv, 2) and feats.shape[1] == conv.in_channels and conv.in_channels % 8 == 0
             and conv.out_channels % 64 == 0)
 
 
@@ -217,12 +196,8 @@ def _conv_stem(feats, inds, h, w, w_taps, table, cout):
     scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     out = torch.empty((B, cout, (h + 1) // 2, (w + 1) // 2), dtype=torch.float32, device=dev,
                       memory_format=torch.channels_last)
-    rc = _lib.lib().pp_conv3x3_s2_pillars_nhwc_dev(
-        _hip_ctx(dev).handle, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
-        ctypes.c_void_p(feats.data_ptr()), ctypes.c_void_p(inds.data_ptr()), B, C, P, int(h), int(w),
-        ctypes.c_void_p(w_taps.data_ptr()), cout, ctypes.c_void_p(table.data_ptr()),
-        ctypes.c_void_p(scratch.data_ptr()), nbytes, ctypes.c_void_p(out.data_ptr()))
-    _lib.check(rc, "pp_conv3x3_s2_pillars_nhwc_dev")
+    _call("pp_conv3x3_s2_pillars_nhwc_dev", dev, _vp(feats), _vp(inds), B, C, P, int(h), int(w), _vp(w_taps), cout,
+          _vp(table), _vp(scratch), nbytes, _vp(out))
     return out
 
 
@@ -233,11 +208,73 @@ def _use_fused_epilogue(module, x):
             and not torch.is_grad_enabled())
 
 
-def _hip_ctx(dev):
-    ctx = _Epilogue._ctx.get(dev.index)
-    if ctx is None:
-        ctx = _Epilogue._ctx[dev.index] = _lib.Context(dev.index)
-    return ctx
+def _nhwc_weight(w):
+    return w.detach().contiguous(memory_format=torch.channels_last)
+
+
+class _FusedConv:
+    """One conv + BatchNorm pair on the no-grad inference path: which kernel takes it, and what that kernel needs
+    beside the activation.  Not a module and no owner of parameters: it caches the epilogue table and the conv weight
+    as each kernel wants it packed, and rebuilds either when a tensor it was made from was edited or replaced (so a
+    copied or moved model starts over)."""
+
+    def __init__(self):
+        self._table_key = None
+        self._table = None
+        self._packed = {}           # kind ("nhwc", "wino", "f16", "stem") -> (key, packed weight)
+
+    def table(self, bias, bn):
+        """[C,3] f32: conv bias, BatchNorm scale, BatchNorm shift."""
+        # num_batches_tracked: the fused training kernels update running_mean / running_var
+        # through raw pointers (no version bump), but every such step bumps the counter
+        ts = (bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked)
+        key = tuple((t.data_ptr(), t._version) for t in ts if t is not None)
+        if key != self._table_key:
+            with torch.no_grad():
+                scale, shift = _bn_affine(bn)
+                b = bias.double() if bias is not None else torch.zeros_like(scale)
+                self._table = torch.stack([b, scale, shift], 1).float().contiguous()
+            self._table_key = key
+        return self._table
+
+    def packed(self, kind, weight, pack, transposed=False):
+        """``pack(weight)``, made once per version of ``weight``.  ``transposed``: the weight of a stride-1
+        ConvTranspose, packed as the conv weight it stands for: w_conv[co][ci][kh][kw] = w_t[ci][co][2-kh][2-kw]."""
+        key = (weight.data_ptr(), weight._version)
+        hit = self._packed.get(kind)
+        if hit is None or hit[0] != key:
+            with torch.no_grad():
+                hit = self._packed[kind] = (key, pack(weight.transpose(0, 1).flip(2, 3) if transposed else weight))
+        return hit[1]
+
+    def __call__(self, module, conv, bn, x, out=None, channel_offset=0, transposed=False):
+        """``bn(relu(conv(x)))`` into a new tensor, or into channels [channel_offset, +Cout) of ``out``: the fp16
+        kernel if ``module.half_mma`` and the layer is eligible, else the Winograd kernel if ``module.winograd``
+        and the layer is eligible, else MIOpen's conv (``transposed``: ConvTranspose) and the epilogue kernel."""
+        out_ok = out is None or (_is_nhwc(out) and out.dtype == torch.float32 and out.shape[0] == x.shape[0]
+                                 and out.shape[2:] == x.shape[2:])
+        if _f16_ok(module, conv, x, transposed) and out_ok and (out is None or out.data_ptr() % 16 == 0):
+            w16 = self.packed("f16", conv.weight, _f16_filter, transposed)
+            return _conv_f16(x, w16, self.table(conv.bias, bn), conv.out_channels, out, channel_offset)
+        if _wino_ok(module, conv, x, transposed) and out_ok:
+            u = self.packed("wino", conv.weight, _wino_filter, transposed)
+            return _conv_wino(x, u, self.table(conv.bias, bn), conv.out_channels, out, channel_offset)
+        w = self.packed("nhwc", conv.weight, _nhwc_weight) if _is_nhwc(x) else conv.weight
+        if transposed:
+            y = F.conv_transpose2d(x, w, None, conv.stride, conv.padding, conv.output_padding)
+            if out is not None and _is_nhwc(out) != _is_nhwc(y):
+                y = y.contiguous(memory_format=torch.channels_last if _is_nhwc(out) else torch.contiguous_format)
+        else:
+            y = F.conv2d(x, w, None, conv.stride, conv.padding)
+        return _epilogue(_dense(y), self.table(conv.bias, bn), out, channel_offset)
+
+
+def _pfn_dense(x, table):
+    """pp_pfn_dense_dev: the feature net of ``x`` [B,9,P,N] from its [64,12] ``table`` in one pass, [B,64,P]."""
+    B, D, P, N = x.shape
+    out = torch.empty((B, 64, P), dtype=torch.float32, device=x.device)
+    _call("pp_pfn_dense_dev", x.device, _vp(x), B, P, N, _vp(table), 64, _vp(out))
+    return out
 
 
 class _PfnTrain(torch.autograd.Function):
@@ -251,14 +288,10 @@ class _PfnTrain(torch.autograd.Function):
         B, D, P, N = x.shape
         M = B * P * N
         dev = x.device
-        h = _hip_ctx(dev)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         w = weight.detach().reshape(64, 9)
         wb = torch.cat([w, bias.detach().reshape(64, 1)], 1).contiguous()
         sums = torch.empty((21, 64), dtype=torch.float64, device=dev)
-        _lib.check(_lib.lib().pp_pfn_train_stats_dev(h.handle, stream, vp(x), B, P, N, vp(wb), 64, vp(sums)),
-                   "pp_pfn_train_stats_dev")
+        _call("pp_pfn_train_stats_dev", dev, _vp(x), B, P, N, _vp(wb), 64, _vp(sums))
         c0 = bias.detach().double().clamp(min=0.0)               # r on a zero-padded slot; sums are about it
         dm = sums[1] / M
         mean = c0 + dm
@@ -267,9 +300,7 @@ class _PfnTrain(torch.autograd.Function):
         scale = gamma.detach().double() * invstd
         shift = beta.detach().double() - mean * scale
         table = torch.cat([wb.double(), scale[:, None], shift[:, None]], 1).float().contiguous()   # [64,12]
-        out = torch.empty((B, 64, P), dtype=torch.float32, device=dev)
-        _lib.check(_lib.lib().pp_pfn_dense_dev(h.handle, stream, vp(x), B, P, N, vp(table), 64, vp(out)),
-                   "pp_pfn_dense_dev")
+        out = _pfn_dense(x, table)
         if running_mean is not None:
             with torch.no_grad():
                 running_mean.mul_(1.0 - momentum).add_(mean.to(running_mean.dtype), alpha=momentum)
@@ -286,14 +317,10 @@ class _PfnTrain(torch.autograd.Function):
         B, D, P, N = x.shape
         M = float(ctx.M)
         dev = x.device
-        h = _hip_ctx(dev)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         g = g.contiguous().float()
         bs = torch.empty((12, 64), dtype=torch.float64, device=dev)
-        _lib.check(_lib.lib().pp_pfn_train_backward_dev(h.handle, stream, vp(x), B, P, N, vp(table), vp(mean32),
-                                                        vp(invstd32), vp(g), 64, vp(bs)),
-                   "pp_pfn_train_backward_dev")
+        _call("pp_pfn_train_backward_dev", dev, _vp(x), B, P, N, _vp(table), _vp(mean32), _vp(invstd32), _vp(g), 64,
+              _vp(bs))
         dbeta, dgamma, db_sel, dw_sel = bs[0], bs[1], bs[2], bs[3:12]
         scale, mean, invstd = table[:, 10].double(), mean32.double(), invstd32.double()
         a = scale * (-dbeta / M + mean * dgamma * invstd / M)      # dr = s*dy + a + b*r on z > 0
@@ -313,15 +340,11 @@ class _ReluBnTrain(torch.autograd.Function):
     def forward(ctx, z, conv_bias, gamma, beta, running_mean, running_var, momentum, eps):
         B, C, H, W = z.shape
         dev = z.device
-        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
         y = torch.empty_like(z)
         mean = torch.empty((C,), dtype=torch.float32, device=dev)
         invstd = torch.empty((C,), dtype=torch.float32, device=dev)
-        rc = _lib.lib().pp_relu_bn_train_fwd_dev(
-            _hip_ctx(dev).handle, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), vp(z),
-            vp(conv_bias), B, C, H * W, vp(gamma), vp(beta), float(eps), float(momentum), vp(running_mean),
-            vp(running_var), vp(y), vp(mean), vp(invstd))
-        _lib.check(rc, "pp_relu_bn_train_fwd_dev")
+        _call("pp_relu_bn_train_fwd_dev", dev, _vp(z), _vp(conv_bias), B, C, H * W, _vp(gamma), _vp(beta), float(eps),
+              float(momentum), _vp(running_mean), _vp(running_var), _vp(y), _vp(mean), _vp(invstd))
         ctx.save_for_backward(z, conv_bias, gamma, mean, invstd)
         return y
 
@@ -330,7 +353,6 @@ class _ReluBnTrain(torch.autograd.Function):
         z, conv_bias, gamma, mean, invstd = ctx.saved_tensors
         B, C, H, W = z.shape
         dev = z.device
-        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
         # a channel slice of a wider NCHW tensor (torch.cat's gradient) is read in place
         if not (dy.dtype == torch.float32 and dy.stride(3) == 1 and dy.stride(2) == W and dy.stride(1) == H * W
                 and (B == 1 or dy.stride(0) >= C * H * W)):
@@ -339,11 +361,8 @@ class _ReluBnTrain(torch.autograd.Function):
         dgamma = torch.empty((C,), dtype=torch.float32, device=dev)
         dbeta = torch.empty((C,), dtype=torch.float32, device=dev)
         dbias = torch.empty((C,), dtype=torch.float32, device=dev) if conv_bias is not None else None
-        rc = _lib.lib().pp_relu_bn_train_bwd_dev(
-            _hip_ctx(dev).handle, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), vp(z),
-            vp(conv_bias), vp(dy), dy.stride(0) if B > 1 else 0, B, C, H * W, vp(gamma), vp(mean), vp(invstd), vp(dz), vp(dgamma), vp(dbeta),
-            vp(dbias))
-        _lib.check(rc, "pp_relu_bn_train_bwd_dev")
+        _call("pp_relu_bn_train_bwd_dev", dev, _vp(z), _vp(conv_bias), _vp(dy), dy.stride(0) if B > 1 else 0, B, C,
+              H * W, _vp(gamma), _vp(mean), _vp(invstd), _vp(dz), _vp(dgamma), _vp(dbeta), _vp(dbias))
         return dz, dbias, dgamma, dbeta, None, None, None, None
 
 
@@ -384,14 +403,17 @@ class PPFeatureNet(nn.Module):
         self.hip_train = True
         self._params = _LayoutCache()
 
+    def _hip_takes(self, x):
+        """The HIP feature-net kernels are written for 9 -> 64 channels, f32, on the GPU."""
+        return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 9
+                and self.conv1.out_channels == 64)
+
     def forward(self, x):                  # [B,D,P,N]
         if not self.training and self.fast_eval:
-            if (self.hip_eval and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
-                    and x.shape[1] == 9 and self.conv1.out_channels == 64 and not torch.is_grad_enabled()):
+            if self.hip_eval and self._hip_takes(x) and not torch.is_grad_enabled():
                 return self.forward_hip(x)
             return self.forward_eval(x)
-        if (self.training and self.hip_train and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
-                and x.shape[1] == 9 and self.conv1.out_channels == 64 and not x.requires_grad
+        if (self.training and self.hip_train and self._hip_takes(x) and not x.requires_grad
                 and self.bn1.track_running_stats and self.bn1.momentum is not None and self.bn1.affine
                 and x.numel() > 0):
             out = _PfnTrain.apply(x if x.is_contiguous() else x.contiguous(), self.conv1.weight,
@@ -422,20 +444,7 @@ class PPFeatureNet(nn.Module):
 
     def forward_hip(self, x):
         """pp_pfn_dense_dev: the same function as ``forward_eval`` in one pass over ``x``."""
-        x = x if x.is_contiguous() else x.contiguous()
-        B, D, P, N = x.shape
-        dev = x.device
-        ctx = _Epilogue._ctx.get(dev.index)
-        if ctx is None:
-            ctx = _Epilogue._ctx[dev.index] = _lib.Context(dev.index)
-        tab = self.fused_table(dev)
-        out = torch.empty((B, 64, P), dtype=torch.float32, device=dev)
-        rc = _lib.lib().pp_pfn_dense_dev(
-            ctx.handle, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
-            ctypes.c_void_p(x.data_ptr()), B, P, N, ctypes.c_void_p(tab.data_ptr()), 64,
-            ctypes.c_void_p(out.data_ptr()))
-        _lib.check(rc, "pp_pfn_dense_dev")
-        return out
+        return _pfn_dense(x if x.is_contiguous() else x.contiguous(), self.fused_table(x.device))
 
     def fused_table(self, dev):
         """``fused_params()`` on ``dev``, rebuilt whenever a weight or BatchNorm statistic of the
@@ -453,8 +462,7 @@ class PPFeatureNet(nn.Module):
         an affine map: scale = gamma/sqrt(var+eps), shift = beta - mean*scale."""
         w = self.conv1.weight.detach().double().reshape(self.conv1.out_channels, -1)
         b = self.conv1.bias.detach().double()
-        scale = self.bn1.weight.detach().double() / torch.sqrt(self.bn1.running_var.double() + self.bn1.eps)
-        shift = self.bn1.bias.detach().double() - self.bn1.running_mean.double() * scale
+        scale, shift = _bn_affine(self.bn1)
         return torch.cat([w, b[:, None], scale[:, None], shift[:, None]], dim=1).float().contiguous()
 
 
@@ -481,11 +489,7 @@ class PPScatter(nn.Module):
                 inds = inds if inds.is_contiguous() else inds.contiguous()
                 out = torch.empty((B, C, self.h, self.w), dtype=torch.float32, device=x.device,
                                   memory_format=torch.channels_last)
-                rc = _lib.lib().pp_scatter_canvas_dev(
-                    _hip_ctx(x.device).handle, ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream),
-                    ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(inds.data_ptr()), B, C, P,
-                    ctypes.c_void_p(out.data_ptr()), self.h, self.w, 1)
-                _lib.check(rc, "pp_scatter_canvas_dev")
+                _call("pp_scatter_canvas_dev", x.device, _vp(x), _vp(inds), B, C, P, _vp(out), self.h, self.w, 1)
                 return out
         lin = inds[:, :, 2] * self.w + inds[:, :, 1]
         if nhwc:
@@ -515,24 +519,21 @@ class PPDownBlock(nn.Module):
         self.fused_epilogue = True
         #: training: ReLU -> BatchNorm2d (batch statistics) through the fused HIP kernels
         self.fused_train = True
-        self._epi = [_Epilogue() for _ in range(num_layers)]
-        self._wcl = [_LayoutCache() for _ in range(num_layers)]
         #: ... and on that path the stride-1 layers as one fused Winograd F(2x2,3x3) kernel each
         #: (csrc/pp_wino.hip: conv and epilogue in one pass, no MIOpen call)
         self.winograd = True
-        self._wino = [_LayoutCache() for _ in range(num_layers)]
         #: opt-in "fp16 inference" (PPModel.set_inference_precision): those layers with fp16 operands and
         #: f32 accumulation instead (csrc/pp_conv_f16.hip); changes results at the 1e-4 level
         self.half_mma = False
-        self._f16 = [_LayoutCache() for _ in range(num_layers)]
-        self._stem = _LayoutCache()
+        self._fused = [_FusedConv() for _ in range(num_layers)]
 
     def stem(self, feats, inds, h, w):
         """Layer 0 on the pillars themselves (``_stem_ok`` holds): what ``forward`` makes of PPScatter's
         canvas in its first layer, as one fused kernel pair that never builds the canvas."""
         conv, bn = self.block[0], self.block[2]
-        w_taps = self._stem.get((conv.weight,), lambda: _stem_filter(conv.weight))
-        return _conv_stem(feats, inds, h, w, w_taps, self._epi[0].table(conv.bias, bn), conv.out_channels)
+        fused = self._fused[0]
+        w_taps = fused.packed("stem", conv.weight, _stem_filter)
+        return _conv_stem(feats, inds, h, w, w_taps, fused.table(conv.bias, bn), conv.out_channels)
 
     def forward(self, x, first=0):
         """``first`` = 1: ``x`` is ``stem``'s output and has passed layer 0 already."""
@@ -540,24 +541,14 @@ class PPDownBlock(nn.Module):
             if first:
                 raise RuntimeError("PPDownBlock: a tensor past layer 0 needs the fused inference path")
             if self.training and self.fused_train and x.is_cuda:
-                for i in range(len(self._epi)):
+                for i in range(len(self._fused)):
                     conv, bn = self.block[3 * i], self.block[3 * i + 2]
                     x = _relu_bn(F.conv2d(x, conv.weight, None, conv.stride, conv.padding), bn,
                                  conv_bias=conv.bias)
                 return x
             return self.block(x)
-        for i in range(first, len(self._epi)):
-            epi, conv, bn = self._epi[i], self.block[3 * i], self.block[3 * i + 2]
-            if _f16_ok(self, conv, x):
-                w16 = self._f16[i].get((conv.weight,), lambda: _f16_filter(conv.weight))
-                x = _conv_f16(x, w16, epi.table(conv.bias, bn), conv.out_channels)
-                continue
-            if _wino_ok(self, conv, x):
-                u = self._wino[i].get((conv.weight,), lambda: _wino_filter(conv.weight))
-                x = _conv_wino(x, u, epi.table(conv.bias, bn), conv.out_channels)
-                continue
-            x = F.conv2d(x, _weight_like(x, conv.weight, self._wcl[i]), None, conv.stride, conv.padding)
-            x = epi(_dense(x), conv.bias, bn)
+        for i in range(first, len(self._fused)):
+            x = self._fused[i](self, self.block[3 * i], self.block[3 * i + 2], x)
         return x
 
 
@@ -571,12 +562,9 @@ class PPUpBlock(nn.Module):
         self.bn = nn.BatchNorm2d(out_channels)
         self.fused_epilogue = True
         self.fused_train = True
-        self._epi = _Epilogue()
-        self._wcl = _LayoutCache()
         self.winograd = True
-        self._wino = _LayoutCache()
         self.half_mma = False
-        self._f16 = _LayoutCache()
+        self._fused = _FusedConv()
 
     def forward(self, x, out=None, channel_offset=0):
         if not _use_fused_epilogue(self, x):
@@ -585,21 +573,7 @@ class PPUpBlock(nn.Module):
                 return _relu_bn(F.conv_transpose2d(x, ct.weight, None, ct.stride, ct.padding, ct.output_padding),
                                 self.bn, conv_bias=ct.bias)
             return self.bn(F.relu(self.conv2d_t(x)))
-        ct = self.conv2d_t
-        out_ok = out is None or (_is_nhwc(out) and out.dtype == torch.float32 and out.shape[0] == x.shape[0]
-                                 and out.shape[2:] == x.shape[2:])
-        # stride 1: the transposed conv is a conv with w_conv[co][ci][kh][kw] = w_t[ci][co][2-kh][2-kw]
-        if _f16_ok(self, ct, x, transposed=True) and out_ok and (out is None or out.data_ptr() % 16 == 0):
-            w16 = self._f16.get((ct.weight,), lambda: _f16_filter(ct.weight.transpose(0, 1).flip(2, 3)))
-            return _conv_f16(x, w16, self._epi.table(ct.bias, self.bn), ct.out_channels, out, channel_offset)
-        if _wino_ok(self, ct, x, transposed=True) and out_ok:
-            u = self._wino.get((ct.weight,), lambda: _wino_filter(ct.weight.transpose(0, 1).flip(2, 3)))
-            return _conv_wino(x, u, self._epi.table(ct.bias, self.bn), ct.out_channels, out, channel_offset)
-        y = F.conv_transpose2d(x, _weight_like(x, ct.weight, self._wcl), None, ct.stride, ct.padding,
-                               ct.output_padding)
-        if out is not None and _is_nhwc(out) != _is_nhwc(y):
-            y = y.contiguous(memory_format=torch.channels_last if _is_nhwc(out) else torch.contiguous_format)
-        return self._epi(_dense(y), ct.bias, self.bn, out, channel_offset)
+        return self._fused(self, self.conv2d_t, self.bn, x, out, channel_offset, transposed=True)
 
 
 def up3_output_padding(canvas):
@@ -633,27 +607,21 @@ class PPBackbone(nn.Module):
 
     def forward(self, x, after_stem=False):
         """``after_stem``: ``x`` is ``down1.stem``'s output instead of the canvas."""
-        first = 1 if after_stem else 0
-        if _use_fused_epilogue(self.up1, x):
-            # inference: the three up blocks write their channel slices of the concatenated
-            # output directly (no torch.cat copy)
-            c = self.up1.conv2d_t.out_channels
-            x = self.down1(x, first)
+        # inference: the three up blocks write their channel slices of the concatenated output directly (no
+        # torch.cat copy); otherwise ``out`` is None, the offsets are 0 and each returns its own tensor
+        fused = _use_fused_epilogue(self.up1, x)
+        c = self.up1.conv2d_t.out_channels if fused else 0
+        x = self.down1(x, 1 if after_stem else 0)
+        out = None
+        if fused:
             out = torch.empty((x.shape[0], 3 * c, x.shape[2], x.shape[3]), dtype=x.dtype, device=x.device,
                               memory_format=torch.channels_last if _is_nhwc(x) else torch.contiguous_format)
-            self.up1(x, out, 0)
-            x = self.down2(x)
-            self.up2(x, out, c)
-            x = self.down3(x)
-            self.up3(x, out, 2 * c)
-            return out
-        x = self.down1(x, first)
-        out1 = self.up1(x)
+        out1 = self.up1(x, out, 0)
         x = self.down2(x)
-        out2 = self.up2(x)
+        out2 = self.up2(x, out, c)
         x = self.down3(x)
-        out3 = self.up3(x)
-        return torch.cat((out1, out2, out3), dim=1)
+        out3 = self.up3(x, out, 2 * c)
+        return out if fused else torch.cat((out1, out2, out3), dim=1)
 
 
 class PPDetectionHead(nn.Module):

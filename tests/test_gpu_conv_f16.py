@@ -332,7 +332,7 @@ def test_end_to_end_small(gpu, monkeypatch):
 
     emul = copy.deepcopy(model)
     bb = emul.backbone
-    layers = [blk.block[3 * i] for blk in (bb.down1, bb.down2, bb.down3) for i in range(1, len(blk._epi))]
+    layers = [blk.block[3 * i] for blk in (bb.down1, bb.down2, bb.down3) for i in range(1, len(blk._fused))]
     layers.append(bb.up1.conv2d_t)
     assert len(layers) == 14
     with torch.no_grad():

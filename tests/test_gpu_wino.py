@@ -141,8 +141,8 @@ def test_channel_offset_into_wider_output_and_up1(gpu):
         assert bool((rest == 7.0).all())
     w_conv = blk.conv2d_t.weight.transpose(0, 1).flip(2, 3)
     with torch.no_grad():
-        y = _run(x, w_conv, blk._epi.table(blk.conv2d_t.bias, blk.bn))
-    _check(x, w_conv, blk._epi.table(blk.conv2d_t.bias, blk.bn), y, "up1 64->128@50")
+        y = _run(x, w_conv, blk._fused.table(blk.conv2d_t.bias, blk.bn))
+    _check(x, w_conv, blk._fused.table(blk.conv2d_t.bias, blk.bn), y, "up1 64->128@50")
 
 
 @pytest.mark.gpu
