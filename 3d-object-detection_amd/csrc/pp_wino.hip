@@ -11,8 +11,16 @@
 // tiles [32*(w&1), +32) x channels [32*(w>>1), +32) for all 16 positions: one
 // v_mfma_f32_32x32x2_f32 accumulator per position (rows = tiles, columns = channels), so every
 // lane holds the 16 positions of the same (tile, channel) pairs and the output transform and
-// the epilogue run in registers.  Input channels stream through LDS in chunks of 8, double
-// buffered: the global loads of chunk c+1 are in flight during the MFMAs of chunk c.
+// the epilogue run in registers.
+//
+// Input channels stream through LDS in chunks of 8, three stages deep, one barrier per chunk.
+// While the MFMAs of chunk c run on one V/U buffer:
+//   - the raw 18x18-pixel input halo of chunk c+2 is in flight in registers (each pixel's 32 bytes
+//     loaded once, as two 16-byte pieces; pixels outside the image are not loaded, zeros take their
+//     place), and is written to one of two small halo buffers at the end of the chunk;
+//   - U of chunk c+1 goes from global memory straight into the other V/U buffer (LDS-DMA: the
+//     packed layout is the LDS image);
+//   - the halo of chunk c+1, in LDS since the previous chunk, is transformed into V of that buffer.
 
 #include <type_traits>
 
@@ -23,8 +31,6 @@ namespace pp {
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-// register-staged chunk (vectors, not arrays: a private array is promoted to LDS before unrolling)
-typedef float f32x32 __attribute__((ext_vector_type(32)));
 
 constexpr int kKc = 8;              // input channels per chunk
 constexpr int kTiles = 64;          // 2x2 tiles per workgroup (8x8)
@@ -33,8 +39,21 @@ constexpr int kCo = 64;             // output channels per workgroup
 constexpr int kVFloats = 16 * 2 * kTiles * 4;
 constexpr int kUFloats = 16 * 2 * kCo * 4;
 constexpr int kBufFloats = kVFloats + kUFloats;
+// one halo buffer: [2 half][18*18 pixel][4] floats, channel 4*half + j of the chunk at j.  The
+// halves lie kHaloHalf floats apart: 16 bytes off a multiple of 32, so that the patch reads of the
+// 8 tiles x 4 channel pairs of a tile row (8 bytes each, 32 bytes from tile to tile) fall on 64
+// different banks
+constexpr int kHaloW = 18;
+constexpr int kHaloPix = kHaloW * kHaloW;
+constexpr int kHaloHalf = kHaloPix * 4 + 20;
+constexpr int kHaloFloats = 2 * kHaloHalf;
+constexpr int kHaloPieces = 2 * kHaloPix;     // 16-byte pieces per chunk
+constexpr int kHaloPer = (kHaloPieces + 255) / 256;
 // s_waitcnt immediate (gfx9 encoding): vmcnt(0), expcnt and lgkmcnt left at their maxima
 constexpr int kWaitVm0 = 0x0F70;
+
+typedef const __attribute__((address_space(1))) void *gptr_t;
+typedef __attribute__((address_space(3))) void *lptr_t;
 
 }  // namespace
 
@@ -49,10 +68,12 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
                                                          float *__restrict__ y, int H, int W, int Cin,
                                                          int Cout, int64_t y_stride, int tiles_x,
                                                          int tiles_y) {
-  __shared__ __attribute__((aligned(16))) float lds[2 * kBufFloats];
+  // one array: two V/U buffers, then the two halo buffers
+  __shared__ __attribute__((aligned(16))) float lds[2 * kBufFloats + 2 * kHaloFloats];
+  float *const halo = lds + 2 * kBufFloats;
 
   const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int bx = blockIdx.x % tiles_x;
   const int rest = blockIdx.x / tiles_x;
   const int by = rest % tiles_y;
@@ -61,64 +82,80 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
   const int co0 = blockIdx.y * kCo;
   const int nchunks = Cin / kKc;
 
-  // ---- loaders: thread = (tile, channel pair) of the input patch; 8 float4 of U each
-  const int lp = tid & 3;           // channel pair: channels 2lp, 2lp+1 of the chunk
-  const int lt = tid >> 2;          // tile 0..63
-  const int iy0 = oy0 + 2 * (lt >> 3) - 1, ix0 = ox0 + 2 * (lt & 7) - 1;
-  const float *xb = x + (int64_t)b * H * W * Cin + 2 * lp;
-  // the 4x4 patch: pixel (iy0 + r, ix0 + c) at xpatch + (r*W + c)*Cin; outside the image it reads
-  // pixel 0 of the sample (always in bounds) and keeps zero
-  const int64_t xpatch = ((int64_t)iy0 * W + ix0) * Cin;
-  unsigned xin = 0;
+  // ---- halo loader: piece q = tid + 256*i is half (q&1) of halo pixel q>>1, image pixel
+  // (oy0 - 1 + pix/18, ox0 - 1 + pix%18).  hin: the pixel is inside the image
+  const float *xb = x + (int64_t)b * H * W * Cin;
+  int64_t hoff[kHaloPer];
+  int hdst[kHaloPer];
+  unsigned hin = 0, hown = 0;
 #pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int iy = iy0 + r, ix = ix0 + c;
-      if (iy >= 0 && iy < H && ix >= 0 && ix < W) xin |= 1u << (4 * r + c);
+  for (int i = 0; i < kHaloPer; ++i) {
+    const int q = tid + 256 * i;
+    const int pix = q >> 1, hf = q & 1;
+    const int iy = oy0 - 1 + pix / kHaloW, ix = ox0 - 1 + pix % kHaloW;
+    hoff[i] = ((int64_t)iy * W + ix) * Cin + 4 * hf;
+    hdst[i] = hf * kHaloHalf + pix * 4;
+    if (q < kHaloPieces) {
+      hown |= 1u << i;
+      if (iy >= 0 && iy < H && ix >= 0 && ix < W) hin |= 1u << i;
     }
-  const int64_t useg = (int64_t)2 * Cout * 4;   // floats per (pos, chunk)
-  const float *ub = u + (int64_t)co0 * 4;
-
-  f32x32 dr;   // 16 pixels x 2 channels
-  f32x32 ur;   // 8 float4 of U
-  auto load = [&](int chunk) {
+  }
+  auto hload = [&](int chunk, float4 (&hr)[kHaloPer]) {
     const float *xc = xb + chunk * kKc;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int64_t off = ((xin >> i) & 1) ? xpatch + (int64_t)((i >> 2) * W + (i & 3)) * Cin : 0;
-      const float2 v = *reinterpret_cast<const float2 *>(xc + off);
-      dr[2 * i] = v.x;   // zeroed in store(): a select here would wait for the load at once
-      dr[2 * i + 1] = v.y;
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int q = tid + 256 * i;      // float4 index in the chunk's 32 KiB of U
-      const int seg = q >> 6;           // pos*2 + half
-      const float4 v = *reinterpret_cast<const float4 *>(
-          ub + ((int64_t)(seg >> 1) * nchunks + chunk) * useg + (int64_t)(seg & 1) * Cout * 4 + (q & 63) * 4);
-      ur[4 * i] = v.x;
-      ur[4 * i + 1] = v.y;
-      ur[4 * i + 2] = v.z;
-      ur[4 * i + 3] = v.w;
+    for (int i = 0; i < kHaloPer; ++i) {
+      hr[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if ((hin >> i) & 1) hr[i] = *reinterpret_cast<const float4 *>(xc + hoff[i]);
     }
   };
-  auto store = [&](float *buf) {
-    // V = B^T d B, rows first.  B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]
+  auto hstore = [&](float *hb, const float4 (&hr)[kHaloPer]) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i)
-      if (!((xin >> i) & 1)) dr[2 * i] = dr[2 * i + 1] = 0.0f;
+    for (int i = 0; i < kHaloPer; ++i)
+      if ((hown >> i) & 1) *reinterpret_cast<float4 *>(hb + hdst[i]) = hr[i];
+  };
+
+  // ---- U: a chunk's 32 KiB are 32 pieces of 1 KiB in the order of the LDS image; wave w copies
+  // pieces w, w + 4, ... (lane l the l-th 16 bytes), global memory to LDS directly
+  const int64_t useg = (int64_t)2 * Cout * 4;   // floats per (pos, chunk)
+  const float *ub = u + (int64_t)co0 * 4 + lane * 4;
+  // issued as an asm statement: the compiler takes an LDS-DMA builtin for a store to any LDS address and
+  // drains vmcnt ahead of the chunk's first operand read.  Nothing counts these copies but the vmcnt(0)
+  // that step() issues itself before its barrier
+  auto uload = [&](int chunk, float *buf) {
+    const unsigned dst0 = (unsigned)(uintptr_t)(lptr_t)(buf + kVFloats) + wave * (kCo * 4 * 4);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int seg = wave + 4 * i;     // pos*2 + half
+      const float *src = ub + ((int64_t)(seg >> 1) * nchunks + chunk) * useg + (int64_t)(seg & 1) * Cout * 4;
+      const unsigned dst = __builtin_amdgcn_readfirstlane(dst0 + i * (4 * kCo * 4 * 4));
+      unsigned keep;
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                   : "=&s"(keep)
+                   : "v"(src), "s"(dst)
+                   : "memory");
+    }
+  };
+
+  // ---- transform: thread = (tile, channel pair) of the input patch, read from the halo buffer
+  const int lp = tid & 3;           // channel pair: channels 2lp, 2lp+1 of the chunk
+  const int lt = tid >> 2;          // tile 0..63
+  const int p_off = (lp >> 1) * kHaloHalf + (2 * (lt >> 3) * kHaloW + 2 * (lt & 7)) * 4 + 2 * (lp & 1);
+  const int v_off = (lp >> 1) * (kTiles * 4) + lt * 4 + 2 * (lp & 1);
+  auto transform = [&](const float *hb, float *buf) {
+    // V = B^T d B, rows first.  B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]
     float2 e[16];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const float2 d0 = make_float2(dr[2 * c], dr[2 * c + 1]), d1 = make_float2(dr[8 + 2 * c], dr[9 + 2 * c]),
-                   d2 = make_float2(dr[16 + 2 * c], dr[17 + 2 * c]), d3 = make_float2(dr[24 + 2 * c], dr[25 + 2 * c]);
+      const float2 d0 = *reinterpret_cast<const float2 *>(hb + p_off + (0 * kHaloW + c) * 4),
+                   d1 = *reinterpret_cast<const float2 *>(hb + p_off + (1 * kHaloW + c) * 4),
+                   d2 = *reinterpret_cast<const float2 *>(hb + p_off + (2 * kHaloW + c) * 4),
+                   d3 = *reinterpret_cast<const float2 *>(hb + p_off + (3 * kHaloW + c) * 4);
       e[c] = make_float2(d0.x - d2.x, d0.y - d2.y);
       e[4 + c] = make_float2(d1.x + d2.x, d1.y + d2.y);
       e[8 + c] = make_float2(d2.x - d1.x, d2.y - d1.y);
       e[12 + c] = make_float2(d1.x - d3.x, d1.y - d3.y);
     }
-    float *vb = buf + (lp >> 1) * (kTiles * 4) + lt * 4 + 2 * (lp & 1);
+    float *vb = buf + v_off;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float2 e0 = e[4 * r], e1 = e[4 * r + 1], e2 = e[4 * r + 2], e3 = e[4 * r + 3];
@@ -128,11 +165,6 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
       for (int c = 0; c < 4; ++c)
         *reinterpret_cast<float2 *>(vb + (4 * r + c) * (2 * kTiles * 4)) = v[c];
     }
-    float *us = buf + kVFloats;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-      *reinterpret_cast<float4 *>(us + (tid + 256 * i) * 4) =
-          make_float4(ur[4 * i], ur[4 * i + 1], ur[4 * i + 2], ur[4 * i + 3]);
   };
 
   // ---- MFMA role: wave = (tile half wt, channel half wc); lane operands A = V[pos][h][tile][s],
@@ -146,11 +178,15 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
   // in VGPRs until it starts, and they spill
   f32x16 acc[16];
 
-  // one chunk: the global loads of chunk+1 are issued, the MFMAs run on `cur`, then chunk+1 is
-  // transformed into `nxt`
-  auto step = [&](float *cur, float *nxt, int chunk, auto first) {
-    const bool more = chunk + 1 < nchunks;
-    if (more) load(chunk + 1);
+  // one chunk: the halo loads of chunk+2 and the U copy of chunk+1 are issued, the MFMAs run on
+  // `cur`, chunk+1's halo is transformed into `nxt`, then chunk+2's halo is written to LDS
+  auto step = [&](int chunk, auto first) {
+    float *cur = lds + (chunk & 1) * kBufFloats, *nxt = lds + ((chunk + 1) & 1) * kBufFloats;
+    const bool more = chunk + 1 < nchunks, more2 = chunk + 2 < nchunks;
+    float4 hr[kHaloPer];
+    if (more2) hload(chunk + 2, hr);
+    // `nxt` was last read in chunk-1, before the barrier that ended it
+    if (more) uload(chunk + 1, nxt);
     // operands of position p+1 are read while the MFMAs of p run
     float4 an = *reinterpret_cast<const float4 *>(cur + a_off);
     float4 bn = *reinterpret_cast<const float4 *>(cur + b_off);
@@ -169,18 +205,28 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
       acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc[p], 0, 0, 0);
       acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc[p], 0, 0, 0);
     }
-    // `nxt` was last read in chunk-1, before the barrier that ended it
-    if (more) store(nxt);
+    if (more) transform(halo + ((chunk + 1) & 1) * kHaloFloats, nxt);
+    // this halo buffer held chunk's own halo, last read by the transform of chunk-1's step
+    if (more2) hstore(halo + (chunk & 1) * kHaloFloats, hr);
+    __builtin_amdgcn_s_waitcnt(kWaitVm0);   // the U copy
     __syncthreads();
   };
 
-  load(0);
-  store(lds);
-  __syncthreads();
-  step(lds, lds + kBufFloats, 0, std::true_type{});
+  {
+    float4 h0[kHaloPer], h1[kHaloPer];
+    hload(0, h0);
+    if (nchunks > 1) hload(1, h1);
+    uload(0, lds);
+    hstore(halo, h0);
+    if (nchunks > 1) hstore(halo + kHaloFloats, h1);
+    __builtin_amdgcn_s_waitcnt(kWaitVm0);
+    __syncthreads();
+    transform(halo, lds);
+    __syncthreads();
+  }
+  step(0, std::true_type{});
 #pragma unroll 1
-  for (int chunk = 1; chunk < nchunks; ++chunk)
-    step(lds + (chunk & 1) * kBufFloats, lds + ((chunk + 1) & 1) * kBufFloats, chunk, std::false_type{});
+  for (int chunk = 1; chunk < nchunks; ++chunk) step(chunk, std::false_type{});
 
   // ---- output transform Y = A^T M A (A^T = [1 1 1 0; 0 1 -1 -1]) and the epilogue, per lane:
   // channel co0 + 32wc + l32, tiles 32wt + (r&3) + 8(r>>2) + 4h for accumulator register r
