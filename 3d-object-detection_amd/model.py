@@ -165,6 +165,48 @@ def _conv_f16(x, w16, table, cout, out=None, channel_offset=0):
     return _conv3x3_nhwc("pp_conv3x3_f16_nhwc_dev", x, w16, table, cout, out, channel_offset)
 
 
+def _convt_f16_filter(w_t):
+    """ConvTranspose weight [Cin,Cout,3,3] -> pp_convt3x3_f16_nhwc_dev's layout: ``_f16_filter``'s of the weight
+    with its first two axes exchanged, [Cout/64][Cin/16][9][2][64][8], tap 3*kh + kw of ``w_t``, not flipped."""
+    return _f16_filter(w_t.transpose(0, 1))
+
+
+def _convt_out_size(conv, n):
+    """ConvTranspose2d's output extent along an axis of ``n`` input pixels (kernel 3, padding 1, square)."""
+    return (n - 1) * conv.stride[0] + 1 + conv.output_padding[0]
+
+
+def _convt_f16_ok(module, conv, x, out):
+    """The fp16-operand transposed-conv kernel takes this layer: the module's ``half_mma_up`` flag; 3x3, padding 1,
+    no dilation, no groups, stride (2,2) or (4,4), equal output padding below the stride; a dense 16-byte aligned
+    channels-last input, Cin % 16 == 0, Cout % 64 == 0; ``out``, if given, channels-last f32, 16-byte aligned and of
+    the transposed conv's output extent."""
+    s, op = tuple(conv.stride), tuple(conv.output_padding)
+    if not (module.half_mma_up and tuple(conv.kernel_size) == (3, 3) and s in ((2, 2), (4, 4))
+            and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.groups == 1
+            and op[0] == op[1] and 0 <= op[0] < s[0]
+            and _is_nhwc(x) and x.data_ptr() % 16 == 0 and x.shape[1] == conv.in_channels
+            and conv.in_channels % 16 == 0 and conv.out_channels % 64 == 0):
+        return False
+    return out is None or (_is_nhwc(out) and out.dtype == torch.float32 and out.data_ptr() % 16 == 0
+                           and out.shape[0] == x.shape[0]
+                           and tuple(out.shape[2:]) == (_convt_out_size(conv, x.shape[2]),
+                                                        _convt_out_size(conv, x.shape[3])))
+
+
+def _convt_f16(x, w16, table, cout, stride, output_padding, out=None, channel_offset=0):
+    """pp_convt3x3_f16_nhwc_dev: ConvTranspose2d(3x3, padding 1, ``stride`` 2 or 4) + bias/ReLU/BatchNorm of ``x``
+    (NHWC) with fp16 operands (``w16`` from ``_convt_f16_filter``) and f32 accumulation, into a new channels-last
+    tensor or into channels [channel_offset, +cout) of the channels-last ``out``."""
+    B, C, H, W = x.shape
+    if out is None:
+        out = torch.empty((B, cout, (H - 1) * stride + 1 + output_padding, (W - 1) * stride + 1 + output_padding),
+                          dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    _call("pp_convt3x3_f16_nhwc_dev", x.device, _vp(x), B, H, W, C, _vp(w16), cout, int(stride), int(output_padding),
+          _vp(table), _vp(out), out.shape[1], int(channel_offset))
+    return out
+
+
 def _stem_filter(w):
     """Conv weight [Cout,Cin,3,3] -> [9][Cin][Cout], tap 3*kh + kw: pp_conv3x3_s2_pillars_nhwc_dev's layout."""
     co, ci = w.shape[:2]
@@ -221,7 +263,7 @@ class _FusedConv:
     def __init__(self):
         self._table_key = None
         self._table = None
-        self._packed = {}           # kind ("nhwc", "wino", "f16", "stem") -> (key, packed weight)
+        self._packed = {}           # kind ("nhwc", "wino", "f16", "convt_f16", "stem") -> (key, packed weight)
 
     def table(self, bias, bn):
         """[C,3] f32: conv bias, BatchNorm scale, BatchNorm shift."""
@@ -250,7 +292,9 @@ class _FusedConv:
     def __call__(self, module, conv, bn, x, out=None, channel_offset=0, transposed=False):
         """``bn(relu(conv(x)))`` into a new tensor, or into channels [channel_offset, +Cout) of ``out``: the fp16
         kernel if ``module.half_mma`` and the layer is eligible, else the Winograd kernel if ``module.winograd``
-        and the layer is eligible, else MIOpen's conv (``transposed``: ConvTranspose) and the epilogue kernel."""
+        and the layer is eligible, else (a strided ConvTranspose) the fp16 transposed-conv kernel if
+        ``module.half_mma_up`` and the layer is eligible, else MIOpen's conv (``transposed``: ConvTranspose) and
+        the epilogue kernel."""
         out_ok = out is None or (_is_nhwc(out) and out.dtype == torch.float32 and out.shape[0] == x.shape[0]
                                  and out.shape[2:] == x.shape[2:])
         if _f16_ok(module, conv, x, transposed) and out_ok and (out is None or out.data_ptr() % 16 == 0):
@@ -259,6 +303,10 @@ class _FusedConv:
         if _wino_ok(module, conv, x, transposed) and out_ok:
             u = self.packed("wino", conv.weight, _wino_filter, transposed)
             return _conv_wino(x, u, self.table(conv.bias, bn), conv.out_channels, out, channel_offset)
+        if transposed and _convt_f16_ok(module, conv, x, out):
+            w16 = self.packed("convt_f16", conv.weight, _convt_f16_filter)
+            return _convt_f16(x, w16, self.table(conv.bias, bn), conv.out_channels, conv.stride[0],
+                              conv.output_padding[0], out, channel_offset)
         w = self.packed("nhwc", conv.weight, _nhwc_weight) if _is_nhwc(x) else conv.weight
         if transposed:
             y = F.conv_transpose2d(x, w, None, conv.stride, conv.padding, conv.output_padding)
@@ -564,6 +612,9 @@ class PPUpBlock(nn.Module):
         self.fused_train = True
         self.winograd = True
         self.half_mma = False
+        #: opt-in "fp16-up" inference: a stride-2 or stride-4 block as one fused fp16-operand kernel
+        #: (csrc/pp_convt_f16.hip: transposed conv and epilogue in one pass, no MIOpen call, no zero fill)
+        self.half_mma_up = False
         self._fused = _FusedConv()
 
     def forward(self, x, out=None, channel_offset=0):
@@ -650,7 +701,7 @@ class PPDetectionHead(nn.Module):
 
 
 #: what PPModel.set_inference_precision takes
-INFERENCE_PRECISIONS = ("f32", "fp16")
+INFERENCE_PRECISIONS = ("f32", "fp16", "fp16-up")
 
 
 def check_inference_precision(precision):
@@ -677,11 +728,15 @@ class PPModel(nn.Module):
     def set_inference_precision(self, precision):
         """``"fp16"``: the backbone's stride-1 3x3 layers (down1-3, up1) multiply fp16-rounded operands and
         accumulate in f32 (csrc/pp_conv_f16.hip) in no-grad channels-last inference on the GPU; results move
-        at the 1e-4 level.  ``"f32"`` (the default): every path in f32.  Activations are f32 either way."""
+        at the 1e-4 level.  ``"fp16-up"``: those, and the two strided transposed convolutions (up2, up3) the same
+        way (csrc/pp_convt_f16.hip).  ``"f32"`` (the default): every path in f32.  Activations are f32 in every
+        mode."""
         check_inference_precision(precision)
         bb = self.backbone
         for m in (bb.down1, bb.down2, bb.down3, bb.up1):
-            m.half_mma = precision == "fp16"
+            m.half_mma = precision in ("fp16", "fp16-up")
+        for m in (bb.up2, bb.up3):
+            m.half_mma_up = precision == "fp16-up"
 
     def forward(self, x, inds):
         return self.forward_features(self.feature_net(x), inds)

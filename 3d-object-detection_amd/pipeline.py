@@ -19,8 +19,8 @@ class PillarPipeline:
     def __init__(self, vox_cfg: VoxelConfig, anchor_cfg: boxes.AnchorConfig = None,
                  feature_channels=64, num_classes=9, reg_dims=8, device=None, seed=0,
                  pos_thresh=0.6, with_targets=False, data_mean=None, precision="f32"):
-        """``precision``: ``PPModel.set_inference_precision`` ("f32", or "fp16" for fp16-operand MFMA in the
-        backbone's stride-1 layers at inference)."""
+        """``precision``: ``PPModel.set_inference_precision`` ("f32", "fp16" for fp16-operand MFMA in the
+        backbone's stride-1 layers at inference, or "fp16-up" for those and the two strided transposed convolutions)."""
         check_inference_precision(precision)      # before anything is built
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.vox_cfg = vox_cfg

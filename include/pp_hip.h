@@ -549,6 +549,43 @@ int pp_conv3x3_f16_nhwc_dev(pp_ctx_t *ctx, void *stream, const float *x_dev, int
                             int64_t y_channel_offset);
 
 /*
+ * A 3x3, padding-1 transposed convolution (ConvTranspose2d) of stride s in {2, 4} and output padding
+ * op in [0, s) of NHWC f32 x[batch][height][width][in_channels], with the same epilogue and the same
+ * arithmetic as pp_conv3x3_f16_nhwc_dev: the opt-in "fp16-up" inference mode.  With
+ * Ho = (height-1)*s + 1 + op, Wo = (width-1)*s + 1 + op and w_t the ConvTranspose2d weight
+ * [in_channels][out_channels][3][3]:
+ *   v[b,oy,ox,co] = sum over kh, kw in {0,1,2} with (oy+1-kh) % s == 0, iy = (oy+1-kh)/s in [0,height),
+ *                                  (ox+1-kw) % s == 0, ix = (ox+1-kw)/s in [0,width), and over ci
+ *                   of half(x[b,iy,ix,ci]) * half(w_t[ci,co,kh,kw])
+ *   y = max(v + bias_co, 0) * scale_co + shift_co,   params_dev [out_channels][3] f32
+ * Arithmetic, as for pp_conv3x3_f16_nhwc_dev: each x value is rounded once to IEEE binary16 by the
+ * kernel, round to nearest even (never pkrtz); w_f16_dev holds the weights already rounded that way;
+ * values beyond the fp16 range become +-inf and fp16 subnormals are kept by both conversions; products
+ * are accumulated in f32 on v_mfma_f32_32x32x16_f16; the epilogue runs in f32; the schedule is fixed
+ * (no split-K, no atomics): results are bit-identical from call to call.
+ * w_f16_dev is w_t as fp16 in the layout [out_channels/64][in_channels/16][9][2][64][8]:
+ * w_t[ci][co][kh][kw] at element
+ *   (((((co/64)*(in_channels/16) + ci/16)*9 + 3*kh + kw)*2 + (ci/8)%2)*64 + co%64)*8 + ci%8
+ * (the layout of pp_conv3x3_f16_nhwc_dev applied to w_t with its first two axes exchanged; the taps are
+ * not flipped).
+ * y_dev: channels [y_channel_offset, +out_channels) of rows of y_channels floats per pixel of
+ * [batch][Ho][Wo], every one written exactly once (no zero fill; other channels untouched), the pixels
+ * that no tap reaches included: there v = 0 and y = max(bias_co, 0) * scale_co + shift_co.
+ * Non-finite operands: the kernel forms the sum over a fixed 3x3 tap pattern per output phase and feeds
+ * fp16 zeros where the definition's iy or ix falls outside the image (the border, and the last row and
+ * column of blocks behind the output padding).  With finite fp16 weights that is the definition exactly.
+ * A weight that overflowed to +-inf in fp16 gives 0 * inf = NaN at those pixels, where the definition
+ * leaves the tap out; pp_conv3x3_f16_nhwc_dev pads with zeros the same way.  Finite weights are the
+ * caller's part of the opt-in.
+ * in_channels a multiple of 16, out_channels a multiple of 64, x, w and y 16-byte aligned,
+ * height*width*in_channels < 2^31.  One launch: no allocation, no synchronisation (graph-capturable).
+ */
+int pp_convt3x3_f16_nhwc_dev(pp_ctx_t *ctx, void *stream, const float *x_dev, int batch, int height,
+                             int width, int in_channels, const void *w_f16_dev, int out_channels,
+                             int stride, int output_padding, const float *params_dev, float *y_dev,
+                             int64_t y_channels, int64_t y_channel_offset);
+
+/*
  * The backbone's first layer straight from the pillars (inference): PPScatter (model/model.py:53-62)
  * -> 3x3, stride-2, padding-1 convolution -> the epilogue of pp_bias_relu_bn_nhwc_dev,
  *   y = max(conv(canvas) + bias_c, 0) * scale_c + shift_c,

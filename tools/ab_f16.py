@@ -1,7 +1,9 @@
 """Dev tool: A/B of the opt-in fp16-operand MFMA layers (``PPModel.set_inference_precision("fp16")``,
-csrc/pp_conv_f16.hip) against the f32 default at bench.py's headline shapes (500x500 canvas, B=4,
-the pipelined step), both legs in one process, alternating; the ``cls``/``reg`` difference of the two
-modes on the same input; then per-layer kernel times of the fp16 kernel and of the Winograd kernel.
+csrc/pp_conv_f16.hip, and ``"fp16-up"``, which adds csrc/pp_convt_f16.hip for up2 and up3) against the f32
+default at bench.py's headline shapes (500x500 canvas, B=4, the pipelined step), all legs in one process,
+alternating; the ``cls``/``reg`` difference of the modes on the same input; then per-layer kernel times of
+the fp16 kernel and of the Winograd kernel, and of the fp16 transposed-conv kernel against today's path
+(``conv_transpose2d`` + ``_epilogue`` into the slice), three alternating legs each.
 
 usage: ab_f16.py [rounds] [steps]      (default 3 x 50 steps each way)"""
 import json
@@ -37,13 +39,13 @@ def run(n):
         pipe.forward_pipelined(sets[k % 4])
 
 
-legs = {"fp16": [], "f32": []}
+legs = {"fp16-up": [], "fp16": [], "f32": []}
 for name in legs:
     pipe.model.set_inference_precision(name)
     run(20)                                  # warm-up: MIOpen's find, the filter packing
 torch.cuda.synchronize()
 for r in range(rounds):
-    for name in (("fp16", "f32") if r % 2 == 0 else ("f32", "fp16")):
+    for name in (("fp16-up", "fp16", "f32") if r % 2 == 0 else ("f32", "fp16", "fp16-up")):
         pipe.model.set_inference_precision(name)
         run(5)
         torch.cuda.synchronize()
@@ -56,19 +58,24 @@ res["speedup"] = res["f32"]["median"] / res["fp16"]["median"]
 # the bar: the slowest fp16 leg ahead of the fastest f32 leg by 10x the larger within-leg spread
 res["margin_ms"] = min(legs["f32"]) - max(legs["fp16"])
 res["margin_over_spread"] = res["margin_ms"] / max(res["fp16"]["spread"], res["f32"]["spread"], 1e-9)
+# "fp16-up" against "fp16", the same bar
+up = {"speedup": res["fp16"]["median"] / res["fp16-up"]["median"], "margin_ms": min(legs["fp16"]) - max(legs["fp16-up"])}
+up["margin_over_spread"] = up["margin_ms"] / max(res["fp16-up"]["spread"], res["fp16"]["spread"], 1e-9)
+res["fp16-up_vs_fp16"] = up
 print(json.dumps({"ab_f16": res}))
 
 # both modes on the same input
 out = {}
-for name in ("f32", "fp16"):
+for name in ("f32", "fp16", "fp16-up"):
     pipe.model.set_inference_precision(name)
     out[name] = tuple(t.clone() for t in pipe.forward(sets[0]))
 pipe.model.set_inference_precision("f32")
 torch.cuda.synchronize()
-print(json.dumps({"fp16_vs_f32": {
-    k: {"max_abs_diff": float((a - b).abs().max()), "max_abs_f32": float(b.abs().max()),
-        "rel": float((a - b).abs().max()) / float(b.abs().max()), "finite": bool(torch.isfinite(a).all())}
-    for k, a, b in zip(("cls", "reg"), out["fp16"], out["f32"])}}))
+for mode in ("fp16", "fp16-up"):
+    print(json.dumps({mode + "_vs_f32": {
+        k: {"max_abs_diff": float((a - b).abs().max()), "max_abs_f32": float(b.abs().max()),
+            "rel": float((a - b).abs().max()) / float(b.abs().max()), "finite": bool(torch.isfinite(a).all())}
+        for k, a, b in zip(("cls", "reg"), out[mode], out["f32"])}}))
 
 
 def timeit(fn, n=30):
@@ -100,3 +107,35 @@ for name, cin, cout, h, count in (("down1.k", 64, 64, 250, 3), ("down2.k", 128, 
                  "f16_xy_GBs": xy_bytes / t_h / 1e3, "f16_direct_TFs": df / t_h / 1e6,
                  "wino_direct_equiv_TFs": df / t_w / 1e6})
 print(json.dumps({"per_layer": rows}))
+
+# up2 and up3 at their headline shapes into their slice of the 384-channel output: the fp16 transposed-conv
+# kernel against today's path, three alternating legs, medians
+rows = []
+for name, cin, cout, h, s, op in (("up2", 128, 128, 125, 2, 1), ("up3", 256, 128, 63, 4, 1)):
+    x = torch.randn(B, cin, h, h, device=dev).contiguous(memory_format=torch.channels_last)
+    wt = torch.randn(cin, cout, 3, 3, device=dev) * 0.05
+    tab = torch.stack([torch.zeros(cout), torch.ones(cout), torch.zeros(cout)], 1).to(dev).contiguous()
+    ho = (h - 1) * s + 1 + op
+    out = torch.empty((B, 3 * cout, ho, ho), device=dev).contiguous(memory_format=torch.channels_last)
+    w16, wn = M._convt_f16_filter(wt), M._nhwc_weight(wt)
+    off = cout if name == "up2" else 2 * cout
+
+    def today():
+        y = torch.nn.functional.conv_transpose2d(x, wn, None, (s, s), (1, 1), (op, op))
+        M._epilogue(M._dense(y), tab, out, off)
+
+    t_new, t_old = [], []
+    with torch.no_grad():
+        for r in range(3):
+            for leg in ((0, 1) if r % 2 == 0 else (1, 0)):
+                if leg == 0:
+                    t_new.append(timeit(lambda: M._convt_f16(x, w16, tab, cout, s, op, out, off)))
+                else:
+                    t_old.append(timeit(today))
+    t_h, t_m = float(np.median(t_new)), float(np.median(t_old))
+    df = 2.0 * B * h * h * cin * cout * 9                # every input pixel meets each of the 9 taps once
+    y_bytes = 4.0 * B * ho * ho * cout                   # the slice, written once
+    rows.append({"layer": name, "f16_us": t_new, "today_us": t_old, "f16_median_us": t_h, "today_median_us": t_m,
+                 "speedup": t_m / t_h, "f16_TFs": df / t_h / 1e6, "f16_y_GBs": y_bytes / t_h / 1e3,
+                 "today_y_GBs": y_bytes / t_m / 1e3})
+print(json.dumps({"per_layer_up": rows}))
