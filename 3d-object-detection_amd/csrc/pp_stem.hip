@@ -9,21 +9,35 @@
 //                    the canvas).  The map is NOT cleared: a reader trusts an entry p only when
 //                    indices[b][p] names that very cell, so whatever the scratch held before --
 //                    an earlier call's map included -- cannot reach the output.
-//   k_stem_conv      one workgroup per 8x16 output pixels x 64 output channels: the tile's 17x33
-//                    map cells -> nine per-tap lists of (pillar, local output) pairs (an output
-//                    has at most one pair per tap, so a list holds at most 128 pairs: the lists
-//                    are sized for a fully occupied tile) -> per tap, blocks of 16 pairs: gather
-//                    the pairs' feature rows (L2 resident), multiply by W[tap] on
-//                    v_mfma_f32_16x16x4_f32, add the 16 result rows to the f32 accumulator tile in
-//                    LDS -> epilogue, one 16-byte store per thread and 4 channels.
+//   k_stem_conv      persistent: two workgroups per compute unit, shared among the Cout / 64 channel groups;
+//                    workgroup x walks the tiles x, x + gridDim.x, ... of 8x16 output pixels x 64 output
+//                    channels: a fixed walk, no state shared between workgroups or between calls.  With
+//                    Cin = 64 each wave first loads its 16 output columns of all nine taps of the filter
+//                    into registers (144 per lane, the MFMA's B layout) and keeps them for
+//                    the whole launch.  Per tile: the 17x33 map cells -> nine per-tap lists of (pillar,
+//                    local output) pairs (an output has at most one pair per tap, so a list holds at most
+//                    128 pairs: the lists are sized for a fully occupied tile) -> per tap, blocks of 16
+//                    pairs: the pairs' feature rows (gathered one block ahead, L2 resident) times W[tap]
+//                    on v_mfma_f32_16x16x4_f32, the 16 result rows added to the f32 accumulator tile in
+//                    LDS -> epilogue, one 16-byte store per thread and 4 channels, which also leaves the
+//                    accumulator zero for the next tile.  The next tile's map cells and their index checks
+//                    are loaded while the current tile is in its taps and its epilogue.
+//                    Tiles are numbered position-major with the sweeps interleaved (tile = position * B +
+//                    sweep).  Real sweeps are dense around the sensor, so the same few positions carry most
+//                    of the pairs in every sweep, and the kernel takes as long as the workgroup with the most
+//                    pairs: numbered this way the tiles one grid apart that a workgroup walks lie at
+//                    positions far apart instead of at one position of every sweep.
 //
 // Summation order.  Wave w owns output channels [16w, 16w+16) of the accumulator tile for ALL
 // outputs and walks the taps 0..8 in order, so an accumulator element is only ever touched by one
 // wave, tap after tap; inside a tap an output has at most one pair, and that pair's 16 sums over
 // Cin are one fixed MFMA chain whatever row of the block the pair sits in.  No floating-point
-// atomics.  The result does not depend on the order of the pillars along P, on the launch, or on
-// the scratch's previous contents.
+// atomics.  The result does not depend on the order of the pillars along P, on the launch (the grid, or
+// which workgroup walks which tile after which), or on the scratch's previous contents.
 #include "pp_common.h"
+
+#include <algorithm>
+#include <atomic>
 
 namespace pp {
 namespace {
@@ -72,153 +86,287 @@ __global__ __launch_bounds__(256) void k_stem_prepare(const float *__restrict__ 
     for (int q = 0; q < np; ++q) rp[(int64_t)q * C] = t[lane][q];
 }
 
-// CIN: the input channels at compile time (the reduction fully unrolled: every load of a block is
-// in flight before its first MFMA), or 0: cin_rt, any multiple of 8
+// CIN: the input channels at compile time (the wave's filter slice lives in registers for the whole launch and
+// the reduction is fully unrolled), or 0: cin_rt, any multiple of 8, the filter re-read per block (there `wr`
+// is a single unused element).
+//
+// Persistent: workgroup x of channel group blockIdx.y walks the tiles x, x + gridDim.x, ...  What a workgroup
+// carries from one tile to the next, and where each piece is reset:
+//   s_acc   all 128 x 64 elements are zero when a tile's taps start: zeroed once before the first tile, and
+//           every element is overwritten with zero by the epilogue pass that reads it (unconditionally, also
+//           for pixels past the image's edge)
+//   s_map   all 17 x 33 entries are written (pillar or -1) for every tile, before the barrier its lists wait on
+//   s_cnt   all nine counts are written for every tile; of the lists only entries below the count are read
 template <int CIN>
-__global__ __launch_bounds__(256) void k_stem_conv(const int *__restrict__ map,
+__global__ __launch_bounds__(256, 2) void k_stem_conv(const int *__restrict__ map,
                                                    const long long *__restrict__ idx,
                                                    const float *__restrict__ rows,
                                                    const float *__restrict__ w,
                                                    const float *__restrict__ params,
                                                    float *__restrict__ y, int P, int H, int W, int OH,
                                                    int OW, int cin_rt, int Cout, int tiles_x,
-                                                   int tiles_y) {
+                                                   int tiles_y, long long tiles) {
   __shared__ __attribute__((aligned(16))) float s_acc[kOut * kAcc];
   __shared__ int s_map[kMH * kMW];
   __shared__ int s_lp[9][kOut];            // per tap: the pairs' pillars ...
-  __shared__ unsigned char s_lo[9][kOut];  // ... and local outputs
+  __shared__ __attribute__((aligned(4))) unsigned char s_lo[9][kOut];  // ... and local outputs
   __shared__ int s_cnt[9];
   const int Cin = CIN ? CIN : cin_rt;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y;
-  const int b = blockIdx.x / (tiles_x * tiles_y);
-  const int oy0 = ty * kTH, ox0 = tx * kTW;
+  const int i16 = lane & 15, kq = lane >> 4;
+  const int batch = (int)(tiles / (tiles_x * tiles_y));
 
-  // the tile's cells: input rows 2*oy0-1 .. 2*oy0+15, columns 2*ox0-1 .. 2*ox0+31.  An entry counts
-  // only if the pillar it names is flagged and sits in this cell (the map is never cleared).
-  {
-    const int *mb = map + (int64_t)b * H * W;
-    const long long *ib = idx + (int64_t)b * P * 3;
-    for (int i = tid; i < kMH * kMW; i += 256) {
-      const int r = i / kMW, c = i - r * kMW;
-      const int iy = 2 * oy0 - 1 + r, ix = 2 * ox0 - 1 + c;
-      int p = -1;
-      if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
-        p = mb[(int64_t)iy * W + ix];
-        if (p >= 0 && p < P) {
-          const long long *io = ib + (int64_t)p * 3;
-          if (io[0] == 0 || io[1] != ix || io[2] != iy) p = -1;
-        } else {
-          p = -1;
-        }
+  // v_mfma_f32_16x16x4_f32: lane l holds A[row l&15][k l>>4] and B[k l>>4][column l&15]; the 8 input
+  // channels of step pair j are assigned k = 0..3 as channel 8j + 2k + e (e = 0, 1: one 8-byte load
+  // of the row per lane).  D: lane l, register r = row 4*(l>>4) + r, column l&15.
+  // wave `wave`: output channels [16*wave, +16) of this workgroup's 64; its B operands of all nine taps
+  const unsigned woff = (unsigned)(2 * kq * Cout + blockIdx.y * 64 + wave * 16 + i16);
+  float wr[CIN ? 9 : 1][CIN ? CIN / 8 : 1][2];
+  if constexpr (CIN != 0) {
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+      for (int j = 0; j < CIN / 8; ++j) {
+        wr[t][j][0] = (w + (int64_t)(t * CIN + 8 * j) * Cout)[woff];  // uniform base + one lane offset
+        wr[t][j][1] = (w + (int64_t)(t * CIN + 8 * j + 1) * Cout)[woff];
       }
-      s_map[i] = p;
+  }
+  // epilogue: thread = 4 channels of one pixel per pass; a pass covers one tile row (16 whole pixels)
+  const int ec4 = (tid & 15) * 4, eox = tid >> 4;
+  const int ecg = blockIdx.y * 64 + ec4;
+
+  // A tile's cells: input rows 2*oy0-1 .. 2*oy0+15, columns 2*ox0-1 .. 2*ox0+31, thread tid takes cells
+  // tid, tid + 256, tid + 512.  An entry counts only if the pillar it names is flagged and sits in this cell
+  // (the map is never cleared).  Three phases, so that the next tile's two dependent round trips run under
+  // the current tile's taps and epilogue: the map entries, the pillars' index rows, the verdict into s_map.
+  constexpr int kCells = (kMH * kMW + 255) / 256;
+  int mp[kCells];
+  long long mf[kCells], mc[kCells], mr[kCells];
+  // Tile number -> position and sweep, the sweeps interleaved (see the file's header).  Any numbering gives the
+  // same output.
+  auto place = [&](int64_t tile, int &b, int &oy0, int &ox0) {
+    const int pos = (int)(tile / batch);
+    b = (int)(tile - (int64_t)pos * batch);
+    oy0 = pos / tiles_x * kTH;
+    ox0 = pos % tiles_x * kTW;
+  };
+  auto map_fetch = [&](int64_t tile) {
+    int b, oy0, ox0;
+    place(tile, b, oy0, ox0);
+    const int *mb = map + (int64_t)b * H * W;
+#pragma unroll
+    for (int k = 0; k < kCells; ++k) {
+      const int i = tid + 256 * k, r = i / kMW, c = i - r * kMW;
+      const int iy = 2 * oy0 - 1 + r, ix = 2 * ox0 - 1 + c;
+      mp[k] = -1;
+      if (i < kMH * kMW && iy >= 0 && iy < H && ix >= 0 && ix < W) mp[k] = mb[(int64_t)iy * W + ix];
     }
+  };
+  auto idx_fetch = [&](int64_t tile) {
+    int b, oy0, ox0;
+    place(tile, b, oy0, ox0);
+    const long long *ib = idx + (int64_t)b * P * 3;
+#pragma unroll
+    for (int k = 0; k < kCells; ++k) {
+      mf[k] = 0;
+      mc[k] = 0;
+      mr[k] = 0;
+      if (mp[k] >= 0 && mp[k] < P) {
+        const long long *io = ib + (int64_t)mp[k] * 3;
+        mf[k] = io[0];
+        mc[k] = io[1];
+        mr[k] = io[2];
+      } else {
+        mp[k] = -1;
+      }
+    }
+  };
+  auto map_store = [&](int64_t tile) {
+    int b, oy0, ox0;
+    place(tile, b, oy0, ox0);
+#pragma unroll
+    for (int k = 0; k < kCells; ++k) {
+      const int i = tid + 256 * k, r = i / kMW, c = i - r * kMW;
+      const int iy = 2 * oy0 - 1 + r, ix = 2 * ox0 - 1 + c;
+      int p = mp[k];
+      if (p >= 0 && (mf[k] == 0 || mc[k] != ix || mr[k] != iy)) p = -1;
+      if (i < kMH * kMW) s_map[i] = p;
+    }
+  };
+
+  // the fixed walk blockIdx.x, blockIdx.x + gridDim.x, ...; the next tile's cells are loaded during the current one
+  int64_t tile = blockIdx.x;
+  if (tile >= tiles) return;  // whole workgroup
+  map_fetch(tile);
+  idx_fetch(tile);
+  map_store(tile);
+  {
     const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     for (int i = tid; i < kOut * kAcc / 4; i += 256) reinterpret_cast<float4 *>(s_acc)[i] = z;
   }
   __syncthreads();
 
-  // nine lists, in output order (ballot + prefix count): tap (ky,kx) pairs output (oy,ox) with
-  // cell (2*oy + ky - 1, 2*ox + kx - 1)
-  for (int t = wave; t < 9; t += 4) {
-    const int ky = t / 3, kx = t - 3 * ky;
-    int n = 0;
-#pragma unroll
-    for (int ch = 0; ch < kOut / 64; ++ch) {
-      const int o = ch * 64 + lane, oy = o / kTW, ox = o % kTW;
-      int p = -1;
-      if (oy0 + oy < OH && ox0 + ox < OW) p = s_map[(2 * oy + ky) * kMW + 2 * ox + kx];
-      const unsigned long long m = __ballot(p >= 0);
-      if (p >= 0) {
-        const int pos = n + __popcll(m & ((1ull << lane) - 1ull));
-        s_lp[t][pos] = p;
-        s_lo[t][pos] = (unsigned char)o;
-      }
-      n += __popcll(m);
-    }
-    if (lane == 0) s_cnt[t] = n;
-  }
-  __syncthreads();
+#pragma unroll 1
+  for (; tile < tiles; tile += gridDim.x) {
+    int b, oy0, ox0;
+    place(tile, b, oy0, ox0);
+    const int64_t next = tile + gridDim.x;
+    const bool more = next < tiles;
 
-  // wave `wave`: output channels [16*wave, +16) of this workgroup's 64, every tap in order.
-  // v_mfma_f32_16x16x4_f32: lane l holds A[row l&15][k l>>4] and B[k l>>4][column l&15]; the 8 input
-  // channels of step pair j are assigned k = 0..3 as channel 8j + 2k + e (e = 0, 1: one 8-byte load
-  // of the row per lane).  D: lane l, register r = row 4*(l>>4) + r, column l&15.
-  {
-    const int i16 = lane & 15, kq = lane >> 4;
-    const float *rb = rows + (int64_t)b * P * Cin + 2 * kq;
-    const float *wc = w + (int64_t)(2 * kq) * Cout + blockIdx.y * 64 + wave * 16 + i16;
-    float *acc = s_acc + wave * 16 + i16;
-#pragma unroll 1
-    for (int t = 0; t < 9; ++t) {
-      const int n = __builtin_amdgcn_readfirstlane(s_cnt[t]);
-      const float *wt = wc + (int64_t)t * Cin * Cout;
-#pragma unroll 1
-      for (int r0 = 0; r0 < n; r0 += 16) {
-        // rows past the list's end repeat its first pair; their results are dropped below
-        const int p = s_lp[t][r0 + i16 < n ? r0 + i16 : r0];
-        const float *ar = rb + (int64_t)p * Cin;
-        f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
-        if constexpr (CIN != 0) {
-          float2 a[CIN / 8];
-          float b0[CIN / 8], b1[CIN / 8];
+    // nine lists, in output order (ballot + prefix count): tap (ky,kx) pairs output (oy,ox) with
+    // cell (2*oy + ky - 1, 2*ox + kx - 1)
+    for (int t = wave; t < 9; t += 4) {
+      const int ky = t / 3, kx = t - 3 * ky;
+      int n = 0;
 #pragma unroll
-          for (int j = 0; j < CIN / 8; ++j) {
-            a[j] = *reinterpret_cast<const float2 *>(ar + 8 * j);
-            b0[j] = wt[(int64_t)(8 * j) * Cout];
-            b1[j] = wt[(int64_t)(8 * j + 1) * Cout];
-          }
+      for (int ch = 0; ch < kOut / 64; ++ch) {
+        const int o = ch * 64 + lane, oy = o / kTW, ox = o % kTW;
+        int p = -1;
+        if (oy0 + oy < OH && ox0 + ox < OW) p = s_map[(2 * oy + ky) * kMW + 2 * ox + kx];
+        const unsigned long long m = __ballot(p >= 0);
+        if (p >= 0) {
+          const int pos = n + __popcll(m & ((1ull << lane) - 1ull));
+          s_lp[t][pos] = p;
+          s_lo[t][pos] = (unsigned char)o;
+        }
+        n += __popcll(m);
+      }
+      if (lane == 0) s_cnt[t] = n;
+    }
+    if (more) map_fetch(next);
+    __syncthreads();
+
+    // every tap in order, blocks of 16 pairs; rows past a list's end repeat the block's first pair and
+    // their results are dropped
+    {
+      const float *rb = rows + (int64_t)b * P * Cin + 2 * kq;
+      float *acc = s_acc + wave * 16 + i16;
+      const int myc = lane < 9 ? s_cnt[lane] : 0;  // lane t: the length of tap t's list
+      if constexpr (CIN != 0) {
+        // The only global reads left are the row gathers.  `an` holds, or waits for, the rows of block
+        // (nt, nr): at a block's start that is the block itself.  The cursor then moves on to the block after
+        // it -- the same tap's next block or the first block of the next tap that has pairs -- and each 8-byte
+        // piece of that block's rows is requested into the registers of `an` as soon as the two MFMAs that
+        // read them have been issued, so a gather has one block's work to arrive in.  After the tile's last
+        // block the cursor stays where it is and the same rows are simply read again.
+        const unsigned ne = (unsigned)__ballot(myc > 0);
+        int nt = ne ? __builtin_ctz(ne) : 9, nr = 0;
+        float2 an[CIN / 8];
+        auto block_rows = [&]() -> const float * {
+          const int cn = __builtin_amdgcn_readlane(myc, nt);
+          const int p = s_lp[nt][nr + i16 < cn ? nr + i16 : nr];
+          return rb + (int64_t)p * CIN;
+        };
+        if (nt < 9) {
+          const float *ar = block_rows();
 #pragma unroll
-          for (int j = 0; j < CIN / 8; ++j) {
-            c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j].x, b0[j], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j].y, b1[j], c, 0, 0, 0);
-          }
-        } else {
-          for (int j = 0; j < Cin / 8; ++j) {
-            const float2 a = *reinterpret_cast<const float2 *>(ar + 8 * j);
-            const float b0 = wt[(int64_t)(8 * j) * Cout], b1 = wt[(int64_t)(8 * j + 1) * Cout];
-            c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b0, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b1, c, 0, 0, 0);
-          }
+          for (int j = 0; j < CIN / 8; ++j) an[j] = *reinterpret_cast<const float2 *>(ar + 8 * j);
         }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int q = r0 + 4 * kq + r;
-          if (q < n) acc[(int)s_lo[t][q] * kAcc] += c[r];
+        for (int t = 0; t < 9; ++t) {
+          const int n = __builtin_amdgcn_readlane(myc, t);
+#pragma unroll 1
+          for (int r0 = 0; r0 < n; r0 += 16) {
+            if (nr + 16 < n) {
+              nr += 16;
+            } else if (ne >> (t + 1)) {
+              nt = t + 1 + __builtin_ctz(ne >> (t + 1));
+              nr = 0;
+            }
+            const float *ar = block_rows();
+            // the block's four result rows of this lane: outputs and their sums so far
+            const unsigned lo4 = *reinterpret_cast<const unsigned *>(&s_lo[t][r0 + 4 * kq]);
+            float *ap[4], old[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              ap[r] = acc + (int)((lo4 >> (8 * r)) & (kOut - 1)) * kAcc;  // masked: bytes past the list's end
+              old[r] = *ap[r];
+            }
+            __builtin_amdgcn_sched_barrier(0);  // the next block's address is known before the first MFMA
+            f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int j = 0; j < CIN / 8; ++j) {
+              c = __builtin_amdgcn_mfma_f32_16x16x4f32(an[j].x, wr[t][j][0], c, 0, 0, 0);
+              c = __builtin_amdgcn_mfma_f32_16x16x4f32(an[j].y, wr[t][j][1], c, 0, 0, 0);
+              an[j] = *reinterpret_cast<const float2 *>(ar + 8 * j);
+              __builtin_amdgcn_sched_barrier(0);  // keep each request right behind its two MFMAs
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (r0 + 4 * kq + r < n) *ap[r] = old[r] + c[r];
+            // another lane of this wave may own the same accumulator element in the next tap
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+          }
         }
-        // another lane of this wave may own the same accumulator element in the next tap
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+      } else {
+#pragma unroll 1
+        for (int t = 0; t < 9; ++t) {
+          const int n = __builtin_amdgcn_readlane(myc, t);
+          const float *wt = w + woff + (int64_t)t * Cin * Cout;
+#pragma unroll 1
+          for (int r0 = 0; r0 < n; r0 += 16) {
+            const int p = s_lp[t][r0 + i16 < n ? r0 + i16 : r0];
+            const float *ar = rb + (int64_t)p * Cin;
+            f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
+            for (int j = 0; j < Cin / 8; ++j) {
+              const float2 a = *reinterpret_cast<const float2 *>(ar + 8 * j);
+              const float b0 = wt[(int64_t)(8 * j) * Cout], b1 = wt[(int64_t)(8 * j + 1) * Cout];
+              c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b0, c, 0, 0, 0);
+              c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b1, c, 0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int q = r0 + 4 * kq + r;
+              if (q < n) acc[(int)s_lo[t][q] * kAcc] += c[r];
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+          }
+        }
       }
     }
-  }
-  __syncthreads();
+    if (more) idx_fetch(next);
+    __syncthreads();
 
-  // epilogue: thread = 4 channels of one pixel per pass; a pass writes one tile row (16 whole pixels)
-  {
-    const int c4 = (tid & 15) * 4, ox = tid >> 4;
-    const int cg = blockIdx.y * 64 + c4;
-    float eb[4], es[4], et[4];
+    // epilogue; the pass that reads an accumulator element leaves it zero for the next tile
+    {
+      float eb[4], es[4], et[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      eb[e] = params[(cg + e) * 3];
-      es[e] = params[(cg + e) * 3 + 1];
-      et[e] = params[(cg + e) * 3 + 2];
-    }
-    if (ox0 + ox < OW) {
+      for (int e = 0; e < 4; ++e) {
+        eb[e] = params[(ecg + e) * 3];
+        es[e] = params[(ecg + e) * 3 + 1];
+        et[e] = params[(ecg + e) * 3 + 2];
+      }
+      const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 #pragma unroll
       for (int oy = 0; oy < kTH; ++oy) {
-        if (oy0 + oy >= OH) continue;
-        float4 v = *reinterpret_cast<const float4 *>(s_acc + (oy * kTW + ox) * kAcc + c4);
+        float4 *ap = reinterpret_cast<float4 *>(s_acc + (oy * kTW + eox) * kAcc + ec4);
+        float4 v = *ap;
+        *ap = z;
+        if (ox0 + eox >= OW || oy0 + oy >= OH) continue;
         v.x = fmaxf(v.x + eb[0], 0.0f) * es[0] + et[0];
         v.y = fmaxf(v.y + eb[1], 0.0f) * es[1] + et[1];
         v.z = fmaxf(v.z + eb[2], 0.0f) * es[2] + et[2];
         v.w = fmaxf(v.w + eb[3], 0.0f) * es[3] + et[3];
-        *reinterpret_cast<float4 *>(y + (((int64_t)b * OH + oy0 + oy) * OW + ox0 + ox) * Cout + cg) = v;
+        *reinterpret_cast<float4 *>(y + (((int64_t)b * OH + oy0 + oy) * OW + ox0 + eox) * Cout + ecg) = v;
       }
     }
+    if (more) map_store(next);
+    __syncthreads();
   }
+}
+
+// the device's compute units, asked once per device
+int compute_units(int device) {
+  static std::atomic<int> cached[64];
+  const bool slot = device >= 0 && device < 64;
+  int n = slot ? cached[device].load(std::memory_order_relaxed) : 0;
+  if (n <= 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n <= 0) n = 256;
+    if (slot) cached[device].store(n, std::memory_order_relaxed);
+  }
+  return n;
 }
 
 }  // namespace
@@ -267,20 +415,24 @@ extern "C" int pp_conv3x3_s2_pillars_nhwc_dev(pp_ctx_t *ctx, void *stream_, cons
   (void)hipGetDevice(&prev);
   if (prev != ctx->device) (void)hipSetDevice(ctx->device);
   hipStream_t st = static_cast<hipStream_t>(stream_);
+  // persistent: two workgroups per compute unit (what the <64> instance's registers allow), shared among the
+  // channel groups (never more than there are tiles)
+  const int groups = out_channels / 64;
+  const int64_t resident = std::max<int64_t>(1, (int64_t)2 * compute_units(ctx->device) / groups);
+  const dim3 grid((unsigned)std::min(blocks, resident), (unsigned)groups);
   const dim3 pgrid((unsigned)((max_pillars + 255) / 256), (unsigned)((in_channels + 63) / 64), (unsigned)batch);
   hipLaunchKernelGGL(k_stem_prepare, pgrid, dim3(256), 0, st, features_dev, idx, map, rows, in_channels,
                      max_pillars, canvas_h, canvas_w);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) {
-    const dim3 grid((unsigned)blocks, (unsigned)(out_channels / 64));
     if (in_channels == 64)
       hipLaunchKernelGGL(k_stem_conv<64>, grid, dim3(256), 0, st, map, idx, rows, w_taps_dev, params_dev, y_dev,
                          max_pillars, canvas_h, canvas_w, oh, ow, in_channels, out_channels, (int)tiles_x,
-                         (int)tiles_y);
+                         (int)tiles_y, (long long)blocks);
     else
       hipLaunchKernelGGL(k_stem_conv<0>, grid, dim3(256), 0, st, map, idx, rows, w_taps_dev, params_dev, y_dev,
                          max_pillars, canvas_h, canvas_w, oh, ow, in_channels, out_channels, (int)tiles_x,
-                         (int)tiles_y);
+                         (int)tiles_y, (long long)blocks);
     e = hipGetLastError();
   }
   if (prev >= 0 && prev != ctx->device) (void)hipSetDevice(prev);
