@@ -27,6 +27,23 @@ void set_error(const char *fmt, ...);
     }                                                                           \
   } while (0)
 
+// Makes `dev` the calling thread's HIP device for a scope; restores the previous one only if it switched.
+struct DeviceGuard {
+  int prev = -1;
+  bool switched = false;
+  explicit DeviceGuard(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) {
+      (void)hipGetLastError();
+    } else if (prev != dev) {
+      (void)hipSetDevice(dev);
+      switched = true;
+    }
+  }
+  ~DeviceGuard() {
+    if (switched) (void)hipSetDevice(prev);
+  }
+};
+
 // A grow-only device buffer.
 struct DevBuf {
   void *ptr = nullptr;

@@ -15,9 +15,9 @@
 // (those pixels are the per-channel constant max(b,0)*s+t).  A workgroup owns a tile of blocks -- the
 // input pixels of the same coordinates plus, at stride 2, a one-pixel halo on the low side -- and all
 // S*S phases of them: the same nine tap-MFMAs per 16 input channels as a stride-1 layer, accumulated
-// into 4 (stride 2) or 9 (stride 4) accumulators, and pp_conv_f16.hip's LDS image: fp16, two planes of
-// 8 channels, 16 bytes per pixel, one ds_read_b128 per A fragment, taps as constant address offsets,
-// Cin streamed in chunks of 16 through two buffers.  Blocks run to j = Ho/S inclusive: the last one may
+// into 4 (stride 2) or 9 (stride 4) accumulators, on the LDS image and chunk pipeline it shares with
+// that kernel (pp_conv_f16_tile.h): fp16, two planes of 8 channels, 16 bytes per pixel, one ds_read_b128 per A
+// fragment, taps as constant address offsets, Cin streamed in chunks of 16 through two buffers.  Blocks run to j = Ho/S inclusive: the last one may
 // have no input pixel (it reads zeros), which is how the output-padding rows and columns are written.
 //
 // Workgroup: 256 threads, 64 output channels.  One MFMA row block is 32 consecutive blocks of one row.
@@ -28,38 +28,17 @@
 // The schedule is fixed (no split-K, no atomics): channel chunks in order, taps in order within a chunk,
 // so results are bit-identical from call to call.
 
-#include "pp_common.h"
+#include "pp_conv_f16_tile.h"
 
 namespace pp {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-// register-staged weights (a vector, not an array: a private array is promoted to LDS before unrolling)
-typedef unsigned u32x20 __attribute__((ext_vector_type(20)));
-
-constexpr int kKc = 16;                      // input channels per chunk
-constexpr int kTw = 32;                      // blocks per tile row
-constexpr int kCo = 64;                      // output channels per workgroup
-constexpr int kBVecs = 9 * 2 * kCo;          // 16-byte vectors of weights per chunk (1152)
-// s_waitcnt immediate (gfx9 encoding): vmcnt(0), expcnt and lgkmcnt left at their maxima
-constexpr int kWaitVm0 = 0x0F70;
-
+// blocks per workgroup: 32 x 4 with a one-pixel halo on the low side (165 pixels), or 32 x 2 with none (64)
 template <int S>
-struct Geo {
-  static constexpr int kHl = S == 2 ? 1 : 0;         // halo pixels on the low side
-  static constexpr int kRows = S == 2 ? 4 : 2;       // block rows per workgroup
+struct Geo : TileGeo<S == 2 ? 4 : 2, S == 2 ? 1 : 0, 0> {
   static constexpr int kNcb = S == 2 ? 2 : 1;        // column blocks of 32 channels per wave
   static constexpr int kNp = S == 2 ? 2 : 3;         // phases per axis that receive a tap
-  static constexpr int kHw = kTw + kHl;              // halo tile width
-  static constexpr int kHalo = kHw * (kRows + kHl);  // halo pixels (165 / 64)
-  // one LDS buffer (bytes): A[2 half][halo pixel][8 fp16] then B[9 tap][2 half][64 cout][8 fp16]
-  static constexpr int kAPlane = kHalo * 16;
-  static constexpr int kABytes = 2 * kAPlane;
-  static constexpr int kBufBytes = kABytes + kBVecs * 16;
-  static constexpr int kItems = 2 * kHalo;           // (pixel, half) pairs of the halo tile
-  static constexpr int kNItem = (kItems + 255) / 256;
 };
 
 }  // namespace
@@ -79,74 +58,13 @@ __global__ __launch_bounds__(256, 2) void k_convt3x3_f16(const float *__restrict
   using G = Geo<S>;
   __shared__ __attribute__((aligned(16))) unsigned char lds[2 * G::kBufBytes];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int bx = blockIdx.x % tiles_x;
-  const int rest = blockIdx.x / tiles_x;
-  const int by = rest % tiles_y;
-  const int b = rest / tiles_y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int bx, by, b;
+  tile_of_block(tiles_x, tiles_y, bx, by, b);
   const int jy0 = by * G::kRows, jx0 = bx * kTw;
   const int co0 = blockIdx.y * kCo;
   const int nchunks = Cin / kKc;
-
-  // ---- loaders: item i = tid + 256k is (halo pixel i>>1, half i&1): 8 channels = two float4.
-  // Outside the image it reads pixel 0 of the sample (always in bounds) and keeps zero; the load is not
-  // predicated on that (see pp_conv_f16.hip).
-  const float *xb = x + (int64_t)b * H * W * Cin;
-  int xoff[G::kNItem], adst[G::kNItem];
-  bool xin[G::kNItem], has[G::kNItem];
-#pragma unroll
-  for (int k = 0; k < G::kNItem; ++k) {
-    const int i = tid + 256 * k;
-    const int pix = i >> 1, hh = i & 1;
-    const int hy = pix / G::kHw, hx = pix - hy * G::kHw;
-    const int iy = jy0 - G::kHl + hy, ix = jx0 - G::kHl + hx;
-    has[k] = i < G::kItems;
-    xin[k] = has[k] && iy >= 0 && iy < H && ix >= 0 && ix < W;
-    xoff[k] = (xin[k] ? (iy * W + ix) * Cin : 0) + 8 * hh;
-    adst[k] = hh * G::kAPlane + pix * 16;
-  }
-  const bool wvec4 = tid + 1024 < kBVecs;     // the fifth weight vector for 128 threads
-  const uint4 *wb = w + (int64_t)blockIdx.y * nchunks * kBVecs;
-
-  float4 xr[G::kNItem][2];
-  u32x20 wr;
-  auto load = [&](int chunk) {
-    const float *xc = xb + chunk * kKc;
-#pragma unroll
-    for (int k = 0; k < G::kNItem; ++k)
-      if (has[k]) {
-        xr[k][0] = *reinterpret_cast<const float4 *>(xc + xoff[k]);
-        xr[k][1] = *reinterpret_cast<const float4 *>(xc + xoff[k] + 4);
-      }
-    const uint4 *wc = wb + (int64_t)chunk * kBVecs;
-#pragma unroll
-    for (int i = 0; i < 5; ++i)
-      if (i < 4 || wvec4) {
-        const uint4 v = wc[tid + 256 * i];
-        wr[4 * i] = v.x;
-        wr[4 * i + 1] = v.y;
-        wr[4 * i + 2] = v.z;
-        wr[4 * i + 3] = v.w;
-      }
-  };
-  auto store = [&](unsigned char *buf) {
-#pragma unroll
-    for (int k = 0; k < G::kNItem; ++k)
-      if (has[k]) {
-        const float4 lo = xr[k][0], hi = xr[k][1];
-        // f32 -> f16 casts: v_cvt_f16_f32, round to nearest even, +-inf beyond the range
-        f16x8 v = {(_Float16)lo.x, (_Float16)lo.y, (_Float16)lo.z, (_Float16)lo.w,
-                   (_Float16)hi.x, (_Float16)hi.y, (_Float16)hi.z, (_Float16)hi.w};
-        if (!xin[k]) v = f16x8{};
-        *reinterpret_cast<f16x8 *>(buf + adst[k]) = v;
-      }
-#pragma unroll
-    for (int i = 0; i < 5; ++i)
-      if (i < 4 || wvec4)
-        *reinterpret_cast<uint4 *>(buf + G::kABytes + (tid + 256 * i) * 16) =
-            make_uint4(wr[4 * i], wr[4 * i + 1], wr[4 * i + 2], wr[4 * i + 3]);
-  };
+  Stager<G> stage(x, w, b, H, W, Cin, jy0 - G::kHl, jx0 - G::kHl, nchunks);
 
   // ---- MFMA role: lane (r = lane&31, h = lane>>5) holds A[block r of the row][channels 8h..8h+7]
   // and B[channels 8h..8h+7][cout r of the wave's column block(s)]
@@ -181,34 +99,12 @@ __global__ __launch_bounds__(256, 2) void k_convt3x3_f16(const float *__restrict
       }
   };
 
-  load(0);
-  store(lds);
-  __syncthreads();
-  // the pipeline of pp_conv_f16.hip: the global loads of chunk+1 are in flight during the MFMAs of
-  // chunk; the last chunk is peeled
-#pragma unroll 1
-  for (int chunk = 0; chunk + 1 < nchunks; ++chunk) {
-    load(chunk + 1);
-    __builtin_amdgcn_sched_barrier(0);
-    mfmas(lds + (chunk & 1) * G::kBufBytes);
-    __builtin_amdgcn_sched_barrier(0);
-    store(lds + ((chunk + 1) & 1) * G::kBufBytes);
-    __syncthreads();
-  }
-  mfmas(lds + ((nchunks - 1) & 1) * G::kBufBytes);
+  chunk_pipeline(stage, lds, nchunks, mfmas);
 
   // ---- epilogue, per lane: channels co + 32n, blocks jx0 + (r&3) + 8(r>>2) + 4h of row jy0 + row for
   // accumulator register r; every phase of a block is stored, the tapless ones from v = 0
   const int co = co0 + cb0 * 32 + l32;
-  float eb[G::kNcb], es[G::kNcb], et[G::kNcb];
-#pragma unroll
-  for (int n = 0; n < G::kNcb; ++n) {
-    eb[n] = prm[(co + 32 * n) * 3 + 0];
-    es[n] = prm[(co + 32 * n) * 3 + 1];
-    et[n] = prm[(co + 32 * n) * 3 + 2];
-  }
-  // wait for the constants here, once (see pp_conv_f16.hip)
-  __builtin_amdgcn_s_waitcnt(kWaitVm0);
+  const Epilogue<G::kNcb> ep(prm, co);
   const int jy = jy0 + row;
 #pragma unroll
   for (int py = 0; py < S; ++py) {
@@ -225,10 +121,7 @@ __global__ __launch_bounds__(256, 2) void k_convt3x3_f16(const float *__restrict
         if (ox >= 0 && ox < Wo) {
           float *yp = yrow + (int64_t)ox * y_stride;
 #pragma unroll
-          for (int n = 0; n < G::kNcb; ++n) {
-            const float v = live ? acc[p][n][r] : 0.0f;
-            yp[32 * n] = fmaxf(v + eb[n], 0.0f) * es[n] + et[n];
-          }
+          for (int n = 0; n < G::kNcb; ++n) yp[32 * n] = ep.apply(live ? acc[p][n][r] : 0.0f, n);
         }
       }
     }
@@ -244,20 +137,13 @@ extern "C" int pp_convt3x3_f16_nhwc_dev(pp_ctx_t *ctx, void *stream_, const floa
                                         int out_channels, int stride, int output_padding,
                                         const float *params_dev, float *y_dev, int64_t y_channels,
                                         int64_t y_channel_offset) {
-  if (!ctx || !x_dev || !w_f16_dev || !params_dev || !y_dev) {
-    set_error("pp_convt3x3_f16_nhwc_dev: NULL argument");
-    return PP_ERR_VALUE;
-  }
-  if (batch < 1 || height < 1 || width < 1 || in_channels < 16 || in_channels % 16 || out_channels < 64 ||
-      out_channels % 64 || out_channels / 64 > 65535 || (stride != 2 && stride != 4) || output_padding < 0 ||
-      output_padding >= stride || y_channel_offset < 0 || y_channel_offset + out_channels > y_channels ||
-      ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(w_f16_dev) |
-        reinterpret_cast<uintptr_t>(y_dev)) & 15)) {
-    set_error("pp_convt3x3_f16_nhwc_dev: need in_channels a multiple of 16, out_channels a multiple of 64, "
-              "stride 2 or 4, 0 <= output_padding < stride, the slice inside y, 16-byte aligned x, w and y "
-              "(batch=%d %dx%d in=%d out=%d stride=%d output_padding=%d y_channels=%lld offset=%lld)", batch,
-              height, width, in_channels, out_channels, stride, output_padding, (long long)y_channels,
-              (long long)y_channel_offset);
+  const char *fn = "pp_convt3x3_f16_nhwc_dev";
+  if (int rc = check_conv_f16_args(fn, ctx, x_dev, w_f16_dev, params_dev, y_dev, batch, height, width, in_channels,
+                                   out_channels, y_channels, y_channel_offset))
+    return rc;
+  if ((stride != 2 && stride != 4) || output_padding < 0 || output_padding >= stride) {
+    set_error("%s: need stride 2 or 4, 0 <= output_padding < stride (stride=%d output_padding=%d)", fn, stride,
+              output_padding);
     return PP_ERR_VALUE;
   }
   const int64_t ho = ((int64_t)height - 1) * stride + 1 + output_padding;
@@ -265,31 +151,18 @@ extern "C" int pp_convt3x3_f16_nhwc_dev(pp_ctx_t *ctx, void *stream_, const floa
   const int rows = stride == 2 ? Geo<2>::kRows : Geo<4>::kRows;
   const int64_t tiles_x = (wo / stride + 1 + kTw - 1) / kTw, tiles_y = (ho / stride + 1 + rows - 1) / rows;
   const int64_t blocks = (int64_t)batch * tiles_x * tiles_y;
-  // the kernel indexes one sample of x with 32-bit offsets, output rows and columns with int
-  if (blocks > 0x7fffffff || (int64_t)height * width * in_channels > 0x7fffffff || ho > 0x3fffffff ||
-      wo > 0x3fffffff || (int64_t)batch * height * width * in_channels > ((int64_t)1 << 40) ||
+  // the kernel indexes output rows and columns with int
+  if (blocks > 0x7fffffff || ho > 0x3fffffff || wo > 0x3fffffff ||
+      (int64_t)batch * height * width * in_channels > ((int64_t)1 << 40) ||
       (double)batch * (double)ho * (double)wo * (double)y_channels > (double)((int64_t)1 << 40)) {
-    set_error("pp_convt3x3_f16_nhwc_dev: tensor too large");
+    set_error("%s: tensor too large", fn);
     return PP_ERR_VALUE;
   }
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != ctx->device) (void)hipSetDevice(ctx->device);
-  const dim3 grid((unsigned)blocks, (unsigned)(out_channels / 64));
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const uint4 *wv = static_cast<const uint4 *>(w_f16_dev);
-  float *ys = y_dev + y_channel_offset;
-  if (stride == 2)
-    hipLaunchKernelGGL(k_convt3x3_f16<2>, grid, dim3(256), 0, stream, x_dev, wv, params_dev, ys, height, width,
-                       in_channels, (int)ho, (int)wo, y_channels, (int)tiles_x, (int)tiles_y);
-  else
-    hipLaunchKernelGGL(k_convt3x3_f16<4>, grid, dim3(256), 0, stream, x_dev, wv, params_dev, ys, height, width,
-                       in_channels, (int)ho, (int)wo, y_channels, (int)tiles_x, (int)tiles_y);
-  hipError_t e = hipGetLastError();
-  if (prev >= 0 && prev != ctx->device) (void)hipSetDevice(prev);
-  if (e != hipSuccess) {
-    set_error("k_convt3x3_f16 launch failed: %s", hipGetErrorString(e));
-    return PP_ERR_HIP;
-  }
-  return PP_OK;
+  return launch_on_device(ctx, "k_convt3x3_f16", [&] {
+    const auto kernel = stride == 2 ? k_convt3x3_f16<2> : k_convt3x3_f16<4>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks, (unsigned)(out_channels / 64)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream_), x_dev, static_cast<const uint4 *>(w_f16_dev), params_dev,
+                       y_dev + y_channel_offset, height, width, in_channels, (int)ho, (int)wo, y_channels,
+                       (int)tiles_x, (int)tiles_y);
+  });
 }

@@ -1983,24 +1983,6 @@ __global__ void k_targets_gt_init(u64 *best, unsigned *bestj, int64_t n, unsigne
   if (k < PP_MAX_BATCH) pos_count[k * kCounterStride] = 0u;
 }
 
-namespace {
-struct DeviceGuard2 {
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard2(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess) {
-      ok = true;
-      if (prev != dev) (void)hipSetDevice(dev);
-    } else {
-      (void)hipGetLastError();
-    }
-  }
-  ~DeviceGuard2() {
-    if (ok) (void)hipSetDevice(prev);
-  }
-};
-}  // namespace
-
 }  // namespace pp
 
 using namespace pp;
@@ -2011,7 +1993,7 @@ static int launch_make_ious(pp_ctx_t *ctx, hipStream_t stream, const double *a_c
                             int64_t a_center_cols, int64_t A, const double *g_corners_dev, const double *g_centers_dev,
                             int64_t g_center_cols, int64_t G, double *ious_dev, IouTriple *triples,
                             unsigned *triple_count, unsigned triple_cap) {
-  DeviceGuard2 guard(ctx->device);
+  DeviceGuard guard(ctx->device);
   int rc = ctx->iou_ws.ensure(4096);
   if (rc) return rc;
   int *errflag = static_cast<int *>(ctx->iou_ws.ptr);
@@ -2084,7 +2066,7 @@ static int iou_flag_result(pp_ctx_t *ctx, int flag);
 // error flag of the last IoU / target launch on this context (synchronises)
 extern "C" int pp_iou_check(pp_ctx_t *ctx, void *stream_) {
   if (!ctx || !ctx->iou_ws.ptr) return PP_OK;
-  DeviceGuard2 guard(ctx->device);
+  DeviceGuard guard(ctx->device);
   int flag = 0;
   PP_HIP_TRY(hipMemcpyAsync(&flag, ctx->iou_ws.ptr, 4, hipMemcpyDeviceToHost,
                             static_cast<hipStream_t>(stream_)));
@@ -2129,7 +2111,7 @@ extern "C" int pp_make_ious_f64(pp_ctx_t *ctx, const void *a_corners, int64_t A,
     set_error("pp_make_ious_f64: NULL array");
     return PP_ERR_VALUE;
   }
-  DeviceGuard2 guard(ctx->device);
+  DeviceGuard guard(ctx->device);
   hipStream_t stream = nullptr;
   // pinned staging: the ground truths [G][8] + [G][2] (per call); the anchors [A][8] + [A][2] in a mirror of their own
   const size_t a_bytes = (size_t)A * 10 * 8, g_bytes = (size_t)G * 10 * 8;
@@ -2329,7 +2311,7 @@ static int assign_targets_impl(pp_ctx_t *ctx, void *stream_, int batch, const in
     return PP_ERR_VALUE;
   }
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  DeviceGuard2 guard(ctx->device);
+  DeviceGuard guard(ctx->device);
   // Which form: anchors on the fly -> the box-centric kernel (k_targets_gt); anchor arrays -> k_targets.
   bool boxes_form = an.grid && an.per_cell <= kLdsTypes;  // (the box-centric kernel keeps the type table in LDS)
   // scratch: [0,8192) error flag + every sample's {list counter, ticket, pair counter} | col_max[Gcap] |

@@ -2024,22 +2024,6 @@ VoxLayout vox_layout(int B, int64_t max_points, const GridGeom &g, int P, int re
   return l;
 }
 
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess) {
-      ok = true;
-      if (prev != dev) (void)hipSetDevice(dev);
-    } else {
-      (void)hipGetLastError();
-    }
-  }
-  ~DeviceGuard() {
-    if (ok) (void)hipSetDevice(prev);
-  }
-};
-
 // Makes the workspace fit (B, max_points, grid, P); zeroed whenever the layout changed
 // (nothing depends on it: every array is written before it is read within one call).
 int prepare_ws(pp_ctx *ctx, hipStream_t stream, int B, int64_t max_points,

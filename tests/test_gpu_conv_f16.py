@@ -46,6 +46,11 @@ def test_rejects_null_and_bad_sizes_without_device():
         assert f(fake, None, fake, b, h, w, ci, fake, co, fake, fake, yc, off) == ERR, args
     assert f(fake, None, vp(20), 1, 4, 4, 16, fake, 64, fake, fake, 64, 0) == ERR    # misaligned x
     assert b"pp_conv3x3_f16_nhwc_dev" in L.pp_last_error()
+    for args in ((1, 65536, 65536, 16, 64, 64, 0),                    # one sample of x beyond 32-bit offsets
+                 (1, 1 << 20, 1 << 20, 16, 64, 64, 0)):               # more workgroups than a grid holds
+        b, h, w, ci, co, yc, off = args
+        assert f(fake, None, fake, b, h, w, ci, fake, co, fake, fake, yc, off) == ERR, args
+        assert b"pp_conv3x3_f16_nhwc_dev: tensor too large" in L.pp_last_error(), args
 
 
 def _unpack(p, co, ci):
@@ -136,6 +141,7 @@ def _bn_table(bias, bn):
 
 
 SHAPES = [(2, 16, 64, 2, 3),        # one K-step, a tile that is nearly all padding
+          (1, 32, 64, 9, 35),       # two chunks: the pipeline loop runs once, the peeled MFMAs read buffer 1
           (2, 64, 64, 1, 1),
           (2, 64, 64, 37, 41),      # partial tiles on both edges
           (2, 48, 192, 31, 15),     # Cin not a multiple of 32, three Cout groups

@@ -57,6 +57,9 @@ def test_rejects_null_and_bad_arguments_without_device():
     assert b"pp_convt3x3_f16_nhwc_dev" in L.pp_last_error()
     assert f(fake, None, fake, 1, 4, 4, 16, fake, 64, 2, 0, fake, vp(24), 64, 0) == ERR    # misaligned y
     assert b"pp_convt3x3_f16_nhwc_dev" in L.pp_last_error()
+    # one sample of x beyond 32-bit offsets
+    assert f(fake, None, fake, 1, 65536, 65536, 16, fake, 64, 2, 1, fake, fake, 64, 0) == ERR
+    assert b"pp_convt3x3_f16_nhwc_dev: tensor too large" in L.pp_last_error()
 
 
 @pytest.mark.parametrize("ci,co", [(16, 64), (48, 192), (256, 128)])
