@@ -19,9 +19,22 @@
 //     loaded once, as two 16-byte pieces; pixels outside the image are not loaded, zeros take their
 //     place), and is written to one of two small halo buffers at the end of the chunk;
 //   - U of chunk c+1 goes from global memory straight into the other V/U buffer (LDS-DMA: the
-//     packed layout is the LDS image);
+//     packed layout is the LDS image), a piece per position;
 //   - the halo of chunk c+1, in LDS since the previous chunk, is transformed into V of that buffer.
+//
+// The schedule inside a chunk is written out, not left to the compiler: a chunk is 16 positions of
+// 4 MFMAs, and every LDS access of the chunk is an asm statement in one of the gaps behind an MFMA,
+// waited for with the kernel's own counted s_waitcnt lgkmcnt (LDS accesses complete in order):
+//   - operands: a ring of three register sets; the two ds_read_b128 of position p+2 are issued
+//     behind the first MFMA of position p, so a read has two positions (512 MFMA cycles) to land
+//     and no wait inside a chunk drains the counter;
+//   - transform of chunk c+1: positions 0..3 read one patch column each, positions 4..7 form
+//     that column's four row-transformed values, positions 8..15 each form and write half a row
+//     of V; scalar adds, two to four per gap (packed f32 adds stall beside MFMAs);
+//   - which of this is present (a chunk behind, two chunks behind) is a compile-time property of
+//     the step, so a step's MFMAs, operand reads and transform are one basic block.
 
+#include <utility>
 #include <type_traits>
 
 #include "pp_common.h"
@@ -54,6 +67,78 @@ constexpr int kWaitVm0 = 0x0F70;
 
 typedef const __attribute__((address_space(1))) void *gptr_t;
 typedef __attribute__((address_space(3))) void *lptr_t;
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N-1>): the loop index is a constant
+// expression inside f (asm immediates, register-array indices)
+template <int... I, class F>
+__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F &&f) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F &&f) {
+  static_for_impl(std::make_integer_sequence<int, N>{}, f);
+}
+
+// The LDS accesses of a chunk's MFMA phase.  The compiler neither counts nor waits for an asm
+// statement's accesses: every value read here passes through lds_wait (below) before its first use,
+// and the writes are drained by step()'s own wait ahead of its barrier.  addr: LDS byte address
+template <int kOff>
+__device__ __forceinline__ void lds_read16(f32x4 &d, unsigned addr) {
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "i"(kOff) : "memory");
+}
+template <int kOff>
+__device__ __forceinline__ void lds_read8(f32x2 &d, unsigned addr) {
+  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "i"(kOff) : "memory");
+}
+template <int kOff>
+__device__ __forceinline__ void lds_write8(unsigned addr, f32x2 v) {
+  asm volatile("ds_write_b64 %0, %1 offset:%2" : : "v"(addr), "v"(v), "i"(kOff) : "memory");
+}
+// waits until at most kLeft LDS accesses are outstanding; the values named are read-write operands,
+// so that no use of them is scheduled ahead of the wait
+template <int kLeft>
+__device__ __forceinline__ void lds_wait(f32x4 &a, f32x4 &b) {
+  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "i"(kLeft));
+}
+template <int kLeft>
+__device__ __forceinline__ void lds_wait(f32x4 &a, f32x4 &b, f32x2 (&d)[4]) {
+  asm volatile("s_waitcnt lgkmcnt(%6)"
+               : "+v"(a), "+v"(b), "+v"(d[0]), "+v"(d[1]), "+v"(d[2]), "+v"(d[3])
+               : "i"(kLeft));
+}
+// one v_add_f32 / v_sub_f32 per component: left to the compiler, adjacent f32 adds are packed
+// (v_pk_add_f32), which costs MFMA cycles when issued beside them.  Same IEEE results
+__device__ __forceinline__ f32x2 add2(f32x2 a, f32x2 b) {
+  f32x2 r;
+  asm("v_add_f32 %0, %1, %2" : "=v"(r.x) : "v"(a.x), "v"(b.x));
+  asm("v_add_f32 %0, %1, %2" : "=v"(r.y) : "v"(a.y), "v"(b.y));
+  return r;
+}
+__device__ __forceinline__ f32x2 sub2(f32x2 a, f32x2 b) {
+  f32x2 r;
+  asm("v_sub_f32 %0, %1, %2" : "=v"(r.x) : "v"(a.x), "v"(b.x));
+  asm("v_sub_f32 %0, %1, %2" : "=v"(r.y) : "v"(a.y), "v"(b.y));
+  return r;
+}
+
+// The order of a step's LDS accesses, by position q = 0..15 (step() follows it to the letter):
+//   ahead of position 0:  operands of positions 0 and 1                       (2 + 2 reads)
+//   position q:           wait(q), operands of position q+2 while q+2 < 16    (2 reads)
+//                         with a transform: patch column q for q < 4 (4 reads), half a row of V for q >= 8 (2 writes)
+// lds_left(p, tr): the accesses issued after the operand reads of position p and ahead of wait(p),
+// which is what wait(p) leaves outstanding
+constexpr int lds_left(int p, bool tr) {
+  int n = p < 2 ? 2 * (1 - p) : 0;
+  for (int q = 0; q < p; ++q) {
+    if (q + 2 < 16 && q + 2 > p) n += 2;
+    if (tr && q < 4 && q + 2 >= p) n += 4;
+    if (tr && q >= 8 && q + 2 >= p) n += 2;
+  }
+  return n;
+}
 
 }  // namespace
 
@@ -115,28 +200,27 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
   };
 
   // ---- U: a chunk's 32 KiB are 32 pieces of 1 KiB in the order of the LDS image; wave w copies
-  // pieces w, w + 4, ... (lane l the l-th 16 bytes), global memory to LDS directly
+  // pieces w, w + 4, ... (lane l the l-th 16 bytes), global memory to LDS directly, one piece behind
+  // the last MFMA of each of a step's positions 0..7
   const int64_t useg = (int64_t)2 * Cout * 4;   // floats per (pos, chunk)
   const float *ub = u + (int64_t)co0 * 4 + lane * 4;
   // issued as an asm statement: the compiler takes an LDS-DMA builtin for a store to any LDS address and
   // drains vmcnt ahead of the chunk's first operand read.  Nothing counts these copies but the vmcnt(0)
   // that step() issues itself before its barrier
-  auto uload = [&](int chunk, float *buf) {
+  auto upiece = [&](int chunk, float *buf, int i) {   // the wave's i-th piece, i = 0..7
     const unsigned dst0 = (unsigned)(uintptr_t)(lptr_t)(buf + kVFloats) + wave * (kCo * 4 * 4);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int seg = wave + 4 * i;     // pos*2 + half
-      const float *src = ub + ((int64_t)(seg >> 1) * nchunks + chunk) * useg + (int64_t)(seg & 1) * Cout * 4;
-      const unsigned dst = __builtin_amdgcn_readfirstlane(dst0 + i * (4 * kCo * 4 * 4));
-      unsigned keep;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep)
-                   : "v"(src), "s"(dst)
-                   : "memory");
-    }
+    const int seg = wave + 4 * i;     // pos*2 + half
+    const float *src = ub + ((int64_t)(seg >> 1) * nchunks + chunk) * useg + (int64_t)(seg & 1) * Cout * 4;
+    const unsigned dst = __builtin_amdgcn_readfirstlane(dst0 + i * (4 * kCo * 4 * 4));
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(src), "s"(dst)
+                 : "memory");
   };
 
-  // ---- transform: thread = (tile, channel pair) of the input patch, read from the halo buffer
+  // ---- transform: thread = (tile, channel pair) of the input patch, read from the halo buffer.
+  // This form transforms chunk 0 ahead of the loop; step() carries the same arithmetic in slices
   const int lp = tid & 3;           // channel pair: channels 2lp, 2lp+1 of the chunk
   const int lt = tid >> 2;          // tile 0..63
   const int p_off = (lp >> 1) * kHaloHalf + (2 * (lt >> 3) * kHaloW + 2 * (lt & 7)) * 4 + 2 * (lp & 1);
@@ -179,36 +263,96 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
   f32x16 acc[16];
 
   // one chunk: the halo loads of chunk+2 and the U copy of chunk+1 are issued, the MFMAs run on
-  // `cur`, chunk+1's halo is transformed into `nxt`, then chunk+2's halo is written to LDS
-  auto step = [&](int chunk, auto first) {
-    float *cur = lds + (chunk & 1) * kBufFloats, *nxt = lds + ((chunk + 1) & 1) * kBufFloats;
-    const bool more = chunk + 1 < nchunks, more2 = chunk + 2 < nchunks;
+  // `cur` with chunk+1's halo transformed into `nxt` in their gaps, then chunk+2's halo is written
+  // to LDS.  first: the accumulators are set, not added to; more, more2: chunk+1, chunk+2 exist
+  const unsigned lds_addr = (unsigned)(uintptr_t)(lptr_t)lds;
+  auto step = [&](int chunk, auto first_, auto more_, auto more2_) {
+    constexpr bool first = decltype(first_)::value, more = decltype(more_)::value,
+                   more2 = decltype(more2_)::value;
+    constexpr bool tr = more;   // the transform of chunk+1 rides in this step's gaps
+    const unsigned cur = lds_addr + (chunk & 1) * (kBufFloats * 4);
+    float *const nxt = lds + ((chunk + 1) & 1) * kBufFloats;
+    const unsigned a_addr = cur + a_off * 4, b_addr = cur + b_off * 4;
+    // the transform's patch (halo buffer of chunk+1) and its V (in `nxt`)
+    const unsigned p_addr = lds_addr + (2 * kBufFloats + ((chunk + 1) & 1) * kHaloFloats + p_off) * 4;
+    const unsigned v_addr = lds_addr + (((chunk + 1) & 1) * kBufFloats + v_off) * 4;
+    constexpr int kPos = 2 * kTiles * 4 * 4;   // bytes from position to position, V and U alike
+    static_assert(kTiles == kCo, "one position stride for V and U");
+    f32x4 av[3], bv[3];
+    f32x2 d[4][4], e[16], v[2];
+    lds_read16<0>(av[0], a_addr);
+    lds_read16<0>(bv[0], b_addr);
+    lds_read16<kPos>(av[1], a_addr);
+    lds_read16<kPos>(bv[1], b_addr);
     float4 hr[kHaloPer];
-    if (more2) hload(chunk + 2, hr);
-    // `nxt` was last read in chunk-1, before the barrier that ended it
-    if (more) uload(chunk + 1, nxt);
-    // operands of position p+1 are read while the MFMAs of p run
-    float4 an = *reinterpret_cast<const float4 *>(cur + a_off);
-    float4 bn = *reinterpret_cast<const float4 *>(cur + b_off);
-#pragma unroll
-    for (int p = 0; p < 16; ++p) {
-      const float4 av = an, bv = bn;
-      if (p + 1 < 16) {
-        an = *reinterpret_cast<const float4 *>(cur + (p + 1) * (2 * kTiles * 4) + a_off);
-        bn = *reinterpret_cast<const float4 *>(cur + (p + 1) * (2 * kCo * 4) + b_off);
-      }
-      if constexpr (decltype(first)::value)
-        acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, f32x16{}, 0, 0, 0);
+    if constexpr (more2) hload(chunk + 2, hr);
+    static_for<16>([&](auto pc) {
+      constexpr int p = decltype(pc)::value, s = p % 3;
+      constexpr int left = lds_left(p, tr);
+      static_assert(left < 16, "lgkmcnt has four bits");
+      if constexpr (tr && p >= 4 && p < 8)
+        lds_wait<left>(av[s], bv[s], d[p - 4]);
       else
-        acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc[p], 0, 0, 0);
-      acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc[p], 0, 0, 0);
-      acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc[p], 0, 0, 0);
-      acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc[p], 0, 0, 0);
-    }
-    if (more) transform(halo + ((chunk + 1) & 1) * kHaloFloats, nxt);
+        lds_wait<left>(av[s], bv[s]);
+      // ---- gap 0: the operands of position p+2, into the set that position p-1 has left
+      if constexpr (first)
+        acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s].x, bv[s].x, f32x16{}, 0, 0, 0);
+      else
+        acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s].x, bv[s].x, acc[p], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (p + 2 < 16) {
+        lds_read16<(p + 2) * kPos>(av[(p + 2) % 3], a_addr);
+        lds_read16<(p + 2) * kPos>(bv[(p + 2) % 3], b_addr);
+      }
+      // V = B^T d B, rows first.  B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]
+      if constexpr (tr && p >= 4 && p < 8) {
+        constexpr int c = p - 4;
+        e[c] = sub2(d[c][0], d[c][2]);
+        e[4 + c] = add2(d[c][1], d[c][2]);
+      }
+      if constexpr (tr && p >= 8) {
+        constexpr int r = (p - 8) >> 1;
+        v[0] = (p & 1) ? sub2(e[4 * r + 2], e[4 * r + 1]) : sub2(e[4 * r], e[4 * r + 2]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      // ---- gap 1
+      acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s].y, bv[s].y, acc[p], 0, 0, 0);
+      if constexpr (tr && p < 4) {   // patch column p, rows 0 and 1
+        lds_read8<(0 * kHaloW + p) * 16>(d[p][0], p_addr);
+        lds_read8<(1 * kHaloW + p) * 16>(d[p][1], p_addr);
+      }
+      if constexpr (tr && p >= 4 && p < 8) {
+        constexpr int c = p - 4;
+        e[8 + c] = sub2(d[c][2], d[c][1]);
+        e[12 + c] = sub2(d[c][1], d[c][3]);
+      }
+      if constexpr (tr && p >= 8) {
+        constexpr int r = (p - 8) >> 1;
+        v[1] = (p & 1) ? sub2(e[4 * r + 1], e[4 * r + 3]) : add2(e[4 * r + 1], e[4 * r + 2]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      // ---- gap 2
+      acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s].z, bv[s].z, acc[p], 0, 0, 0);
+      if constexpr (tr && p < 4) {   // rows 2 and 3
+        lds_read8<(2 * kHaloW + p) * 16>(d[p][2], p_addr);
+        lds_read8<(3 * kHaloW + p) * 16>(d[p][3], p_addr);
+      }
+      if constexpr (tr && p >= 8) {  // V[row r][columns 2(p&1), 2(p&1)+1]
+        constexpr int r = (p - 8) >> 1, c0 = 2 * (p & 1);
+        lds_write8<(4 * r + c0) * kPos>(v_addr, v[0]);
+        lds_write8<(4 * r + c0 + 1) * kPos>(v_addr, v[1]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      // ---- gap 3
+      acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s].w, bv[s].w, acc[p], 0, 0, 0);
+      // `nxt` was last read in chunk-1, before the barrier that ended it
+      if constexpr (more && p < 8) upiece(chunk + 1, nxt, p);
+      __builtin_amdgcn_sched_barrier(0);
+    });
     // this halo buffer held chunk's own halo, last read by the transform of chunk-1's step
-    if (more2) hstore(halo + (chunk & 1) * kHaloFloats, hr);
-    __builtin_amdgcn_s_waitcnt(kWaitVm0);   // the U copy
+    if constexpr (more2) hstore(halo + (chunk & 1) * kHaloFloats, hr);
+    // the U copy and the V writes: the compiler knows of neither
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();
   };
 
@@ -216,7 +360,8 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
     float4 h0[kHaloPer], h1[kHaloPer];
     hload(0, h0);
     if (nchunks > 1) hload(1, h1);
-    uload(0, lds);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) upiece(0, lds, i);
     hstore(halo, h0);
     if (nchunks > 1) hstore(halo + kHaloFloats, h1);
     __builtin_amdgcn_s_waitcnt(kWaitVm0);
@@ -224,9 +369,21 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
     transform(halo, lds);
     __syncthreads();
   }
-  step(0, std::true_type{});
+  // the chunk loop, peeled: first, steady, second-to-last and last
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  if (nchunks == 1) {
+    step(0, yes, no, no);
+  } else if (nchunks == 2) {
+    step(0, yes, yes, no);
+    step(1, no, no, no);
+  } else {
+    step(0, yes, yes, yes);
 #pragma unroll 1
-  for (int chunk = 1; chunk < nchunks; ++chunk) step(chunk, std::false_type{});
+    for (int chunk = 1; chunk < nchunks - 2; ++chunk) step(chunk, no, yes, yes);
+    step(nchunks - 2, no, yes, no);
+    step(nchunks - 1, no, no, no);
+  }
 
   // ---- output transform Y = A^T M A (A^T = [1 1 1 0; 0 1 -1 -1]) and the epilogue, per lane:
   // channel co0 + 32wc + l32, tiles 32wt + (r&3) + 8(r>>2) + 4h for accumulator register r
@@ -290,14 +447,14 @@ extern "C" int pp_conv3x3_wino_nhwc_dev(pp_ctx_t *ctx, void *stream_, const floa
     set_error("pp_conv3x3_wino_nhwc_dev: tensor too large");
     return PP_ERR_VALUE;
   }
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != ctx->device) (void)hipSetDevice(ctx->device);
-  hipLaunchKernelGGL(k_conv3x3_wino, dim3((unsigned)blocks, (unsigned)(out_channels / 64)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream_), x_dev, u_dev, params_dev, y_dev + y_channel_offset,
-                     height, width, in_channels, out_channels, y_channels, (int)tiles_x, (int)tiles_y);
-  hipError_t e = hipGetLastError();
-  if (prev >= 0 && prev != ctx->device) (void)hipSetDevice(prev);
+  hipError_t e;
+  {
+    DeviceGuard guard(ctx->device);
+    hipLaunchKernelGGL(k_conv3x3_wino, dim3((unsigned)blocks, (unsigned)(out_channels / 64)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream_), x_dev, u_dev, params_dev, y_dev + y_channel_offset,
+                       height, width, in_channels, out_channels, y_channels, (int)tiles_x, (int)tiles_y);
+    e = hipGetLastError();      // the launch's, before the guard's own HIP call
+  }
   if (e != hipSuccess) {
     set_error("k_conv3x3_wino launch failed: %s", hipGetErrorString(e));
     return PP_ERR_HIP;
