@@ -243,6 +243,49 @@ def _conv_stem(feats, inds, h, w, w_taps, table, cout):
     return out
 
 
+#: pp_head1x1_nhwc_dev's limits: sources, output channels, bytes of LDS for the packed weight and the tables
+_HEAD_MAX_SOURCES, _HEAD_MAX_OUT, _HEAD_MAX_LDS = 4, 64, 160 * 1024
+
+
+def _head_fits(channels, n_out):
+    """The head kernel takes sources of these channel counts and ``n_out`` outputs."""
+    kb = sum(channels) // 16
+    return (1 <= len(channels) <= _HEAD_MAX_SOURCES and all(c >= 16 and c % 16 == 0 for c in channels)
+            and 1 <= n_out <= _HEAD_MAX_OUT and kb * (((n_out + 15) // 16) * 1024 + 192) <= _HEAD_MAX_LDS)
+
+
+def _head_filter(w):
+    """1x1 conv weight [N,K,1,1] -> pp_head1x1_nhwc_dev's layout [K/16][Npad/16][64][4]: element [kb][nt][l][j] is
+    W[16*nt + l%16][16*kb + 4*(l//16) + j] (a lane's four consecutive channels of a block of 16), rows past N zero."""
+    n, k = w.shape[:2]
+    nt = (n + 15) // 16
+    wp = w.detach().new_zeros((nt * 16, k))
+    wp[:n] = w.detach().reshape(n, k)
+    return wp.reshape(nt, 16, k // 16, 4, 4).permute(2, 0, 3, 1, 4).contiguous()
+
+
+def _part_ok(t):
+    """A source the head kernel reads in place: a dense 16-byte aligned channels-last f32 tensor."""
+    return _is_nhwc(t) and t.dtype == torch.float32 and t.data_ptr() % 16 == 0
+
+
+def _head_parts(parts, w_packed, bias, n_out):
+    """pp_head1x1_nhwc_dev: the 1x1 head convolution of the channel concatenation of ``parts`` -- pairs
+    ``(tensor, table)`` of equally sized channels-last tensors, ``table`` None or the bias/ReLU/BatchNorm table
+    to apply on load -- without building the concatenation; a new channels-last [B,n_out,H,W] tensor."""
+    x0 = parts[0][0]
+    B, _, H, W = x0.shape
+    n = len(parts)
+    y = torch.empty((B, n_out, H, W), dtype=torch.float32, device=x0.device, memory_format=torch.channels_last)
+    src = (ctypes.c_void_p * n)(*[t.data_ptr() for t, _ in parts])
+    stride = (ctypes.c_int64 * n)(*[t.shape[1] for t, _ in parts])
+    channels = (ctypes.c_int32 * n)(*[t.shape[1] for t, _ in parts])
+    tables = (ctypes.c_void_p * n)(*[None if tb is None else tb.data_ptr() for _, tb in parts])
+    _call("pp_head1x1_nhwc_dev", x0.device, B * H * W, n, src, stride, channels, tables, _vp(w_packed), _vp(bias),
+          int(n_out), _vp(y), int(n_out))
+    return y
+
+
 def _use_fused_epilogue(module, x):
     # the epilogue kernels work in place through raw pointers: autograd never sees them, so
     # they are for no-grad inference only (eval-mode fine-tuning / saliency take the modules)
@@ -289,24 +332,31 @@ class _FusedConv:
                 hit = self._packed[kind] = (key, pack(weight.transpose(0, 1).flip(2, 3) if transposed else weight))
         return hit[1]
 
-    def __call__(self, module, conv, bn, x, out=None, channel_offset=0, transposed=False):
+    def __call__(self, module, conv, bn, x, out=None, channel_offset=0, transposed=False, defer=False):
         """``bn(relu(conv(x)))`` into a new tensor, or into channels [channel_offset, +Cout) of ``out``: the fp16
         kernel if ``module.half_mma`` and the layer is eligible, else the Winograd kernel if ``module.winograd``
         and the layer is eligible, else (a strided ConvTranspose) the fp16 transposed-conv kernel if
         ``module.half_mma_up`` and the layer is eligible, else MIOpen's conv (``transposed``: ConvTranspose) and
-        the epilogue kernel."""
+        the epilogue kernel.
+
+        ``defer`` (``out`` is None): a pair ``(tensor, table)`` for a consumer that applies the epilogue as it
+        reads (``PPDetectionHead.forward_parts``).  ``table`` is None where a fused kernel has applied it already;
+        on the MIOpen branch ``tensor`` is the bare conv output and ``_epilogue(tensor, table)`` is still owed."""
+        if defer and out is not None:
+            raise ValueError("a deferred epilogue has no destination")
+        done = (lambda t: (t, None)) if defer else (lambda t: t)
         out_ok = out is None or (_is_nhwc(out) and out.dtype == torch.float32 and out.shape[0] == x.shape[0]
                                  and out.shape[2:] == x.shape[2:])
         if _f16_ok(module, conv, x, transposed) and out_ok and (out is None or out.data_ptr() % 16 == 0):
             w16 = self.packed("f16", conv.weight, _f16_filter, transposed)
-            return _conv_f16(x, w16, self.table(conv.bias, bn), conv.out_channels, out, channel_offset)
+            return done(_conv_f16(x, w16, self.table(conv.bias, bn), conv.out_channels, out, channel_offset))
         if _wino_ok(module, conv, x, transposed) and out_ok:
             u = self.packed("wino", conv.weight, _wino_filter, transposed)
-            return _conv_wino(x, u, self.table(conv.bias, bn), conv.out_channels, out, channel_offset)
+            return done(_conv_wino(x, u, self.table(conv.bias, bn), conv.out_channels, out, channel_offset))
         if transposed and _convt_f16_ok(module, conv, x, out):
             w16 = self.packed("convt_f16", conv.weight, _convt_f16_filter)
-            return _convt_f16(x, w16, self.table(conv.bias, bn), conv.out_channels, conv.stride[0],
-                              conv.output_padding[0], out, channel_offset)
+            return done(_convt_f16(x, w16, self.table(conv.bias, bn), conv.out_channels, conv.stride[0],
+                                   conv.output_padding[0], out, channel_offset))
         w = self.packed("nhwc", conv.weight, _nhwc_weight) if _is_nhwc(x) else conv.weight
         if transposed:
             y = F.conv_transpose2d(x, w, None, conv.stride, conv.padding, conv.output_padding)
@@ -314,6 +364,8 @@ class _FusedConv:
                 y = y.contiguous(memory_format=torch.channels_last if _is_nhwc(out) else torch.contiguous_format)
         else:
             y = F.conv2d(x, w, None, conv.stride, conv.padding)
+        if defer:
+            return _dense(y), self.table(conv.bias, bn)
         return _epilogue(_dense(y), self.table(conv.bias, bn), out, channel_offset)
 
 
@@ -617,14 +669,17 @@ class PPUpBlock(nn.Module):
         self.half_mma_up = False
         self._fused = _FusedConv()
 
-    def forward(self, x, out=None, channel_offset=0):
+    def forward(self, x, out=None, channel_offset=0, defer=False):
+        """``defer``: ``_FusedConv.__call__``'s, on the fused inference path only."""
         if not _use_fused_epilogue(self, x):
+            if defer:
+                raise RuntimeError("PPUpBlock: a deferred epilogue needs the fused inference path")
             if self.fused_train and _relu_bn_fusable(x, self.bn):
                 ct = self.conv2d_t
                 return _relu_bn(F.conv_transpose2d(x, ct.weight, None, ct.stride, ct.padding, ct.output_padding),
                                 self.bn, conv_bias=ct.bias)
             return self.bn(F.relu(self.conv2d_t(x)))
-        return self._fused(self, self.conv2d_t, self.bn, x, out, channel_offset, transposed=True)
+        return self._fused(self, self.conv2d_t, self.bn, x, out, channel_offset, transposed=True, defer=defer)
 
 
 def up3_output_padding(canvas):
@@ -656,11 +711,27 @@ class PPBackbone(nn.Module):
         #: its epilogue in one kernel pair; the 95 % empty canvas is never built)
         self.sparse_stem = True
 
-    def forward(self, x, after_stem=False):
-        """``after_stem``: ``x`` is ``down1.stem``'s output instead of the canvas."""
+    def parts_ok(self, x):
+        """``forward(x, parts=True)`` is possible: every up block on the fused inference path, ``x`` channels-last."""
+        return all(_use_fused_epilogue(up, x) for up in (self.up1, self.up2, self.up3)) and _is_nhwc(x)
+
+    def forward(self, x, after_stem=False, parts=False):
+        """``after_stem``: ``x`` is ``down1.stem``'s output instead of the canvas.  ``parts`` (needs ``parts_ok``):
+        the three up blocks' outputs as ``(tensor, table)`` pairs (``_FusedConv.__call__``'s ``defer``) in the
+        order of the concatenation, each block in a tensor of its own; the concatenated tensor is not built."""
+        if parts:
+            if not self.parts_ok(x):
+                raise RuntimeError("PPBackbone: parts need the fused inference path and a channels-last input")
+            x = self.down1(x, 1 if after_stem else 0)
+            p1 = self.up1(x, defer=True)
+            x = self.down2(x)
+            p2 = self.up2(x, defer=True)
+            x = self.down3(x)
+            return [p1, p2, self.up3(x, defer=True)]
         # inference: the three up blocks write their channel slices of the concatenated output directly (no
         # torch.cat copy); otherwise ``out`` is None, the offsets are 0 and each returns its own tensor
-        fused = _use_fused_epilogue(self.up1, x)
+        # (all three or none: a block off the fused path returns a tensor of its own and takes no ``out``)
+        fused = all(_use_fused_epilogue(up, x) for up in (self.up1, self.up2, self.up3))
         c = self.up1.conv2d_t.out_channels if fused else 0
         x = self.down1(x, 1 if after_stem else 0)
         out = None
@@ -685,7 +756,12 @@ class PPDetectionHead(nn.Module):
         #: inference on channels-last activations: both 1x1 convolutions as ONE (the 384-channel
         #: input is read once); the results are channel slices of the merged output
         self.merge_heads = True
+        #: ... and straight from the three up blocks' outputs (``forward_parts``; csrc/pp_head.hip: no concatenated
+        #: tensor, up2's and up3's bias/ReLU/BatchNorm applied on load, the head's bias in the same kernel); needs
+        #: ``merge_heads``.  Changes results at summation-order level.  Off here, on in ``PillarPipeline``
+        self.fused_parts = False
         self._merged = _LayoutCache()
+        self._packed = _LayoutCache()
 
     def forward(self, x):
         if (self.training or not self.merge_heads or not x.is_cuda or not _is_nhwc(x)
@@ -698,6 +774,38 @@ class PPDetectionHead(nn.Module):
         y = F.conv2d(x, w, b)
         n = self.cls.out_channels
         return y[:, :n], y[:, n:]
+
+    def _is_1x1(self, conv):
+        return (tuple(conv.kernel_size) == (1, 1) and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (0, 0)
+                and tuple(conv.dilation) == (1, 1) and conv.groups == 1 and conv.bias is not None
+                and conv.weight.dtype == torch.float32)
+
+    def parts_ok(self, channels):
+        """``forward_parts`` may take sources of these channel counts: both switches on, eval mode, no grad, two
+        plain 1x1 convolutions of their concatenation, within the kernel's limits."""
+        return (self.fused_parts and self.merge_heads and not self.training and not torch.is_grad_enabled()
+                and self._is_1x1(self.cls) and self._is_1x1(self.reg) and self.cls.weight.is_cuda
+                and self.cls.in_channels == self.reg.in_channels == sum(channels)
+                and _head_fits(channels, self.cls.out_channels + self.reg.out_channels))
+
+    def forward_parts(self, parts):
+        """``forward`` of the channel concatenation of ``parts`` (``PPBackbone.forward(..., parts=True)``'s pairs),
+        read where the parts lie.  A part the kernel cannot read in place (not dense channels-last, misaligned)
+        sends the call the long way round: the owed epilogues, ``torch.cat``, ``forward``."""
+        if (self.parts_ok([t.shape[1] for t, _ in parts]) and all(_part_ok(t) for t, _ in parts)
+                and all(t.shape[0] == parts[0][0].shape[0] and t.shape[2:] == parts[0][0].shape[2:]
+                        and t.device == self.cls.weight.device for t, _ in parts)):
+            w, b = self._packed.get(
+                (self.cls.weight, self.cls.bias, self.reg.weight, self.reg.bias),
+                lambda: (_head_filter(torch.cat((self.cls.weight, self.reg.weight), 0)),
+                         torch.cat((self.cls.bias, self.reg.bias), 0).contiguous()))
+            n = self.cls.out_channels
+            y = _head_parts(parts, w, b, n + self.reg.out_channels)
+            return y[:, :n], y[:, n:]
+        done = [t if table is None else _epilogue(t, table) for t, table in parts]
+        nhwc = all(_is_nhwc(t) for t in done)
+        x = torch.cat(done, dim=1)
+        return self.forward(x.contiguous(memory_format=torch.channels_last) if nhwc else x)
 
 
 #: what PPModel.set_inference_precision takes
@@ -744,14 +852,27 @@ class PPModel(nn.Module):
     def forward_canvas(self, canvas):
         """The network from PPScatter's output on: ``canvas[B,C,H,W]`` in either memory
         format (the fused HIP voxelizer + feature net + scatter writes it channels-last)."""
+        if self._parts_ok(canvas):
+            return self.det_head.forward_parts(self.backbone(canvas, parts=True))
         return self.det_head(self.backbone(canvas))
+
+    def _parts_ok(self, x):
+        """The detection head reads the up blocks' outputs directly (``PPDetectionHead.fused_parts``) for the
+        backbone input ``x``."""
+        bb = self.backbone
+        return (bb.parts_ok(x) and self.det_head.parts_ok(
+            [up.conv2d_t.out_channels for up in (bb.up1, bb.up2, bb.up3)]))
 
     def forward_features(self, feats, inds):
         """Same network from PPFeatureNet's output ``feats[B,C,P]`` on (the fused
         HIP voxelizer + feature net produces it directly)."""
         if _stem_ok(self.backbone, self.scatter, feats, inds):
             x = self.backbone.down1.stem(feats, inds, self.scatter.h, self.scatter.w)
+            if self._parts_ok(x):
+                return self.det_head.forward_parts(self.backbone(x, after_stem=True, parts=True))
             return self.det_head(self.backbone(x, after_stem=True))
         x = self.scatter(feats, inds)
+        if self._parts_ok(x):
+            return self.det_head.forward_parts(self.backbone(x, parts=True))
         x = self.backbone(x)
         return self.det_head(x)

@@ -34,6 +34,8 @@ class PillarPipeline:
         self.model = PPModel(9, feature_channels, anchor_cfg.per_cell * num_classes,
                              anchor_cfg.per_cell * reg_dims, h, w).to(self.device)
         self.model.set_inference_precision(precision)
+        # inference: the head reads the up blocks' outputs where they lie (PPDetectionHead.fused_parts)
+        self.model.det_head.fused_parts = True
         self.loss = PPLoss()
         self.assigner = None
         if with_targets:

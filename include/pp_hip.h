@@ -612,6 +612,34 @@ int pp_conv3x3_s2_pillars_nhwc_dev(pp_ctx_t *ctx, void *stream, const float *fea
                                    void *scratch_dev, size_t scratch_bytes, float *y_dev);
 
 /*
+ * The detection head (model/model.py:144-160, both 1x1 convolutions as one) on the up blocks' outputs
+ * where they lie, channels-last f32, without the concatenated tensor (inference):
+ *   y[p][n] = bias[n] + sum_k sum_c W[n][off_k + c] * a_k[p][c],   off_k = channels of the sources before k
+ *   a_k[p][c] = src_k[p][c]                                        src_table_dev[k] NULL
+ *             = max(src_k[p][c] + b_c, 0) * s_c + t_c              src_table_dev[k] [C_k][3] f32 {b, s, t}
+ * The second form is pp_bias_relu_bn_nhwc_dev's expression, operation for operation, applied as the
+ * source is loaded: the values multiplied are the bits that kernel would have stored.  f32 throughout
+ * (v_mfma_f32_16x16x4_f32, f32 accumulation, channels summed in ascending blocks of 16).
+ *   src_dev, src_stride, src_channels, src_table_dev: HOST arrays of n_src (1..4) entries; src_dev[k]
+ *                points at source k's first pixel, 16-byte aligned, its pixels src_stride[k] floats
+ *                apart (>= C_k, a multiple of 4: a channel slice of a wider tensor is a source);
+ *                C_k a multiple of 16
+ *   w_packed_dev [K/16][Npad/16][64][4] f32, K = sum C_k, Npad = out_channels rounded up to 16:
+ *                element [kb][nt][l][j] = W[16*nt + l%16][16*kb + 4*(l/16) + j], zero for rows past
+ *                out_channels; 16-byte aligned
+ *   bias_dev     [out_channels] f32
+ *   y_dev        rows of y_stride (>= out_channels) floats per pixel; [p][0, out_channels) is written
+ *                exactly once, nothing else
+ * out_channels 1..64; (K/16) * (Npad * 64 + 192) bytes must fit 160 KiB of LDS (K = 384 at Npad 64).
+ * One launch of persistent workgroups: no allocation, no synchronisation (graph-capturable); no atomics
+ * and a fixed summation order, so the result is bit-identical from call to call.
+ */
+int pp_head1x1_nhwc_dev(pp_ctx_t *ctx, void *stream, int64_t pixels, int n_src,
+                        const float *const *src_dev, const int64_t *src_stride, const int *src_channels,
+                        const float *const *src_table_dev, const float *w_packed_dev,
+                        const float *bias_dev, int out_channels, float *y_dev, int64_t y_stride);
+
+/*
  * The ReLU -> BatchNorm2d tail of the backbone blocks in TRAINING mode (model/model.py:76-84,
  * 105-109; BatchNorm with batch statistics), forward and backward, on NCHW f32 tensors:
  *   forward   y = gamma*(max(z,0) - mean)*invstd + beta with the batch mean / biased variance
