@@ -19,6 +19,7 @@ HEADERS = [os.path.join(_HERE, "csrc", "pp_common.h"), os.path.join(_HERE, "csrc
 PP_OK, PP_ERR_INDEX, PP_ERR_VALUE, PP_ERR_WINDING = 0, -2, -3, -4
 PP_ERR_NOMEM, PP_ERR_HIP, PP_ERR_INTERNAL = -5, -6, -7
 ORDER_ROW_MAJOR, ORDER_SCRAMBLED = 0, 1
+NMS_ANCHOR_RECT, NMS_ROTATED_BEV = 0, 1     # PP_NMS_*: pp_decode_nms_batch_dev's nms_mode
 NUM_FEATURES = 9
 MAX_BATCH = 32
 MAX_INGEST_SWEEPS = 16       # PP_MAX_INGEST_SWEEPS
@@ -27,7 +28,7 @@ KERNEL_SPLIT, KERNEL_TILE, KERNEL_EMIT = 0, 1, 2
 EXPORTS = [
     "pp_last_error", "pp_version", "pp_device_count", "pp_ctx_create", "pp_ctx_destroy",
     "pp_voxelize_reserve", "pp_voxelize_dev", "pp_voxelize_step_dev", "pp_voxelize_step_pfn_canvas_dev", "pp_voxelize_step_kernel_name", "pp_voxelize_step_reset", "pp_subtract_mean_dev", "pp_voxelize_pfn_dev", "pp_voxelize_pfn_canvas_dev", "pp_voxelize_pfn_canvas_reuse_dev", "pp_pfn_dense_dev", "pp_scatter_canvas_dev", "pp_pfn_train_stats_dev", "pp_pfn_train_backward_dev", "pp_create_pillars_f64", "pp_make_ious_f64",
-    "pp_iou_check", "pp_make_ious_dev", "pp_assign_targets_dev", "pp_assign_targets_grid_dev", "pp_assign_targets_batch_dev", "pp_assign_targets_grid_batch_dev", "pp_ingest_dev", "pp_ingest_sweeps_dev", "pp_decode_dev", "pp_decode_strided_dev", "pp_decode_batch_dev", "pp_bias_relu_bn_dev", "pp_bias_relu_bn_nhwc_dev", "pp_conv3x3_wino_nhwc_dev", "pp_conv3x3_f16_nhwc_dev", "pp_convt3x3_f16_nhwc_dev", "pp_conv3x3_s2_pillars_nhwc_dev", "pp_head1x1_nhwc_dev", "pp_relu_bn_train_fwd_dev", "pp_relu_bn_train_bwd_dev", "pp_ctx_set_timing",
+    "pp_iou_check", "pp_make_ious_dev", "pp_assign_targets_dev", "pp_assign_targets_grid_dev", "pp_assign_targets_batch_dev", "pp_assign_targets_grid_batch_dev", "pp_ingest_dev", "pp_ingest_sweeps_dev", "pp_decode_dev", "pp_decode_strided_dev", "pp_decode_batch_dev", "pp_decode_nms_batch_dev", "pp_bias_relu_bn_dev", "pp_bias_relu_bn_nhwc_dev", "pp_conv3x3_wino_nhwc_dev", "pp_conv3x3_f16_nhwc_dev", "pp_convt3x3_f16_nhwc_dev", "pp_conv3x3_s2_pillars_nhwc_dev", "pp_head1x1_nhwc_dev", "pp_relu_bn_train_fwd_dev", "pp_relu_bn_train_bwd_dev", "pp_ctx_set_timing",
     "pp_ctx_read_emit_ms", "pp_ctx_read_kernel_ms", "pp_voxelize_check", "pp_host_pool_selftest",
     "pp_box3d_iou_dev", "pp_eval_match_batch_dev",
 ]
@@ -234,6 +235,8 @@ def _load(path):
                                         ctypes.POINTER(DecodeParams), vp, vp, vp]
     L.pp_decode_batch_dev.argtypes = [vp, vp, c_int, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp,
                                       ctypes.POINTER(DecodeParams), vp, vp, vp]
+    L.pp_decode_nms_batch_dev.argtypes = [vp, vp, c_int, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp,
+                                          ctypes.POINTER(DecodeParams), c_int, c_int, vp, vp, vp]
     L.pp_bias_relu_bn_dev.argtypes = [vp, vp, vp, i64, c_int, i64, vp, vp, i64, i64]
     L.pp_bias_relu_bn_nhwc_dev.argtypes = [vp, vp, vp, i64, c_int, vp, vp, i64, i64]
     L.pp_conv3x3_wino_nhwc_dev.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, vp, c_int, vp, vp, i64, i64]

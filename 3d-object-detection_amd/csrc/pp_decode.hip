@@ -18,9 +18,17 @@
 // through an on-the-fly merge of their next 256 entries each, more than that after an
 // in-place bitonic sort in global memory -- in 256-candidate chunks: kept-list test, an
 // in-chunk suppression matrix resolved serially, and the box decode of the survivors).
+//
+// pp_decode_nms_batch_dev adds two switches that have no counterpart in the reference: class-aware
+// suppression, and PP_NMS_ROTATED_BEV -- the pair test is the f64 BEV IoU of the DECODED boxes (the
+// rows of the output) instead of the f32 IoU of the anchor rectangles.  k_nms is a template over the
+// box record and the pair test; the rotated form splits each test into a cheap reject for all pairs
+// and a register-resident Sutherland-Hodgman clip for the pairs that pass (rot_pairs).
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "pp_common.h"
 
@@ -175,14 +183,9 @@ __device__ __forceinline__ bool suppresses(const NmsBox &i, const NmsBox &j, flo
   return ovr > thresh;
 }
 
-// make_pred_boxes (evaluate.py:33-89) + move_box_to_car_space (:91-125, image=True) for output
-// row i; a = kept anchor id or -1
-__device__ void decode_row(const DecodeArgs &d, int i, int a) {
-  double *o = d.boxes + (int64_t)i * 9;
-  if (a < 0) {
-    for (int k = 0; k < 9; ++k) o[k] = 0.0;
-    return;
-  }
+// make_pred_boxes (evaluate.py:33-89) + move_box_to_car_space (:91-125, image=True) for anchor a:
+// the output row x,y,z,w,l,h,yaw,score,class.  The one decode: the rotated NMS compares these values.
+__device__ void decode_box(const DecodeArgs &d, int a, double (&o)[9]) {
   float score;
   int klass;
   anchor_score(d, a, score, klass);
@@ -214,8 +217,271 @@ __device__ void decode_row(const DecodeArgs &d, int i, int a) {
   o[8] = (double)klass;
 }
 
+// output row i; a = kept anchor id or -1
+__device__ void decode_row(const DecodeArgs &d, int i, int a) {
+  double *o = d.boxes + (int64_t)i * 9;
+  double v[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (a >= 0) decode_box(d, a, v);
+  for (int k = 0; k < 9; ++k) o[k] = v[k];
+}
+
+// ---- what k_nms compares: the box record in LDS, its load and the pair test ----
+
+struct NmsBoxC {  // NmsBox + the argmax class (class-aware anchor mode)
+  float x1, y1, x2, y2, area;
+  int cls;
+};
+
+// PP_NMS_ANCHOR_RECT; CA: a kept box only suppresses candidates of its own class
+template <bool CA>
+struct AnchorNms {
+  static constexpr bool kRotated = false;
+  using Box = std::conditional_t<CA, NmsBoxC, NmsBox>;
+  __device__ static __forceinline__ Box load(const DecodeArgs &d, int a) {
+    const NmsBox b = load_box(d, a);
+    if constexpr (CA) {
+      float score;
+      int klass;
+      anchor_score(d, a, score, klass);
+      return {b.x1, b.y1, b.x2, b.y2, b.area, klass};
+    } else {
+      return b;
+    }
+  }
+  __device__ static __forceinline__ bool suppresses(const Box &i, const Box &j, float thresh) {
+    if constexpr (CA) {
+      const NmsBox bi = {i.x1, i.y1, i.x2, i.y2, i.area}, bj = {j.x1, j.y1, j.x2, j.y2, j.area};
+      return i.cls == j.cls && pp::suppresses(bi, bj, thresh);
+    } else {
+      return pp::suppresses(i, j, thresh);
+    }
+  }
+};
+
+// PP_NMS_ROTATED_BEV: the decoded footprint, 64 B (corners are rebuilt in registers for the clip).
+// ok = x, y, w, l, yaw finite and w*l > 0; a box that is not ok takes part in no pair.
+struct RotBox {
+  double x, y, w, l, c, s, r;  // centre, width across / length along yaw, cos / sin yaw, circumradius
+  int cls, ok;
+};
+
+template <bool CA>
+struct RotatedNms {
+  static constexpr bool kRotated = true;
+  static constexpr bool kClassAware = CA;
+  using Box = RotBox;
+  __device__ static __forceinline__ Box load(const DecodeArgs &d, int a) {
+    double v[9];
+    decode_box(d, a, v);
+    RotBox b;
+    b.x = v[0];
+    b.y = v[1];
+    b.w = v[3];
+    b.l = v[4];
+    b.ok = isfinite(v[0]) && isfinite(v[1]) && isfinite(v[3]) && isfinite(v[4]) && isfinite(v[6]) &&
+           v[3] * v[4] > 0.0;
+    b.c = cos(v[6]);
+    b.s = sin(v[6]);
+    const double hl = v[4] * 0.5, hw = v[3] * 0.5;
+    b.r = sqrt(hl * hl + hw * hw);
+    b.cls = (int)v[8];
+    return b;
+  }
+};
+
+// footprint corners counter-clockwise (pp_eval.hip make_box, Box.bottom_corners)
+__device__ __forceinline__ void rot_corners(const RotBox &b, double (&cx)[4], double (&cy)[4]) {
+  const double hl = b.l * 0.5, hw = b.w * 0.5;
+  const double dx[4] = {hl, -hl, -hl, hl}, dy[4] = {hw, hw, -hw, -hw};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    cx[k] = b.x + (dx[k] * b.c - dy[k] * b.s);
+    cy[k] = b.y + (dx[k] * b.s + dy[k] * b.c);
+  }
+}
+
+// One Sutherland-Hodgman pass in registers: polygon p[0..n) (n <= NIN) against the half-plane left of the
+// edge from (ax,ay) along (ex,ey); inside = cross product >= 0.  A convex polygon gains at most one vertex
+// per pass, so the output holds NIN + 1.  Every array index is a compile-time constant: the append at the
+// running position m is a select over the output slots (a runtime index would put the arrays in scratch).
+template <int NIN>
+__device__ __forceinline__ int clip_pass(const double (&px)[NIN], const double (&py)[NIN], int n, double ax,
+                                         double ay, double ex, double ey, double (&ox)[NIN + 1],
+                                         double (&oy)[NIN + 1]) {
+#pragma unroll
+  for (int k = 0; k <= NIN; ++k) ox[k] = oy[k] = 0.0;
+  double qx = px[0], qy = py[0];  // the last vertex, p[n-1]
+#pragma unroll
+  for (int i = 1; i < NIN; ++i)
+    if (i == n - 1) {
+      qx = px[i];
+      qy = py[i];
+    }
+  double dq = ex * (qy - ay) - ey * (qx - ax);
+  int m = 0;
+#pragma unroll
+  for (int i = 0; i < NIN; ++i) {
+    const bool live = i < n;
+    const double cx = px[i], cy = py[i];
+    const double dc = ex * (cy - ay) - ey * (cx - ax);
+    const bool cross = live && ((dc >= 0.0) != (dq >= 0.0));
+    const bool in = live && dc >= 0.0;
+    const double t = dq / (dq - dc);
+    const double ix = qx + t * (cx - qx), iy = qy + t * (cy - qy);
+#pragma unroll
+    for (int k = 0; k <= NIN; ++k)
+      if (cross && k == m) {
+        ox[k] = ix;
+        oy[k] = iy;
+      }
+    m += (cross && m <= NIN) ? 1 : 0;
+#pragma unroll
+    for (int k = 0; k <= NIN; ++k)
+      if (in && k == m) {
+        ox[k] = cx;
+        oy[k] = cy;
+      }
+    m += (in && m <= NIN) ? 1 : 0;
+    qx = cx;
+    qy = cy;
+    dq = dc;
+  }
+  return m;
+}
+
+// The last pass keeps no polygon: the shoelace sum runs over the vertices as they come out, in the order
+// (v0,v1), (v1,v2), ..., (v_last,v0) of the stored form.  Returns the area; 0 with fewer than 3 vertices.
+template <int NIN>
+__device__ __forceinline__ double clip_pass_area(const double (&px)[NIN], const double (&py)[NIN], int n, double ax,
+                                                 double ay, double ex, double ey) {
+  double qx = px[0], qy = py[0];
+#pragma unroll
+  for (int i = 1; i < NIN; ++i)
+    if (i == n - 1) {
+      qx = px[i];
+      qy = py[i];
+    }
+  double dq = ex * (qy - ay) - ey * (qx - ax);
+  int m = 0;
+  double fx = 0.0, fy = 0.0, lx = 0.0, ly = 0.0, s = 0.0;  // first and latest vertex out, running sum
+  auto emit = [&](bool pred, double vx, double vy) {
+    const double term = lx * vy - vx * ly;
+    if (pred && m > 0) s += term;
+    if (pred && m == 0) {
+      fx = vx;
+      fy = vy;
+    }
+    if (pred) {
+      lx = vx;
+      ly = vy;
+      ++m;
+    }
+  };
+#pragma unroll
+  for (int i = 0; i < NIN; ++i) {
+    const bool live = i < n;
+    const double cx = px[i], cy = py[i];
+    const double dc = ex * (cy - ay) - ey * (cx - ax);
+    const double t = dq / (dq - dc);
+    emit(live && ((dc >= 0.0) != (dq >= 0.0)), qx + t * (cx - qx), qy + t * (cy - qy));
+    emit(live && dc >= 0.0, cx, cy);
+    qx = cx;
+    qy = cy;
+    dq = dc;
+  }
+  if (m < 3) return 0.0;
+  s += lx * fy - fx * ly;
+  return fabs(s) * 0.5;
+}
+
+// BEV IoU of the footprints: a (the kept, higher-scoring box) clipped by the four edges of b, shoelace area,
+// inter / (w_a l_a + w_b l_b - inter); 0 when the union is not finite and > 0.  Both boxes are ok.
+__device__ __forceinline__ double rot_iou(const RotBox &a, const RotBox &b) {
+  double p0x[4], p0y[4], bx[4], by[4];
+  rot_corners(a, p0x, p0y);
+  rot_corners(b, bx, by);
+  double p1x[5], p1y[5], p2x[6], p2y[6], p3x[7], p3y[7];
+  int n = clip_pass<4>(p0x, p0y, 4, bx[0], by[0], bx[1] - bx[0], by[1] - by[0], p1x, p1y);
+  n = clip_pass<5>(p1x, p1y, n, bx[1], by[1], bx[2] - bx[1], by[2] - by[1], p2x, p2y);
+  n = clip_pass<6>(p2x, p2y, n, bx[2], by[2], bx[3] - bx[2], by[3] - by[2], p3x, p3y);
+  const double inter = clip_pass_area<7>(p3x, p3y, n, bx[3], by[3], bx[0] - bx[3], by[0] - by[3]);
+  const double uni = a.w * a.l + b.w * b.l - inter;
+  if (!(isfinite(uni) && uni > 0.0)) return 0.0;
+  return inter / uni;
+}
+
+// The conservative reject: true only when the footprints are disjoint -- the circumscribed circles are
+// apart, or one of the four edge directions separates the rectangles.  Every comparison carries a relative
+// slack of 1e-9, so that rounding cannot reject a touching pair.
+__device__ __forceinline__ bool rot_apart(const RotBox &a, const RotBox &b) {
+  const double slack = 1.0 + 1e-9;
+  const double dx = b.x - a.x, dy = b.y - a.y, rs = a.r + b.r;
+  if (dx * dx + dy * dy > rs * rs * slack) return true;
+  const double hla = a.l * 0.5, hwa = a.w * 0.5, hlb = b.l * 0.5, hwb = b.w * 0.5;
+  const double cd = fabs(a.c * b.c + a.s * b.s), sd = fabs(a.s * b.c - a.c * b.s);
+  return fabs(dx * a.c + dy * a.s) > (hla + (hlb * cd + hwb * sd)) * slack ||
+         fabs(dy * a.c - dx * a.s) > (hwa + (hlb * sd + hwb * cd)) * slack ||
+         fabs(dx * b.c + dy * b.s) > (hlb + (hla * cd + hwa * sd)) * slack ||
+         fabs(dy * b.c - dx * b.s) > (hwb + (hla * sd + hwa * cd)) * slack;
+}
+
+constexpr int kBand = 16;                  // rows of pairs per round of rot_pairs
+constexpr int kWork = kBand * kChunkN;     // its work list: 4096 pairs
+
+// The rotated pair test over rows[0..nr) x cols[0..nc) (TRI: only j > r), for the whole workgroup, in bands
+// of kBand rows and two steps per band, because a clip is about 2000 instructions (counted in the ISA) and few pairs need one:
+//   1. every pair gets the cheap test -- both ok, same class if class-aware, the column still alive, not
+//      rot_apart -- and the pairs that pass are appended to a work list in LDS (one LDS atomic per wave);
+//   2. the threads share the work list evenly: clip, and hit(r, j) where IoU > thresh.
+// Which pairs hit does not depend on the order of the list, so the result is deterministic.
+template <bool TRI, bool CA, class Hit>
+__device__ __forceinline__ void rot_pairs(const RotBox *rows, int nr, const RotBox *cols, int nc,
+                                          const int *col_alive, u64 *merge_buf, double thresh, int t, Hit hit) {
+  // the work list borrows k_nms's merge buffer, which is idle between two merges
+  static_assert(kMaxRuns * kChunkN * sizeof(u64) >= kWork * sizeof(unsigned), "the work list must fit");
+  unsigned *const work = reinterpret_cast<unsigned *>(merge_buf);
+  __shared__ int s_nwork;
+  int *const nwork = &s_nwork;
+  const int lane = t & 63;
+  for (int r0 = 0; r0 < nr; r0 += kBand) {
+    if (t == 0) *nwork = 0;
+    __syncthreads();
+    for (int idx = t; idx < kWork; idx += kNmsThreads) {
+      const int r = r0 + idx / kChunkN, j = idx % kChunkN;
+      bool need = r < nr && j < nc && (!TRI || j > r);
+      if (need && col_alive) need = col_alive[j] != 0;
+      if (need) {
+        const RotBox &a = rows[r], &b = cols[j];
+        need = a.ok && b.ok && (!CA || a.cls == b.cls) && !rot_apart(a, b);
+      }
+      const u64 m = __ballot(need);
+      if (m) {
+        int base = 0;
+        if (lane == 0) base = atomicAdd(nwork, __popcll(m));
+        base = __builtin_amdgcn_readfirstlane(base);
+        const u64 lt = lane ? (~0ull >> (64 - lane)) : 0ull;
+        if (need) work[base + __popcll(m & lt)] = ((unsigned)r << 8) | (unsigned)j;  // <= kWork per band
+      }
+    }
+    __syncthreads();
+    const int n = *nwork;
+    for (int w = t; w < n; w += kNmsThreads) {
+      const unsigned e = work[w];
+      const int r = (int)(e >> 8), j = (int)(e & 255u);
+      if (rot_iou(rows[r], cols[j]) > thresh) hit(r, j);
+    }
+    __syncthreads();
+  }
+}
+
 // One workgroup per sample; chunks of kChunkN = 256 candidates in key order, four threads per candidate.
+// P = AnchorNms<class_aware> or RotatedNms<class_aware>: the record and the pair test; the merge, the
+// packing of the survivors, the greedy walk and the output are the same for all.  LDS with the 64-byte
+// RotBox: kept list 64 KiB, chunk and packed survivors 16 KiB each, masks 8 KiB, merge buffer 16 KiB
+// (rot_pairs' work list lives in it between two merges), ids 7 KiB: 127 KiB of the 160 KiB.
+template <class P>
 __global__ __launch_bounds__(kNmsThreads) void k_nms(DecodeArgs d_) {
+  using NmsBox = typename P::Box;
   const DecodeArgs d = sample_view(d_);
   __shared__ NmsBox s_kept[kMaxOut];
   __shared__ NmsBox s_chunk[kChunkN];
@@ -275,24 +541,28 @@ __global__ __launch_bounds__(kNmsThreads) void k_nms(DecodeArgs d_) {
     }
     const bool valid = key != kSentinel;
     const int a = (int)(key & 0xFFFFFull);
-    NmsBox b = {0, 0, 0, 0, 0};
+    NmsBox b = {};
     int alive = 0;
     if (valid) {
-      b = load_box(d, a);
       alive = 1;
-      // this thread's quarter of the kept list, four boxes per trip: the LDS reads of a trip do
-      // not wait for each other (one at a time the test was a 100 ns round trip per kept box)
-      for (int k0 = sub; k0 < nk; k0 += 16) {
-        bool hit = false;
+      if constexpr (P::kRotated) {
+        if (sub == 0) b = P::load(d, a);  // one decode per candidate and chunk; rot_pairs tests it below
+      } else {
+        b = P::load(d, a);
+        // this thread's quarter of the kept list, four boxes per trip: the LDS reads of a trip do
+        // not wait for each other (one at a time the test was a 100 ns round trip per kept box)
+        for (int k0 = sub; k0 < nk; k0 += 16) {
+          bool hit = false;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int k = k0 + 4 * u;
-          const NmsBox kb = s_kept[min(k, nk - 1)];
-          hit = hit || (k < nk && suppresses(kb, b, d.nms_thresh));
-        }
-        if (hit) {
-          alive = 0;
-          break;
+          for (int u = 0; u < 4; ++u) {
+            const int k = k0 + 4 * u;
+            const NmsBox kb = s_kept[min(k, nk - 1)];
+            hit = hit || (k < nk && P::suppresses(kb, b, d.nms_thresh));
+          }
+          if (hit) {
+            alive = 0;
+            break;
+          }
         }
       }
     }
@@ -310,6 +580,10 @@ __global__ __launch_bounds__(kNmsThreads) void k_nms(DecodeArgs d_) {
     s_mask[c][sub] = 0ull;
     if (t == kNmsThreads - 1) s_full = valid;       // the chunk's last candidate exists
     __syncthreads();
+    if constexpr (P::kRotated) {  // the kept-list test: a hit clears the candidate's flag
+      rot_pairs<false, P::kClassAware>(s_kept, nk, s_chunk, kChunkN, s_alive, s_merge, (double)d.nms_thresh, t,
+                                       [&](int, int j) { s_alive[j] = 0; });
+    }
     // The members the kept list left alive, packed to the front (score order kept): the matrix and the
     // greedy pass then cost what the survivors cost -- 30 to 100 of 256 in all chunks but the first.
     int my_pos = -1;
@@ -329,7 +603,11 @@ __global__ __launch_bounds__(kNmsThreads) void k_nms(DecodeArgs d_) {
     // Suppression matrix among the survivors: bit j of s_mask[r] = (j > r and r suppresses j).  Row r has
     // na - 1 - r entries: rows p and na - 1 - p together have na - 1, shared by eight threads, four
     // entries per trip (all their LDS reads first, then the arithmetic, then the bits).
-    {
+    if constexpr (P::kRotated) {
+      rot_pairs<true, P::kClassAware>(s_cbox, na, s_cbox, na, nullptr, s_merge, (double)d.nms_thresh, t, [&](int r, int j) {
+        atomicOr(&s_mask[r][j >> 6], 1ull << (j & 63));
+      });
+    } else {
       const int p = t >> 3, u = t & 7;
       const int rA = p, rB = na - 1 - p;
       if (rA <= rB) {
@@ -349,13 +627,8 @@ __global__ __launch_bounds__(kNmsThreads) void k_nms(DecodeArgs d_) {
           }
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            NmsBox br;
-            br.x1 = first[q] ? bA.x1 : bB.x1;
-            br.y1 = first[q] ? bA.y1 : bB.y1;
-            br.x2 = first[q] ? bA.x2 : bB.x2;
-            br.y2 = first[q] ? bA.y2 : bB.y2;
-            br.area = first[q] ? bA.area : bB.area;
-            sup[q] = in[q] && suppresses(br, bj[q], d.nms_thresh);
+            const NmsBox br = first[q] ? bA : bB;
+            sup[q] = in[q] && P::suppresses(br, bj[q], d.nms_thresh);
           }
 #pragma unroll
           for (int q = 0; q < 4; ++q)
@@ -434,15 +707,29 @@ using namespace pp;
 constexpr size_t kCounterBytes = 4096;  // one candidate counter per sample at the head of the scratch
 constexpr int kMaxDecodeBatch = (int)(kCounterBytes / 4);
 
-extern "C" int pp_decode_batch_dev(pp_ctx_t *ctx, void *stream_, int32_t batch, const float *cls_dev,
-                                   const float *reg_dev, int64_t cls_stride_b, int64_t cls_stride_c,
-                                   int64_t cls_stride_pix, int64_t reg_stride_b, int64_t reg_stride_c,
-                                   int64_t reg_stride_pix, const double *a_centers, const double *a_wlh,
-                                   const double *a_yaw, const double *a_xy, const pp_decode_params_t *prm,
-                                   double *boxes_out, int32_t *kept_out, int32_t *count_out) {
-  if (!ctx || !cls_dev || !reg_dev || !a_centers || !a_wlh || !a_yaw || !a_xy || !prm || !boxes_out ||
+extern "C" int pp_decode_nms_batch_dev(pp_ctx_t *ctx, void *stream_, int32_t batch, const float *cls_dev,
+                                       const float *reg_dev, int64_t cls_stride_b, int64_t cls_stride_c,
+                                       int64_t cls_stride_pix, int64_t reg_stride_b, int64_t reg_stride_c,
+                                       int64_t reg_stride_pix, const double *a_centers, const double *a_wlh,
+                                       const double *a_yaw, const double *a_xy, const pp_decode_params_t *prm,
+                                       int32_t nms_mode, int32_t class_aware, double *boxes_out,
+                                       int32_t *kept_out, int32_t *count_out) {
+  if (nms_mode != PP_NMS_ANCHOR_RECT && nms_mode != PP_NMS_ROTATED_BEV) {
+    set_error("pp_decode_nms_batch_dev: unknown nms_mode %d", (int)nms_mode);
+    return PP_ERR_VALUE;
+  }
+  if (class_aware != 0 && class_aware != 1) {
+    set_error("pp_decode_nms_batch_dev: class_aware must be 0 or 1, not %d", (int)class_aware);
+    return PP_ERR_VALUE;
+  }
+  const bool rotated = nms_mode == PP_NMS_ROTATED_BEV;
+  if (!ctx || !cls_dev || !reg_dev || !a_centers || !a_wlh || !a_yaw || (!a_xy && !rotated) || !prm || !boxes_out ||
       !kept_out || !count_out) {
     set_error("pp_decode_dev: NULL argument");
+    return PP_ERR_VALUE;
+  }
+  if (rotated && !(std::isfinite(prm->nms_thresh) && prm->nms_thresh >= 0.0)) {
+    set_error("pp_decode_nms_batch_dev: the rotated mode needs a finite nms_thresh >= 0");
     return PP_ERR_VALUE;
   }
   const int64_t A = (int64_t)prm->fm_height * prm->fm_width * prm->anchors_per_cell;
@@ -517,7 +804,15 @@ extern "C" int pp_decode_batch_dev(pp_ctx_t *ctx, void *stream_, int32_t batch, 
   d.run = (int)std::min<size_t>(kRun, cap);
   const unsigned nrun_wgs = (unsigned)std::min<size_t>(kMaxRuns, cap / d.run);
   hipLaunchKernelGGL(k_sort_runs, dim3(nrun_wgs, nb), dim3(kSortThreads), (size_t)d.run * 8, stream, d, d.run);
-  hipLaunchKernelGGL(k_nms, dim3(1, nb), dim3(kNmsThreads), 0, stream, d);  // + box decode
+  // + box decode
+  if (!rotated && !class_aware)
+    hipLaunchKernelGGL(k_nms<AnchorNms<false>>, dim3(1, nb), dim3(kNmsThreads), 0, stream, d);
+  else if (!rotated)
+    hipLaunchKernelGGL(k_nms<AnchorNms<true>>, dim3(1, nb), dim3(kNmsThreads), 0, stream, d);
+  else if (!class_aware)
+    hipLaunchKernelGGL(k_nms<RotatedNms<false>>, dim3(1, nb), dim3(kNmsThreads), 0, stream, d);
+  else
+    hipLaunchKernelGGL(k_nms<RotatedNms<true>>, dim3(1, nb), dim3(kNmsThreads), 0, stream, d);
   {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -528,6 +823,17 @@ extern "C" int pp_decode_batch_dev(pp_ctx_t *ctx, void *stream_, int32_t batch, 
     }
   }
   return PP_OK;
+}
+
+extern "C" int pp_decode_batch_dev(pp_ctx_t *ctx, void *stream_, int32_t batch, const float *cls_dev,
+                                   const float *reg_dev, int64_t cls_stride_b, int64_t cls_stride_c,
+                                   int64_t cls_stride_pix, int64_t reg_stride_b, int64_t reg_stride_c,
+                                   int64_t reg_stride_pix, const double *a_centers, const double *a_wlh,
+                                   const double *a_yaw, const double *a_xy, const pp_decode_params_t *prm,
+                                   double *boxes_out, int32_t *kept_out, int32_t *count_out) {
+  return pp_decode_nms_batch_dev(ctx, stream_, batch, cls_dev, reg_dev, cls_stride_b, cls_stride_c, cls_stride_pix,
+                                 reg_stride_b, reg_stride_c, reg_stride_pix, a_centers, a_wlh, a_yaw, a_xy, prm,
+                                 PP_NMS_ANCHOR_RECT, 0, boxes_out, kept_out, count_out);
 }
 
 extern "C" int pp_decode_strided_dev(pp_ctx_t *ctx, void *stream_, const float *cls_dev,

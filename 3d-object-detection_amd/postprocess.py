@@ -4,8 +4,14 @@ Counterpart of the per-sample tail of ``evaluate()`` (/root/reference
 evaluate.py:231-245): scores/classes, threshold, ``box_nms`` over the anchor
 rectangles, the first 100 survivors decoded by ``make_pred_boxes`` and moved to car
 space.  Returns plain arrays instead of lyft ``Box`` objects.
+
+Two switches go beyond the reference (defaults: the reference's behaviour, bit for bit):
+``nms="rotated"`` suppresses by the f64 bird's-eye-view IoU of the decoded boxes themselves
+instead of the anchor rectangles, ``class_aware=True`` lets a box suppress only boxes of its
+own class (include/pp_hip.h, pp_decode_nms_batch_dev).
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -15,7 +21,14 @@ from . import _lib
 
 class Detector:
     def __init__(self, anchors, anchor_cfg, canvas_height, x_step, y_step, x_min, y_min,
-                 pos_thresh=0.5, nms_thresh=0.1, max_out=100, num_classes=9, device=None):
+                 pos_thresh=0.5, nms_thresh=0.1, max_out=100, num_classes=9, device=None,
+                 nms="anchor", class_aware=False):
+        if nms not in ("anchor", "rotated"):
+            raise ValueError(f"nms must be 'anchor' or 'rotated', not {nms!r}")
+        if nms == "rotated" and not (math.isfinite(nms_thresh) and nms_thresh >= 0):
+            raise ValueError(f"nms='rotated' needs a finite nms_thresh >= 0, not {nms_thresh!r}")
+        self.nms, self.class_aware = nms, bool(class_aware)
+        self._mode = _lib.NMS_ROTATED_BEV if nms == "rotated" else _lib.NMS_ANCHOR_RECT
         if not torch.cuda.is_available():
             raise RuntimeError("Detector needs a HIP device; there is no CPU fallback")
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None
@@ -50,12 +63,12 @@ class Detector:
         kept = torch.empty((B, self.max_out), dtype=torch.int32, device=self.device)
         count = torch.empty((B,), dtype=torch.int32, device=self.device)
         vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        rc = _lib.lib().pp_decode_batch_dev(
+        rc = _lib.lib().pp_decode_nms_batch_dev(
             self._ctx.handle, ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream), B,
             vp(cls), vp(reg), cls.stride(0), cls.stride(1), cls.stride(3), reg.stride(0), reg.stride(1), reg.stride(3),
             vp(self.a_centers), vp(self.a_wlh), vp(self.a_yaw), vp(self.a_xy),
-            ctypes.byref(self._prm), vp(boxes), vp(kept), vp(count))
-        _lib.check(rc, "pp_decode_batch_dev")
+            ctypes.byref(self._prm), self._mode, int(self.class_aware), vp(boxes), vp(kept), vp(count))
+        _lib.check(rc, "pp_decode_nms_batch_dev")
         if batched:
             return boxes, kept, count
         return boxes[0], kept[0], count

@@ -478,6 +478,36 @@ int pp_decode_batch_dev(pp_ctx_t *ctx, void *stream, int32_t batch, const float 
                         const double *a_yaw, const double *a_xy, const pp_decode_params_t *prm,
                         double *boxes_out, int32_t *kept_out, int32_t *count_out);
 
+/* pp_decode_batch_dev with a choice of the suppression rule.  Candidates (score > pos_thresh), their
+ * order (decreasing score, ties by ascending anchor id), the greedy pass, the max_out cap and the
+ * outputs are pp_decode_batch_dev's; nms_mode picks what "overlap" means:
+ *   PP_NMS_ANCHOR_RECT  box_nms (evaluate.py:127-139): f32 IoU of the ANCHOR rectangles a_xy.  With
+ *       class_aware 0 this is pp_decode_batch_dev, bit for bit.
+ *   PP_NMS_ROTATED_BEV  NOT in the reference: the f64 bird's-eye-view IoU of the DECODED boxes -- the
+ *       very rows x,y,z,w,l,h,yaw written to boxes_out (every candidate is decoded by the code that
+ *       writes them).  Footprint as in pp_box3d_iou_dev: centre (x,y), length l along yaw, width w
+ *       across it, corners counter-clockwise.  inter = the kept box's footprint clipped by the four
+ *       edges of the candidate's (f64 Sutherland-Hodgman, inside = cross product >= 0), shoelace area;
+ *       iou = inter / (w_a l_a + w_b l_b - inter).  iou is 0 -- the box is never suppressed and
+ *       suppresses nothing -- when either box has a non-finite x, y, w, l or yaw or w*l not > 0
+ *       (checked before any clipping), or when the union is not finite and > 0.  Pairs whose
+ *       footprints are disjoint by a conservative test (circumscribed circles apart, or a separating
+ *       edge direction, each comparison with a relative slack of 1e-9) are not clipped: iou 0.
+ *       A candidate is dropped iff iou(kept, candidate) > (double)(float)nms_thresh (strict) for an
+ *       already kept box.  a_xy is not read and may be NULL.  nms_thresh must be finite and >= 0.
+ *   class_aware 1 (either mode, not in the reference): a kept box only suppresses candidates with the
+ *       same argmax class.
+ * PP_ERR_VALUE for any other nms_mode or class_aware; limits otherwise as pp_decode_batch_dev. */
+#define PP_NMS_ANCHOR_RECT 0 /* box_nms, evaluate.py:127-139: what pp_decode_*_dev do */
+#define PP_NMS_ROTATED_BEV 1 /* BEV IoU of the decoded boxes (not in the reference)   */
+int pp_decode_nms_batch_dev(pp_ctx_t *ctx, void *stream, int32_t batch, const float *cls_dev,
+                            const float *reg_dev, int64_t cls_stride_b, int64_t cls_stride_c,
+                            int64_t cls_stride_pix, int64_t reg_stride_b, int64_t reg_stride_c,
+                            int64_t reg_stride_pix, const double *a_centers, const double *a_wlh,
+                            const double *a_yaw, const double *a_xy, const pp_decode_params_t *prm,
+                            int32_t nms_mode, int32_t class_aware, double *boxes_out, int32_t *kept_out,
+                            int32_t *count_out);
+
 /*
  * Fused conv epilogue for the inference backbone: y = max(x + b_c, 0) * s_c + t_c in
  * place on a contiguous NCHW f32 tensor -- the ReLU -> BatchNorm2d(eval) tail (plus the
