@@ -17,7 +17,7 @@
 // accumulators (64 registers) per lane.  Input channels stream through LDS in chunks of 16 (one
 // MFMA K-step per tap), double buffered: the global loads of chunk c+1 are in flight during the
 // MFMAs of chunk c (pp_conv_f16_tile.h: the LDS image, its loader and the pipeline, shared with
-// pp_convt_f16.hip).  58.6 KB of LDS: two workgroups per CU.
+// pp_convt_f16.hip and pp_conv_s2_f16.hip).  58.6 KB of LDS: two workgroups per CU.
 //
 // The schedule is fixed (no split-K, no atomics): channel chunks in order, taps in order within a
 // chunk, so results are bit-identical from call to call.

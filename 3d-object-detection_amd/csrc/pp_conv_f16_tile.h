@@ -1,8 +1,9 @@
-// pp_conv_f16_tile.h -- what the fp16-operand MFMA convolutions (pp_conv_f16.hip, pp_convt_f16.hip) share:
+// pp_conv_f16_tile.h -- what the fp16-operand MFMA convolutions (pp_conv_f16.hip, pp_convt_f16.hip,
+// pp_conv_s2_f16.hip) share:
 // the LDS image of one chunk of 16 input channels, the loader that stages it through registers, the
 // double-buffered chunk pipeline, the epilogue constants, and the host-side argument checks and launch.
 // A kernel brings its tile geometry, its MFMA role (which fragments feed which accumulators) and the
-// accumulator-to-pixel mapping of its stores.  Included by those two files only.
+// accumulator-to-pixel mapping of its stores.  Included by those three files only.
 //
 // One LDS buffer (bytes): A[2 half][halo pixel][8 fp16] then B[9 tap][2 half][64 cout][8 fp16]; half h
 // holds channels 8h .. 8h+7 of the chunk.  A lane's A fragment is 8 consecutive channels of one pixel,
@@ -29,19 +30,26 @@ constexpr int kBVecs = 9 * 2 * kCo;          // 16-byte vectors of weights per c
 // s_waitcnt immediate (gfx9 encoding): vmcnt(0), expcnt and lgkmcnt left at their maxima
 constexpr int kWaitVm0 = 0x0F70;
 
-// The input tile of a workgroup of 256 threads: ROWS rows of kTw pixels plus LO / HI halo pixels on the
-// low / high side of both axes.
-template <int ROWS, int LO, int HI>
-struct TileGeo {
-  static constexpr int kRows = ROWS;
-  static constexpr int kHl = LO;                               // halo pixels on the low side
-  static constexpr int kHw = kTw + LO + HI;                    // halo tile width
-  static constexpr int kHalo = kHw * (ROWS + LO + HI);         // halo pixels
+// The halo tile a workgroup of 256 threads stages per chunk: HH rows of HW input pixels.  slot() places
+// halo pixel pix = hy * HW + hx in an A plane, in units of 16 bytes: pixel-linear here; a kernel whose
+// taps step two pixels along a row hides it with a row order of its own (pp_conv_s2_f16.hip).
+template <int HW, int HH>
+struct HaloGeo {
+  static constexpr int kHw = HW;                               // halo tile width
+  static constexpr int kHalo = HW * HH;                        // halo pixels
   static constexpr int kAPlane = kHalo * 16;
   static constexpr int kABytes = 2 * kAPlane;
   static constexpr int kBufBytes = kABytes + kBVecs * 16;
   static constexpr int kItems = 2 * kHalo;                     // (pixel, half) pairs of the halo tile
   static constexpr int kNItem = (kItems + 255) / 256;          // ... per thread, the last round partial
+  __device__ static __forceinline__ int slot(int pix, int /*hy*/, int /*hx*/) { return pix; }
+};
+
+// The input tile of ROWS rows of kTw pixels plus LO / HI halo pixels on the low / high side of both axes.
+template <int ROWS, int LO, int HI>
+struct TileGeo : HaloGeo<kTw + LO + HI, ROWS + LO + HI> {
+  static constexpr int kRows = ROWS;
+  static constexpr int kHl = LO;                               // halo pixels on the low side
 };
 
 // blockIdx.x = (sample * tiles_y + tile row) * tiles_x + tile column
@@ -82,7 +90,7 @@ struct Stager {
       const int iy = iy0 + hy, ix = ix0 + hx;
       xin[k] = i < G::kItems && iy >= 0 && iy < H && ix >= 0 && ix < W;
       xoff[k] = (xin[k] ? (iy * W + ix) * Cin : 0) + 8 * hh;
-      adst[k] = hh * G::kAPlane + pix * 16;
+      adst[k] = hh * G::kAPlane + G::slot(pix, hy, hx) * 16;
     }
   }
 

@@ -165,6 +165,37 @@ def _conv_f16(x, w16, table, cout, out=None, channel_offset=0):
     return _conv3x3_nhwc("pp_conv3x3_f16_nhwc_dev", x, w16, table, cout, out, channel_offset)
 
 
+def _conv_out_size(n):
+    """The output extent of a 3x3, padding-1, stride-2 conv along an axis of ``n`` input pixels."""
+    return (n + 1) // 2
+
+
+def _f16_s2_ok(module, conv, x, out):
+    """The fp16-operand stride-2 kernel takes this layer: the module's ``half_mma_s2`` flag; ``_is_conv3x3`` at
+    stride 2; a dense 16-byte aligned channels-last f32 input, Cin % 16 == 0, Cout % 64 == 0; ``out``, if given,
+    channels-last f32, 16-byte aligned and of the strided conv's output extent."""
+    if not (module.half_mma_s2 and _is_conv3x3(conv, 2) and _is_nhwc(x) and x.dtype == torch.float32
+            and x.data_ptr() % 16 == 0 and x.shape[1] == conv.in_channels and conv.in_channels % 16 == 0
+            and conv.out_channels % 64 == 0):
+        return False
+    return out is None or (_is_nhwc(out) and out.dtype == torch.float32 and out.data_ptr() % 16 == 0
+                           and out.shape[0] == x.shape[0]
+                           and tuple(out.shape[2:]) == (_conv_out_size(x.shape[2]), _conv_out_size(x.shape[3])))
+
+
+def _conv_s2_f16(x, w16, table, cout, out=None, channel_offset=0):
+    """pp_conv3x3_s2_f16_nhwc_dev: Conv2d(3x3, padding 1, stride 2) + bias/ReLU/BatchNorm of ``x`` (NHWC) with fp16
+    operands (``w16`` from ``_f16_filter``) and f32 accumulation, into a new channels-last tensor or into channels
+    [channel_offset, +cout) of the channels-last ``out``."""
+    B, C, H, W = x.shape
+    if out is None:
+        out = torch.empty((B, cout, _conv_out_size(H), _conv_out_size(W)), dtype=torch.float32, device=x.device,
+                          memory_format=torch.channels_last)
+    _call("pp_conv3x3_s2_f16_nhwc_dev", x.device, _vp(x), B, H, W, C, _vp(w16), cout, _vp(table), _vp(out),
+          out.shape[1], int(channel_offset))
+    return out
+
+
 def _convt_f16_filter(w_t):
     """ConvTranspose weight [Cin,Cout,3,3] -> pp_convt3x3_f16_nhwc_dev's layout: ``_f16_filter``'s of the weight
     with its first two axes exchanged, [Cout/64][Cin/16][9][2][64][8], tap 3*kh + kw of ``w_t``, not flipped."""
@@ -336,7 +367,8 @@ class _FusedConv:
         """``bn(relu(conv(x)))`` into a new tensor, or into channels [channel_offset, +Cout) of ``out``: the fp16
         kernel if ``module.half_mma`` and the layer is eligible, else the Winograd kernel if ``module.winograd``
         and the layer is eligible, else (a strided ConvTranspose) the fp16 transposed-conv kernel if
-        ``module.half_mma_up`` and the layer is eligible, else MIOpen's conv (``transposed``: ConvTranspose) and
+        ``module.half_mma_up`` and the layer is eligible, else (a stride-2 conv) the fp16 stride-2 kernel if
+        ``module.half_mma_s2`` and the layer is eligible, else MIOpen's conv (``transposed``: ConvTranspose) and
         the epilogue kernel.
 
         ``defer`` (``out`` is None): a pair ``(tensor, table)`` for a consumer that applies the epilogue as it
@@ -357,6 +389,9 @@ class _FusedConv:
             w16 = self.packed("convt_f16", conv.weight, _convt_f16_filter)
             return done(_convt_f16(x, w16, self.table(conv.bias, bn), conv.out_channels, conv.stride[0],
                                    conv.output_padding[0], out, channel_offset))
+        if not transposed and _f16_s2_ok(module, conv, x, out):
+            w16 = self.packed("f16", conv.weight, _f16_filter)
+            return done(_conv_s2_f16(x, w16, self.table(conv.bias, bn), conv.out_channels, out, channel_offset))
         w = self.packed("nhwc", conv.weight, _nhwc_weight) if _is_nhwc(x) else conv.weight
         if transposed:
             y = F.conv_transpose2d(x, w, None, conv.stride, conv.padding, conv.output_padding)
@@ -625,6 +660,10 @@ class PPDownBlock(nn.Module):
         #: opt-in "fp16 inference" (PPModel.set_inference_precision): those layers with fp16 operands and
         #: f32 accumulation instead (csrc/pp_conv_f16.hip); changes results at the 1e-4 level
         self.half_mma = False
+        #: opt-in, with either fp16 mode (``set_inference_precision(..., strided=True)``): the stride-2 layer that
+        #: opens the block as one fused fp16-operand kernel too (csrc/pp_conv_s2_f16.hip: conv and epilogue in one
+        #: pass, no MIOpen call); where the pillar-driven stem takes down1's first layer, it keeps it, in f32
+        self.half_mma_s2 = False
         self._fused = [_FusedConv() for _ in range(num_layers)]
 
     def stem(self, feats, inds, h, w):
@@ -812,9 +851,11 @@ class PPDetectionHead(nn.Module):
 INFERENCE_PRECISIONS = ("f32", "fp16", "fp16-up")
 
 
-def check_inference_precision(precision):
+def check_inference_precision(precision, strided=False):
     if precision not in INFERENCE_PRECISIONS:
         raise ValueError(f"precision must be one of {INFERENCE_PRECISIONS}, not {precision!r}")
+    if strided and precision == "f32":
+        raise ValueError("strided=True needs precision \"fp16\" or \"fp16-up\": \"f32\" keeps every path in f32")
     return precision
 
 
@@ -833,14 +874,18 @@ class PPModel(nn.Module):
         self.det_head = PPDetectionHead(6 * feature_net_out_channels, class_layer_channels,
                                         reg_layer_channels)
 
-    def set_inference_precision(self, precision):
+    def set_inference_precision(self, precision, strided=False):
         """``"fp16"``: the backbone's stride-1 3x3 layers (down1-3, up1) multiply fp16-rounded operands and
         accumulate in f32 (csrc/pp_conv_f16.hip) in no-grad channels-last inference on the GPU; results move
         at the 1e-4 level.  ``"fp16-up"``: those, and the two strided transposed convolutions (up2, up3) the same
-        way (csrc/pp_convt_f16.hip).  ``"f32"`` (the default): every path in f32.  Activations are f32 in every
-        mode."""
-        check_inference_precision(precision)
+        way (csrc/pp_convt_f16.hip).  ``"f32"`` (the default): every path in f32.  ``strided`` (with ``"fp16"`` or
+        ``"fp16-up"`` only): the stride-2 convolutions that open down1, down2 and down3 the same way too
+        (csrc/pp_conv_s2_f16.hip), except where the pillar-driven stem takes down1's; a call without it clears
+        them.  Activations are f32 in every mode."""
+        check_inference_precision(precision, strided)
         bb = self.backbone
+        for m in (bb.down1, bb.down2, bb.down3):
+            m.half_mma_s2 = bool(strided)
         for m in (bb.down1, bb.down2, bb.down3, bb.up1):
             m.half_mma = precision in ("fp16", "fp16-up")
         for m in (bb.up2, bb.up3):

@@ -18,10 +18,12 @@ from .voxelizer import PillarVoxelizer, VoxelConfig
 class PillarPipeline:
     def __init__(self, vox_cfg: VoxelConfig, anchor_cfg: boxes.AnchorConfig = None,
                  feature_channels=64, num_classes=9, reg_dims=8, device=None, seed=0,
-                 pos_thresh=0.6, with_targets=False, data_mean=None, precision="f32"):
+                 pos_thresh=0.6, with_targets=False, data_mean=None, precision="f32",
+                 strided=False):
         """``precision``: ``PPModel.set_inference_precision`` ("f32", "fp16" for fp16-operand MFMA in the
-        backbone's stride-1 layers at inference, or "fp16-up" for those and the two strided transposed convolutions)."""
-        check_inference_precision(precision)      # before anything is built
+        backbone's stride-1 layers at inference, or "fp16-up" for those and the two strided transposed convolutions);
+        ``strided``: its keyword of the same name (the down blocks' stride-2 convolutions too; not with "f32")."""
+        check_inference_precision(precision, strided)      # before anything is built
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.vox_cfg = vox_cfg
         h, w = vox_cfg.canvas_height, vox_cfg.canvas_width
@@ -33,7 +35,7 @@ class PillarPipeline:
         torch.manual_seed(seed)  # model/model.py:9
         self.model = PPModel(9, feature_channels, anchor_cfg.per_cell * num_classes,
                              anchor_cfg.per_cell * reg_dims, h, w).to(self.device)
-        self.model.set_inference_precision(precision)
+        self.model.set_inference_precision(precision, strided)
         # inference: the head reads the up blocks' outputs where they lie (PPDetectionHead.fused_parts)
         self.model.det_head.fused_parts = True
         self.loss = PPLoss()

@@ -616,6 +616,46 @@ int pp_convt3x3_f16_nhwc_dev(pp_ctx_t *ctx, void *stream, const float *x_dev, in
                              int64_t y_channels, int64_t y_channel_offset);
 
 /*
+ * A 3x3, padding-1, stride-2 convolution of NHWC f32 x[batch][height][width][in_channels], with the same
+ * epilogue and the same arithmetic as pp_conv3x3_f16_nhwc_dev: the layers that open the down blocks in the
+ * opt-in fp16 inference modes (PPModel.set_inference_precision(..., strided=True)).  height and width are
+ * the input's; with Ho = (height+1)/2, Wo = (width+1)/2 and w the Conv2d weight
+ * [out_channels][in_channels][3][3]:
+ *   v[b,oy,ox,co] = sum over kh, kw in {0,1,2} with iy = 2*oy-1+kh in [0,height), ix = 2*ox-1+kw in
+ *                   [0,width), and over ci of half(x[b,iy,ix,ci]) * half(w[co,ci,kh,kw])
+ *   y = max(v + bias_co, 0) * scale_co + shift_co,   params_dev [out_channels][3] f32
+ * Arithmetic, as for pp_conv3x3_f16_nhwc_dev:
+ *   - Each x value is rounded once to IEEE binary16 by the kernel, round to nearest even (never the
+ *     round-toward-zero pkrtz conversion); w_f16_dev holds the weights already rounded that way
+ *     (torch.Tensor.half()).
+ *   - Values beyond the fp16 range become +-inf; fp16 subnormals are kept by both conversions (what the
+ *     matrix unit makes of subnormal operands is not part of this contract, as there).
+ *   - Products are accumulated in f32 on v_mfma_f32_32x32x16_f16, a direct implicit GEMM (M = output
+ *     pixels, N = out_channels, K = 9 * in_channels).
+ *   - The bias, ReLU and BatchNorm epilogue runs in f32.
+ *   - The schedule is fixed: no split-K and no atomics.  Results are bit-identical from call to call.
+ * w_f16_dev is w as fp16 in pp_conv3x3_f16_nhwc_dev's layout [out_channels/64][in_channels/16][9][2][64][8]:
+ * w[co][ci][kh][kw] at element
+ *   (((((co/64)*(in_channels/16) + ci/16)*9 + 3*kh + kw)*2 + (ci/8)%2)*64 + co%64)*8 + ci%8
+ * (the taps are not flipped).
+ * y_dev: channels [y_channel_offset, +out_channels) of rows of y_channels floats per pixel of
+ * [batch][Ho][Wo], every one written exactly once (no zero fill; other channels untouched).
+ * Non-finite operands: the kernel forms the sum over all nine taps and feeds fp16 zeros where the
+ * definition's iy or ix falls outside the image (the top row and left column of taps, and the bottom row /
+ * right column when height / width is odd).  With finite fp16 weights that is the definition exactly.  A
+ * weight that overflowed to +-inf in fp16 gives 0 * inf = NaN at those pixels, where the definition leaves
+ * the tap out; pp_conv3x3_f16_nhwc_dev and pp_convt3x3_f16_nhwc_dev pad with zeros the same way.  Finite
+ * weights are the caller's part of the opt-in.
+ * in_channels a multiple of 16, out_channels a multiple of 64, x, w and y 16-byte aligned,
+ * height*width*in_channels < 2^31.  Arguments are rejected before any HIP call.  One launch: no
+ * allocation, no synchronisation (graph-capturable).
+ */
+int pp_conv3x3_s2_f16_nhwc_dev(pp_ctx_t *ctx, void *stream, const float *x_dev, int batch, int height,
+                               int width, int in_channels, const void *w_f16_dev, int out_channels,
+                               const float *params_dev, float *y_dev, int64_t y_channels,
+                               int64_t y_channel_offset);
+
+/*
  * The backbone's first layer straight from the pillars (inference): PPScatter (model/model.py:53-62)
  * -> 3x3, stride-2, padding-1 convolution -> the epilogue of pp_bias_relu_bn_nhwc_dev,
  *   y = max(conv(canvas) + bias_c, 0) * scale_c + shift_c,
