@@ -81,18 +81,22 @@ __device__ __forceinline__ DecodeArgs sample_view(DecodeArgs d) {
 __device__ __forceinline__ float sigmoidf_ref(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // scores,classes = torch.max(torch.sigmoid(cls), dim=-1)   (evaluate.py:231-235)
+// torch.max propagates NaN: an anchor with a NaN class score has score NaN, which is above no threshold
 __device__ __forceinline__ void anchor_score(const DecodeArgs &d, int a, float &score, int &klass) {
   const int cell = a / d.Ac, k = a - cell * d.Ac;
   const float *p = d.cls + (int64_t)(k * d.C) * d.cls_sc + (int64_t)cell * d.cls_sp;
   score = -1.0f;
   klass = 0;
+  bool poisoned = false;
   for (int c = 0; c < d.C; ++c) {
     const float s = sigmoidf_ref(p[(int64_t)c * d.cls_sc]);
+    poisoned = poisoned || s != s;
     if (s > score) {  // first maximum wins
       score = s;
       klass = c;
     }
   }
+  if (poisoned) score = __int_as_float(0x7FC00000);
 }
 
 __global__ __launch_bounds__(256) void k_score(DecodeArgs d_) {

@@ -442,6 +442,13 @@ int pp_ingest_sweeps_dev(pp_ctx_t *ctx, void *stream, int32_t n_sweeps, const fl
  *       (box_utils.py:111-159; a_xy = the (x1,y1,x2,y2) rows of anchor_xy.pkl)
  *   boxes_out [max_out][9] f64: car-space x,y,z,w,l,h,yaw,score,class (zeros beyond count)
  *   kept_out  [max_out] int32 anchor ids in keep order (-1 beyond count); count_out [1]
+ * Non-finite class logits (all pp_decode_*_dev): the score of an anchor is torch.max over its class
+ * scores, which propagates NaN -- an anchor with a NaN score in ANY class has score NaN, is above no
+ * pos_thresh and is never a candidate, whatever its other classes hold.  A logit of +inf gives the score
+ * exactly 1.0f (as does every finite logit from about 17 up) and is a candidate like any other; -inf and
+ * every logit whose sigmoid rounds to zero give the score 0, a candidate only for a negative pos_thresh.
+ * Candidates are taken in decreasing score order, equal scores (bit for bit) by ascending anchor id; of
+ * several classes with the same maximal score the lowest index is reported.
  */
 typedef struct pp_decode_params {
   int32_t fm_height, fm_width, anchors_per_cell, num_classes;

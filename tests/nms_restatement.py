@@ -1,7 +1,8 @@
 """Plain numpy / f64 restatement of pp_decode_nms_batch_dev (include/pp_hip.h) -- the yardstick of
-tests/test_gpu_nms_rotated.py.  Not a test module.
+tests/test_gpu_nms_rotated.py and tests/test_gpu_decode_paths.py.  Not a test module.
 
-  candidates  anchors with score > pos_thresh, decreasing score, ties by ascending anchor id; every one
+  candidates  anchors with score > pos_thresh, decreasing score, ties by ascending anchor id (the score is
+              the maximum over the classes, NaN if any class score is NaN: no candidate); every one
               is decoded as oracle.postprocess decodes its kept ones (make_pred_boxes +
               move_box_to_car_space, f32 exp / tanh / arcsin, the rest f64);
   rotated     iou(a, b) = inter / (w_a l_a + w_b l_b - inter), inter = eval_restatement's

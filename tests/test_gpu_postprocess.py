@@ -112,8 +112,9 @@ def test_postprocess_on_channels_last_slices(gpu, oracle):
 def test_postprocess_low_score_thresholds(gpu, oracle, fm, bias, thresh):
     """Scores at or below 0.25 need more than 24 bits of the key's score field: the candidates
     must still come out in decreasing score order (the first release sorted 44 of the
-    50 key bits and mis-ordered them).  The (120, -1.0, 0.01) case has > 2048 candidates: the
-    in-place global-memory sort."""
+    50 key bits and mis-ordered them).  The (120, -1.0, 0.01) case has thousands of candidates (of A = 28800
+    anchors: at most two sorted runs); every sort path, the in-place global-memory sort for more than
+    131072 candidates included, is covered by tests/test_gpu_decode_paths.py."""
     import torch
     from pp_amd.postprocess import Detector
     anchors, acfg, cls, reg, H, _ = _setup(gpu, fm, 11, bias)
