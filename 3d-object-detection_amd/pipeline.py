@@ -6,9 +6,11 @@ the loss: ``PPDataset.__getitem__``'s voxel stage and target stage
 (train.py:144-145, evaluate.py:228) on PyTorch-ROCm.  Nothing crosses PCIe
 except the raw points (0.96 MB per 60k-point sweep) and the boxes.
 """
+import numpy as np
 import torch
 
 from . import boxes
+from .augment import Augmenter, draw
 from .loss import PPLoss
 from .model import PPModel, check_inference_precision
 from .targets import TargetAssigner
@@ -19,8 +21,10 @@ class PillarPipeline:
     def __init__(self, vox_cfg: VoxelConfig, anchor_cfg: boxes.AnchorConfig = None,
                  feature_channels=64, num_classes=9, reg_dims=8, device=None, seed=0,
                  pos_thresh=0.6, with_targets=False, data_mean=None, precision="f32",
-                 strided=False):
-        """``precision``: ``PPModel.set_inference_precision`` ("f32", "fp16" for fp16-operand MFMA in the
+                 strided=False, augment=None):
+        """``augment``: an ``augment.AugmentConfig`` -- ``train_forward_backward(..., augment_rng=rng)`` then augments
+        the points and the boxes on the device before the voxelizer and the assigner (needs ``with_targets``).
+        ``precision``: ``PPModel.set_inference_precision`` ("f32", "fp16" for fp16-operand MFMA in the
         backbone's stride-1 layers at inference, or "fp16-up" for those and the two strided transposed convolutions);
         ``strided``: its keyword of the same name (the down blocks' stride-2 convolutions too; not with "f32")."""
         check_inference_precision(precision, strided)      # before anything is built
@@ -45,6 +49,11 @@ class PillarPipeline:
             self.assigner = TargetAssigner(anchor_cfg, canvas_height=h,
                                            pos_thresh=pos_thresh, num_classes=num_classes,
                                            device=self.device)
+        self.augmenter = None
+        if augment is not None:
+            if self.assigner is None:
+                raise ValueError("augment needs with_targets=True: it feeds the target assigner")
+            self.augmenter = Augmenter(vox_cfg, augment, device=self.device)
         self._bufs = None
         self._fbufs = None
         self._cbuf = None
@@ -207,13 +216,22 @@ class PillarPipeline:
         ``train_forward_backward`` consume."""
         return self.assigner.upload_batch(gts)
 
-    def train_forward_backward(self, points, gts, n_points=None, shard_ctx=None):
+    def train_forward_backward(self, points, gts, n_points=None, shard_ctx=None, augment_rng=None):
         """train.py:139-147 without the optimizer: voxel stage, target stage, forward,
         loss, backward.  ``gts`` is a list (one per sweep) of dicts with
         centers / wlh / yaw / classes in canvas space.  With a multi-rank ``shard_ctx`` the
         back-propagated loss is ``shard.global_batch_loss`` (this rank's share of the ONE loss
         the reference computes over the gathered batch); the returned scalars stay the local
-        PPLoss values."""
+        PPLoss values.  With an ``augment`` config at construction, a ``numpy.random.Generator`` as ``augment_rng``
+        and ``gts`` as a list of dicts, the step trains on an augmented copy of the points and the boxes
+        (``augment.Augmenter``: the draws on the host, one upload, two launches); every other call is untouched."""
+        if (self.augmenter is not None and augment_rng is not None and not isinstance(gts, tuple)
+                and all(isinstance(g, dict) for g in gts)):
+            if points.dim() == 2:
+                points = points.unsqueeze(0)
+            counts = [int(np.asarray(g["yaw"]).reshape(-1).shape[0]) for g in gts]
+            g_counts, packed = self.augmenter.upload_batch(gts, draw(self.augmenter.cfg, augment_rng, counts))
+            points, gts, _, _ = self.augmenter.apply(points.contiguous(), n_points, g_counts, packed)
         pillars, indices = self.voxelize(points, n_points)
         if isinstance(gts, tuple) and len(gts) == 2 and torch.is_tensor(gts[1]):
             cls_t, reg_t = self.assigner.assign_batch_device(*gts)

@@ -818,6 +818,83 @@ int pp_eval_match_batch_dev(pp_ctx_t *ctx, void *stream, int32_t batch, const do
                             uint16_t *tp_mask_out, double *max_iou_out, int32_t *argmax_out,
                             int32_t *gt_per_class_out);
 
+/*
+ * Training augmentation of the points and the ground-truth boxes of a batch (the
+ * reference has none): the global flip / rotation / scale / translation and the per-object noise of
+ * SECOND / PointPillars, where every box and the points inside it get a small rigid motion that is
+ * rejected if it collides with another box.  The HOST draws every random number; there is no RNG on the
+ * device.  Two launches on `stream` (k_aug_boxes, k_aug_points), ordered by the launch boundary alone;
+ * no allocation, no synchronisation.  All geometry is f64, every product and sum rounded separately.
+ * The augmentation works in car space (metres), where the points live; the boxes come in and go out in
+ * canvas space: x = cx*x_step + x_min, y = cy*y_step + y_min, z = cz, w_car = w*y_step, l_car = l*x_step,
+ * h, yaw unchanged (evaluate.gt_to_car_space), and the inverse on the way out.
+ *
+ * Inputs (device memory unless marked HOST):
+ *   batch          1..PP_MAX_BATCH samples
+ *   points_dev     [batch][points_stride][4] f32 (x, y, z, reflectance), 16-byte aligned
+ *   n_points       HOST [batch]: rows at or beyond n_points[b] are neither read nor written
+ *   g_counts       HOST [batch]: boxes per sample, 0..1024 each (a sample's footprints live in LDS);
+ *                  the samples' boxes are concatenated in sample order, T = their sum
+ *   g_centers_dev [T][3]  g_wlh_dev [T][3]  g_yaw_dev [T]   f64, canvas space
+ *   noise_dev      [T][tries][6] f64: {dx, dy, dz, dpsi, cos(dpsi), sin(dpsi)} (metres, radians)
+ *   global_dev     [batch][10] f64: {fx, fy, theta, cos(theta), sin(theta), s, tx, ty, tz, 0},
+ *                  fx, fy in {+1.0, -1.0}
+ *   prm            the grid scalars of the voxelizer and `tries` (1..64)
+ *
+ * Boxes, one workgroup per sample.  The footprint of a pose (x, y, w, l, yaw) is the rectangle of
+ * Box.bottom_corners: length l along the yaw direction, width w across it.  cur[i] starts as the
+ * car-space pose of every box.  For j ascending, for k = 0..tries-1: the candidate is
+ * (c_j + (dx,dy,dz), yaw_j + dpsi) of noise[j][k]; it collides unless, for every i != j, it and cur[i]
+ * are separated along one of the four edge directions (projection intervals strictly disjoint; touching
+ * collides; a candidate with a non-finite component collides).  The first candidate that does not collide
+ * is taken: cur[j] = candidate, sel[j] = k; if every try collides, sel[j] = -1 and cur[j] stays.  Later
+ * boxes are tested against the updated cur[].  Then every cur[j] goes through the global transform: the
+ * centre as a point (below), wlh' = s*wlh, yaw' = theta + yaw for (fx,fy) = (+,+), theta - yaw for (+,-),
+ * theta + pi - yaw for (-,+), theta + pi + yaw for (-,-); yaw is not wrapped.  keep[j] = 1 iff the new
+ * car-space centre lies in [x_min,x_max] x [y_min,y_max] x [z_min,z_max], bounds included
+ * (utils/box_utils.py:265-267).  A box with keep 0 is PARKED: its canvas-space centre is written as
+ * (-1e6, -1e6, z'), so its IoU with every anchor is 0, the target kernels drop it as create_target's
+ * np.nonzero(top_anchor_for_box) filter does, and g_counts stays what it was.
+ *
+ * Points.  A row whose x is NaN (a point pp_ingest_dev removed) is copied unchanged.  Otherwise, with
+ * x, y, z as f64: the owner is the lowest j whose ORIGINAL box contains the point -- ux = x-cx, uy = y-cy,
+ * lx = c*ux + s*uy, ly = -s*ux + c*uy, lz = z-cz, inside iff |lx| <= l/2, |ly| <= w/2, |lz| <= h/2 (c, s of
+ * the original yaw, computed on the device).  With an owner and sel[j] = k >= 0:
+ *   x1 = (cd*ux - sd*uy) + (cx + dx),  y1 = (sd*ux + cd*uy) + (cy + dy),  z1 = z + dz
+ * (cd, sd, dx, dy, dz of noise[j][k]); otherwise x1, y1, z1 = x, y, z.  Then, with xf = fx*x1, yf = fy*y1:
+ *   x2 = s*(ct*xf - st*yf) + tx,  y2 = s*(st*xf + ct*yf) + ty,  z2 = s*z1 + tz
+ * each rounded to f32 once; the reflectance is copied bit for bit.  The moved coordinates use only
+ * host-supplied cosines and sines, so an f64 restatement reproduces them bit for bit.
+ *
+ * Outputs, the five arrays pp_assign_targets_batch_dev reads plus two flags per box:
+ *   points_out_dev      [batch][points_stride][4] f32; may alias points_dev
+ *   corners_out_dev [T][4][2]  centers_img_out_dev [T][3]  centers_out_dev [T][3]  wlh_out_dev [T][3]
+ *   yaw_out_dev [T]     f64, canvas space; corners and image-space centres as boxes_to_image_space
+ *                       (utils/box_utils.py:19-32): the bottom corners, then (canvas_height-1) - y.
+ *                       They must not alias the box inputs (the points read the originals).
+ *   sel_out_dev [T]  keep_out_dev [T]  int32
+ * The classes are not touched: the caller hands the same class array on.
+ * Limits (PP_ERR_VALUE beyond, checked before any HIP call): 1 <= batch <= PP_MAX_BATCH, 0..1024 boxes
+ * per sample, 1 <= tries <= 64, 0 <= n_points[b] <= points_stride, positive finite steps.
+ */
+typedef struct pp_augment_params {
+  double x_step, y_step;            /* cfg.DATA.X_STEP / Y_STEP, config.py:46-47         */
+  double x_min, y_min, z_min;       /* the range filter and the canvas frame              */
+  double x_max, y_max, z_max;
+  double canvas_height;             /* cfg.DATA.CANVAS_HEIGHT, config.py:60               */
+  int32_t tries;                    /* candidate motions per box                          */
+  int32_t reserved;
+} pp_augment_params_t;
+
+int pp_augment_batch_dev(pp_ctx_t *ctx, void *stream, int32_t batch, const float *points_dev,
+                         int64_t points_stride, const int32_t *n_points, const int32_t *g_counts,
+                         const double *g_centers_dev, const double *g_wlh_dev, const double *g_yaw_dev,
+                         const double *noise_dev, const double *global_dev,
+                         const pp_augment_params_t *prm, float *points_out_dev,
+                         double *corners_out_dev, double *centers_img_out_dev, double *centers_out_dev,
+                         double *wlh_out_dev, double *yaw_out_dev, int32_t *sel_out_dev,
+                         int32_t *keep_out_dev);
+
 /* Timing hooks for bench.py: with a ring of `slots` HIP event pairs per kernel
  * (slots = 0 disables), every pp_voxelize*_dev call brackets each of its three launches
  * (PP_KERNEL_SPLIT, PP_KERNEL_TILE, PP_KERNEL_EMIT) with an event pair bound to the dispatch
