@@ -12,8 +12,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("PP_HIP_LIB") or os.path.join(_HERE, "libpp_hip.so")
 SOURCES = [os.path.join(_HERE, "csrc", f)
-           for f in ("pp_runtime.hip", "pp_voxelize.hip", "pp_iou.hip", "pp_ingest.hip", "pp_decode.hip", "pp_epilogue.hip", "pp_pfn.hip", "pp_pfn_train.hip", "pp_bn_train.hip", "pp_eval.hip", "pp_wino.hip", "pp_conv_f16.hip", "pp_convt_f16.hip", "pp_conv_s2_f16.hip", "pp_stem.hip", "pp_head.hip", "pp_augment.hip")]
+           for f in ("pp_runtime.hip", "pp_voxelize.hip", "pp_iou.hip", "pp_ingest.hip", "pp_decode.hip", "pp_epilogue.hip", "pp_pfn.hip", "pp_pfn_train.hip", "pp_bn_train.hip", "pp_eval.hip", "pp_wino.hip", "pp_conv_f16.hip", "pp_convt_f16.hip", "pp_conv_s2_f16.hip", "pp_stem.hip", "pp_head.hip", "pp_augment.hip", "pp_paste.hip")]
 HEADERS = [os.path.join(_HERE, "csrc", "pp_common.h"), os.path.join(_HERE, "csrc", "pp_conv_f16_tile.h"),
+           os.path.join(_HERE, "csrc", "pp_box_geom.h"),
            os.path.join(_ROOT, "include", "pp_hip.h")]
 
 PP_OK, PP_ERR_INDEX, PP_ERR_VALUE, PP_ERR_WINDING = 0, -2, -3, -4
@@ -30,7 +31,7 @@ EXPORTS = [
     "pp_voxelize_reserve", "pp_voxelize_dev", "pp_voxelize_step_dev", "pp_voxelize_step_pfn_canvas_dev", "pp_voxelize_step_kernel_name", "pp_voxelize_step_reset", "pp_subtract_mean_dev", "pp_voxelize_pfn_dev", "pp_voxelize_pfn_canvas_dev", "pp_voxelize_pfn_canvas_reuse_dev", "pp_pfn_dense_dev", "pp_scatter_canvas_dev", "pp_pfn_train_stats_dev", "pp_pfn_train_backward_dev", "pp_create_pillars_f64", "pp_make_ious_f64",
     "pp_iou_check", "pp_make_ious_dev", "pp_assign_targets_dev", "pp_assign_targets_grid_dev", "pp_assign_targets_batch_dev", "pp_assign_targets_grid_batch_dev", "pp_ingest_dev", "pp_ingest_sweeps_dev", "pp_decode_dev", "pp_decode_strided_dev", "pp_decode_batch_dev", "pp_decode_nms_batch_dev", "pp_bias_relu_bn_dev", "pp_bias_relu_bn_nhwc_dev", "pp_conv3x3_wino_nhwc_dev", "pp_conv3x3_f16_nhwc_dev", "pp_convt3x3_f16_nhwc_dev", "pp_conv3x3_s2_f16_nhwc_dev", "pp_conv3x3_s2_pillars_nhwc_dev", "pp_head1x1_nhwc_dev", "pp_relu_bn_train_fwd_dev", "pp_relu_bn_train_bwd_dev", "pp_ctx_set_timing",
     "pp_ctx_read_emit_ms", "pp_ctx_read_kernel_ms", "pp_voxelize_check", "pp_host_pool_selftest",
-    "pp_box3d_iou_dev", "pp_eval_match_batch_dev", "pp_augment_batch_dev",
+    "pp_box3d_iou_dev", "pp_eval_match_batch_dev", "pp_augment_batch_dev", "pp_paste_batch_dev",
 ]
 
 
@@ -83,6 +84,16 @@ class AugmentParams(ctypes.Structure):
                 ("x_max", ctypes.c_double), ("y_max", ctypes.c_double), ("z_max", ctypes.c_double),
                 ("canvas_height", ctypes.c_double),
                 ("tries", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+MAX_PASTE_CANDIDATES = 256  # pp_paste_batch_dev: candidates per sample
+
+
+class PasteParams(ctypes.Structure):
+    """pp_paste_params_t: the canvas -> car scalars and whether accepted objects clear the scene points under them."""
+    _fields_ = [("x_step", ctypes.c_double), ("y_step", ctypes.c_double),
+                ("x_min", ctypes.c_double), ("y_min", ctypes.c_double),
+                ("remove_scene_points", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 def _compile(out, defines=(), force=False, verbose=False):
@@ -276,6 +287,8 @@ def _load(path):
                                           ctypes.POINTER(EvalParams), vp, vp, vp, vp]
     L.pp_augment_batch_dev.argtypes = [vp, vp, ctypes.c_int32, vp, i64, pi32, pi32, vp, vp, vp, vp, vp,
                                        ctypes.POINTER(AugmentParams), vp, vp, vp, vp, vp, vp, vp, vp]
+    L.pp_paste_batch_dev.argtypes = [vp, vp, ctypes.c_int32, vp, i64, pi32, pi32, pi32, vp, vp, vp, vp, i64, vp,
+                                     ctypes.POINTER(PasteParams), vp, i64, pi32, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("pp_last_error", "pp_version", "pp_ctx_destroy"):

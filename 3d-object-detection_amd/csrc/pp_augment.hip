@@ -25,14 +25,14 @@
 
 #pragma clang fp contract(off)
 
+#include "pp_box_geom.h"  // Rect, rects_separated, OwnerBox, kAugMaxBoxes, kAugParked
+
 namespace pp {
 
-constexpr int kAugMaxBoxes = 1024;   // boxes per sample: their footprints live in LDS
 constexpr int kAugMaxTries = 64;     // one bit per try in a lane's collision mask
 constexpr int kAugBoxThreads = 256;  // k_aug_boxes
 constexpr int kAugPtThreads = 256;   // k_aug_points
 constexpr int kAugPtPerThread = 4;   // ... points per thread: a workgroup stages the table once per 1024 points
-constexpr double kAugParked = -1e6;  // canvas-space x, y of a box outside the range
 constexpr double kAugPi = 3.14159265358979323846;
 
 struct AugArgs {
@@ -49,23 +49,6 @@ struct AugArgs {
   int g_off[PP_MAX_BATCH + 1];
   int n_points[PP_MAX_BATCH];
 };
-
-// A footprint in LDS: centre, half length (along the yaw direction), half width, cosine and sine of the yaw.
-struct Rect {
-  double x, y, hl, hw, c, s;
-};
-
-// The largest separation of two rectangles over their four edge directions: > 0 iff the projection
-// intervals are strictly disjoint along one of them.  NaN compares false: it collides.
-__device__ __forceinline__ bool rects_separated(const Rect &a, const Rect &b) {
-  const double dx = b.x - a.x, dy = b.y - a.y;
-  const double cc = fabs(a.c * b.c + a.s * b.s), ss = fabs(a.c * b.s - a.s * b.c);
-  const double s1 = fabs(dx * a.c + dy * a.s) - (a.hl + (b.hl * cc + b.hw * ss));
-  const double s2 = fabs(dy * a.c - dx * a.s) - (a.hw + (b.hl * ss + b.hw * cc));
-  const double s3 = fabs(dx * b.c + dy * b.s) - (b.hl + (a.hl * cc + a.hw * ss));
-  const double s4 = fabs(dy * b.c - dx * b.s) - (b.hw + (a.hl * ss + a.hw * cc));
-  return s1 > 0.0 || s2 > 0.0 || s3 > 0.0 || s4 > 0.0;
-}
 
 __global__ __launch_bounds__(kAugBoxThreads) void k_aug_boxes(const AugArgs d) {
   __shared__ Rect cur[kAugMaxBoxes];
@@ -196,11 +179,6 @@ __global__ __launch_bounds__(kAugBoxThreads) void k_aug_boxes(const AugArgs d) {
     d.o_centers_img[3 * r + 2] = z2;
   }
 }
-
-// One row of the staged table of k_aug_points: an ORIGINAL box in car space.
-struct OwnerBox {
-  double x, y, z, hl, hw, hh, c, s;
-};
 
 __global__ __launch_bounds__(kAugPtThreads) void k_aug_points(const AugArgs d) {
   extern __shared__ double aug_lds[];  // [G] OwnerBox

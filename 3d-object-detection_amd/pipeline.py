@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import boxes
-from .augment import Augmenter, draw
+from .augment import Augmenter, Paster, draw, draw_paste, extend_gts
 from .loss import PPLoss
 from .model import PPModel, check_inference_precision
 from .targets import TargetAssigner
@@ -21,13 +21,17 @@ class PillarPipeline:
     def __init__(self, vox_cfg: VoxelConfig, anchor_cfg: boxes.AnchorConfig = None,
                  feature_channels=64, num_classes=9, reg_dims=8, device=None, seed=0,
                  pos_thresh=0.6, with_targets=False, data_mean=None, precision="f32",
-                 strided=False, augment=None):
+                 strided=False, augment=None, paste=None):
         """``augment``: an ``augment.AugmentConfig`` -- ``train_forward_backward(..., augment_rng=rng)`` then augments
         the points and the boxes on the device before the voxelizer and the assigner (needs ``with_targets``).
+        ``paste``: ``(augment.GtBank, augment.PasteConfig)`` -- ground-truth sampling before that augmentation, so
+        pasted objects get the per-object noise and the global transform like native ones (needs ``augment``; for
+        pasting alone pass ``AugmentConfig.identity()``).
         ``precision``: ``PPModel.set_inference_precision`` ("f32", "fp16" for fp16-operand MFMA in the
         backbone's stride-1 layers at inference, or "fp16-up" for those and the two strided transposed convolutions);
         ``strided``: its keyword of the same name (the down blocks' stride-2 convolutions too; not with "f32")."""
         check_inference_precision(precision, strided)      # before anything is built
+        self.check_paste_argument(paste, augment)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.vox_cfg = vox_cfg
         h, w = vox_cfg.canvas_height, vox_cfg.canvas_width
@@ -54,6 +58,9 @@ class PillarPipeline:
             if self.assigner is None:
                 raise ValueError("augment needs with_targets=True: it feeds the target assigner")
             self.augmenter = Augmenter(vox_cfg, augment, device=self.device)
+        self.paster = None
+        if paste is not None:
+            self.paster = Paster(vox_cfg, paste[0], paste[1], device=self.device)
         self._bufs = None
         self._fbufs = None
         self._cbuf = None
@@ -61,6 +68,18 @@ class PillarPipeline:
         self._canvas_key = None
         #: forward_fused also fuses PPScatter and runs the backbone channels-last
         self.fused_scatter = True
+
+    @staticmethod
+    def check_paste_argument(paste, augment):
+        """The constructor's check of ``paste``, before any device is touched."""
+        if paste is None:
+            return
+        if augment is None:
+            raise ValueError("paste needs augment: the pasted boxes go through the augmenter "
+                             "(for pasting alone pass AugmentConfig.identity())")
+        if not isinstance(paste, (tuple, list)) or len(paste) != 2:
+            raise ValueError("paste: a (GtBank, PasteConfig) pair")
+        paste[1].validate()
 
     def _buffers(self, batch):
         cfg = self.vox_cfg
@@ -224,14 +243,23 @@ class PillarPipeline:
         the reference computes over the gathered batch); the returned scalars stay the local
         PPLoss values.  With an ``augment`` config at construction, a ``numpy.random.Generator`` as ``augment_rng``
         and ``gts`` as a list of dicts, the step trains on an augmented copy of the points and the boxes
-        (``augment.Augmenter``: the draws on the host, one upload, two launches); every other call is untouched."""
+        (``augment.Augmenter``: the draws on the host, one upload, two launches); with ``paste`` too, bank objects
+        are pasted first (``augment.Paster``); every other call is untouched."""
         if (self.augmenter is not None and augment_rng is not None and not isinstance(gts, tuple)
                 and all(isinstance(g, dict) for g in gts)):
             if points.dim() == 2:
                 points = points.unsqueeze(0)
+            if self.paster is not None:
+                ids = draw_paste(self.paster.cfg, augment_rng, self.paster.bank, gts)
+                gts, c_counts = extend_gts(self.paster.bank, gts, ids)
             counts = [int(np.asarray(g["yaw"]).reshape(-1).shape[0]) for g in gts]
             g_counts, packed = self.augmenter.upload_batch(gts, draw(self.augmenter.cfg, augment_rng, counts))
-            points, gts, _, _ = self.augmenter.apply(points.contiguous(), n_points, g_counts, packed)
+            points = points.contiguous()
+            if self.paster is not None:
+                points, n_points, _ = self.paster.apply(points, n_points, (g_counts, packed), c_counts, ids)
+            # the pasted cloud is this step's own buffer: augment it in place
+            points, gts, _, _ = self.augmenter.apply(points, n_points, g_counts, packed,
+                                                     out=points if self.paster is not None else None)
         pillars, indices = self.voxelize(points, n_points)
         if isinstance(gts, tuple) and len(gts) == 2 and torch.is_tensor(gts[1]):
             cls_t, reg_t = self.assigner.assign_batch_device(*gts)

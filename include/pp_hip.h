@@ -895,6 +895,71 @@ int pp_augment_batch_dev(pp_ctx_t *ctx, void *stream, int32_t batch, const float
                          double *wlh_out_dev, double *yaw_out_dev, int32_t *sel_out_dev,
                          int32_t *keep_out_dev);
 
+/*
+ * Ground-truth sampling ("object pasting") of SECOND / PointPillars for a batch (the
+ * reference has no augmentation): objects recorded in a bank -- their points in car space, their boxes in
+ * canvas space -- are pasted into the samples where they fit.  The HOST draws which bank objects to try and
+ * appends their boxes to each sample's ground truth; the device decides which fit, copies their points in
+ * and removes the scene points underneath.  Two launches on `stream` (k_paste_boxes, k_paste_points),
+ * ordered by the launch boundary alone; no allocation, no synchronisation, no atomics.  All geometry is
+ * f64, every product and sum rounded separately; canvas -> car as for pp_augment_batch_dev.
+ *
+ * Inputs (device memory unless marked HOST):
+ *   batch          1..PP_MAX_BATCH samples
+ *   points_dev     [batch][points_stride][4] f32 (x, y, z, reflectance), 16-byte aligned
+ *   n_points       HOST [batch]: the scene rows of each sample, 0..points_stride
+ *   g_counts       HOST [batch]: boxes per sample, originals AND candidates, 0..1024; the samples' boxes
+ *                  are concatenated in sample order
+ *   c_counts       HOST [batch]: the LAST c_counts[b] boxes of sample b are its candidates, in try order;
+ *                  0..256 and at most g_counts[b].  S = their sum
+ *   g_centers_dev [T][3] (in/out)  g_wlh_dev [T][3]  g_yaw_dev [T]   f64, canvas space
+ *   bank_points_dev [bank_rows][4] f32, car space, 16-byte aligned
+ *   table_dev      [S][3] int32, the samples' candidates concatenated: {first bank row, rows, first
+ *                  output row}.  A sample's entries ascend in their first output row (augment.paste_table
+ *                  builds them contiguous from n_points[b])
+ *   n_out          HOST [batch]: output rows per sample, n_points[b]..out_stride
+ *
+ * Boxes, one workgroup per sample.  The footprint of a box is that of pp_augment_batch_dev, with cos and
+ * sin of the yaw computed on the device.  For k ascending, candidate k is ACCEPTED iff its x, y, z, w, l and
+ * yaw are finite, its footprint is separated from the footprint of every original box of the sample, and
+ * from that of every candidate accepted before it.  Separated: projection intervals strictly disjoint
+ * along one of the four edge directions; touching collides; an original whose x, y, z, w, l or yaw is not
+ * finite collides with every candidate.  A candidate that was rejected stands in nobody's way.
+ * accept_out_dev[k] = 1 or 0.  A rejected candidate is PARKED: x and y of its canvas-space centre are
+ * overwritten with -1e6 (its z, wlh and yaw stay), so the target kernels drop it and g_counts stays what
+ * it was.  Nothing else of the box arrays is written.
+ *
+ * Points.  Scene rows p < n_points[b] are copied bit for bit; with remove_scene_points = 1, a row whose x
+ * is not NaN and that lies inside an ACCEPTED candidate's box (the point-in-box test of
+ * pp_augment_batch_dev: f64, bounds included) is copied with x replaced by the f32 quiet NaN 0x7FC00000,
+ * the mark of a removed point; its y, z and reflectance stay.  Rows n_points[b] <= p < n_out[b] belong to
+ * the candidates: row first_out + i (0 <= i < rows) receives bank row first_bank + i bit for bit if the
+ * candidate was accepted, and with x replaced by 0x7FC00000 if it was rejected.  The candidate of a row is
+ * the last table entry of the sample whose first output row is at or before it; an entry with 0 rows owns
+ * none.  Rows at or beyond n_out[b] are neither read nor written.  A table entry is never followed outside
+ * its arrays: a row whose bank row would be negative or at or beyond bank_rows, or that no entry covers, is
+ * skipped (left unwritten); no row below n_points[b] or at or beyond n_out[b] is written for it.
+ *
+ * Outputs:
+ *   points_out_dev  [batch][out_stride][4] f32; may be points_dev itself when out_stride == points_stride
+ *   accept_out_dev  [S] int32
+ * S = 0 is legal: the call copies the scene rows.
+ * Limits (PP_ERR_VALUE beyond, checked before any HIP call): NULL arguments, 1 <= batch <= PP_MAX_BATCH,
+ * 0 <= g_counts[b] <= 1024, 0 <= c_counts[b] <= min(256, g_counts[b]), 0 <= n_points[b] <= points_stride,
+ * n_points[b] <= n_out[b] <= out_stride, positive finite steps, remove_scene_points in {0, 1}.
+ */
+typedef struct pp_paste_params {
+  double x_step, y_step, x_min, y_min;     /* canvas -> car, as pp_augment_params_t */
+  int32_t remove_scene_points, reserved;
+} pp_paste_params_t;
+
+int pp_paste_batch_dev(pp_ctx_t *ctx, void *stream, int32_t batch, const float *points_dev,
+                       int64_t points_stride, const int32_t *n_points, const int32_t *g_counts,
+                       const int32_t *c_counts, double *g_centers_dev, const double *g_wlh_dev,
+                       const double *g_yaw_dev, const float *bank_points_dev, int64_t bank_rows,
+                       const int32_t *table_dev, const pp_paste_params_t *prm, float *points_out_dev,
+                       int64_t out_stride, const int32_t *n_out, int32_t *accept_out_dev);
+
 /* Timing hooks for bench.py: with a ring of `slots` HIP event pairs per kernel
  * (slots = 0 disables), every pp_voxelize*_dev call brackets each of its three launches
  * (PP_KERNEL_SPLIT, PP_KERNEL_TILE, PP_KERNEL_EMIT) with an event pair bound to the dispatch
