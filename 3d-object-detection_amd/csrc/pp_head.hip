@@ -19,6 +19,11 @@
 //     the loads of block i + kHeadDepth are issued when block i has been multiplied, across tile boundaries.
 //     (Refilling two blocks at a time, so that both halves of a pixel's 128-byte line are asked for together, and
 //     issuing the first blocks ahead of the LDS fill measured 8 us slower: profiles/r18/NOTES.md.)
+//   * The bookkeeping stays out of the MFMA stream: where a wave stands (tile, source, block) is scalar state, the
+//     current source's pointer, stride, block count and table flag are read from a descriptor in LDS only when the
+//     source changes, a lane's two row offsets are recomputed only then, and a block's cursor steps and refill
+//     addresses sit between its four groups of MFMAs.  About 4 scalar branches per block instead of about 28 took
+//     the kernel from 141 to 107 us at the headline shape (profiles/r23/NOTES.md).
 //   * The results leave as 4-byte stores from the accumulator layout (16 lanes = 64 contiguous bytes).
 // No atomics and a fixed summation order: bit-identical from call to call.
 
@@ -54,23 +59,45 @@ __device__ __forceinline__ T head_pick(const T (&a)[kHeadMaxSrc], int s) {
   return s == 0 ? a[0] : s == 1 ? a[1] : s == 2 ? a[2] : a[3];
 }
 
+__device__ __forceinline__ int64_t head_uniform(int64_t v) {
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
+  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((uint64_t)v >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
 // Where a wave stands in its sequence of (tile, step): a tile is kbp = kb rounded up to kHeadDepth steps, so that a
 // step's ring slot is known at compile time.  Step fb < kb is block cb of source s; a padding step (fb >= kb) and every
-// step past the wave's last tile re-read a valid block and are never multiplied.  Branch-free: wave-uniform selects.
+// step past the wave's last tile re-read a valid block and are never multiplied.  Everything here is wave-uniform and
+// lives in scalar registers.  The current source's pointer, stride, block count and "has a table" are held beside the
+// position and read again -- one descriptor of four in LDS -- only when the source changes: a step costs an increment
+// and two compares, and no chain of picks among the kernel arguments runs at any load or block.
 struct HeadCursor {
   int64_t tile, last_tile, tile_step;
   int s, cb, fb;   // source, block inside it, step of the tile
-  __device__ __forceinline__ void advance(const HeadArgs &a, int kbp) {
+  const float *src;
+  int64_t stride;
+  int blocks;
+  bool table;
+  __device__ __forceinline__ void pick(const int64_t *desc) {   // desc: [kHeadMaxSrc][4] in LDS
+    const int64_t *d = desc + s * 4;
+    src = reinterpret_cast<const float *>(head_uniform(d[0]));
+    stride = head_uniform(d[1]);
+    blocks = __builtin_amdgcn_readfirstlane((int)d[2]);
+    table = __builtin_amdgcn_readfirstlane((int)d[3]) != 0;
+  }
+  // true when the source or the tile changed: the one branch of a step, and seldom taken
+  __device__ __forceinline__ bool advance(int kb, int kbp, const int64_t *desc) {
     ++fb;
-    const bool src_end = fb < a.kb && cb + 1 == head_pick(a.blocks, s);
-    cb = fb < a.kb ? (src_end ? 0 : cb + 1) : cb;
-    s = src_end ? s + 1 : s;
-    const bool tile_end = fb == kbp;
+    const bool src_end = fb < kb && cb + 1 == blocks, tile_end = fb == kbp;
+    cb = fb < kb ? cb + 1 : cb;
+    if (__builtin_expect(!(src_end || tile_end), 1)) return false;
     const int64_t next = tile + tile_step <= last_tile ? tile + tile_step : last_tile;
     tile = tile_end ? next : tile;
     fb = tile_end ? 0 : fb;
-    s = tile_end ? 0 : s;
-    cb = tile_end ? 0 : cb;
+    s = tile_end ? 0 : s + 1;
+    cb = 0;
+    pick(desc);
+    return true;
   }
 };
 
@@ -79,7 +106,8 @@ __global__ __launch_bounds__(256) void k_head1x1(const HeadArgs a) {
   extern __shared__ float4 s_head[];
   float4 *s_w = s_head;                                                   // [kb][NT][64] float4
   float *s_tab = reinterpret_cast<float *>(s_head + (size_t)a.kb * NT * 64);  // [kb][4 groups][3][4]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int64_t *s_desc = reinterpret_cast<int64_t *>(s_tab + (size_t)a.kb * 48);  // [kHeadMaxSrc] {src, stride, blocks, table?}
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int row = lane & 15, g = lane >> 4;
 
   {
@@ -97,6 +125,13 @@ __global__ __launch_bounds__(256) void k_head1x1(const HeadArgs a) {
       const float *t = head_pick(a.table, s);
       s_tab[i] = t ? t[(fb * 16 + grp * 4 + j) * 3 + comp] : 0.0f;
     }
+    if (threadIdx.x < kHeadMaxSrc) {
+      const int k = threadIdx.x;
+      s_desc[k * 4 + 0] = reinterpret_cast<int64_t>(head_pick(a.src, k));
+      s_desc[k * 4 + 1] = head_pick(a.stride, k);
+      s_desc[k * 4 + 2] = head_pick(a.blocks, k);
+      s_desc[k * 4 + 3] = head_pick(a.table, k) != nullptr;
+    }
   }
   __syncthreads();   // the only workgroup barrier: a wave without a tile may leave below
 
@@ -107,6 +142,7 @@ __global__ __launch_bounds__(256) void k_head1x1(const HeadArgs a) {
   const int kbp = (a.kb + kHeadDepth - 1) / kHeadDepth * kHeadDepth;
 
   HeadCursor ld{first, first + (my_tiles - 1) * waves, waves, 0, 0, 0};   // the loads, kHeadDepth steps ahead of
+  ld.pick(s_desc);
   HeadCursor mm = ld;                                                      // the MFMAs
 
   using f32x4 = __attribute__((ext_vector_type(4))) float;
@@ -119,20 +155,38 @@ __global__ __launch_bounds__(256) void k_head1x1(const HeadArgs a) {
 #pragma unroll
     for (int r = 0; r < 2; ++r) acc[r][t] = f32x4{bias[t], bias[t], bias[t], bias[t]};
   }
-
-  auto issue = [&](float4 (&slot)[2]) {
-    const float *base = head_pick(a.src, ld.s) + ld.cb * 16 + g * 4;
-    const int64_t st = head_pick(a.stride, ld.s);
+  // the lane's two pixel rows of the load cursor's tile in its source, in floats: computed again only when the
+  // cursor says that the source or the tile changed
+  int64_t off[2];
+  auto locate = [&]() {
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       int64_t p = ld.tile * kHeadTilePixels + r * 16 + row;
       p = p < a.pixels ? p : a.pixels - 1;   // a partial last tile re-reads the last pixel; its rows are not stored
-      slot[r] = *reinterpret_cast<const float4 *>(base + p * st);
+      off[r] = p * ld.stride + g * 4;
     }
-    ld.advance(a, kbp);
+  };
+  locate();
+  // a refill in two parts, so that the addresses and the cursor's step can sit between the MFMAs of a block while
+  // the loads themselves go out behind the block's last MFMA: the slot's registers are the MFMAs' operands until then
+  using gptr = const __attribute__((address_space(1))) f32x4 *;   // the pointer came through LDS: not a flat load
+  auto aim = [&](gptr (&q)[2]) {
+    const float *base = ld.src + ld.cb * 16;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) q[r] = (gptr)(base + off[r]);
+    if (ld.advance(a.kb, kbp, s_desc)) locate();
+  };
+  auto fetch = [&](f32x4 (&slot)[2], gptr (&q)[2]) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r) slot[r] = *q[r];
+  };
+  auto issue = [&](f32x4 (&slot)[2]) {
+    gptr q[2];
+    aim(q);
+    fetch(slot, q);
   };
 
-  float4 ring[kHeadDepth][2];
+  f32x4 ring[kHeadDepth][2];
 #pragma unroll
   for (int i = 0; i < kHeadDepth; ++i) issue(ring[i]);
 
@@ -144,8 +198,8 @@ __global__ __launch_bounds__(256) void k_head1x1(const HeadArgs a) {
 #pragma unroll
       for (int i = 0; i < kHeadDepth; ++i) {
         if (mm.fb < a.kb) {
-          float4 v[2] = {ring[i][0], ring[i][1]};
-          if (head_pick(a.table, mm.s) != nullptr) {
+          f32x4 v[2] = {ring[i][0], ring[i][1]};
+          if (mm.table) {
             const float4 *tq = reinterpret_cast<const float4 *>(s_tab + mm.fb * 48 + g * 12);
             const float4 b = tq[0], s = tq[1], t = tq[2];
 #pragma unroll
@@ -159,18 +213,25 @@ __global__ __launch_bounds__(256) void k_head1x1(const HeadArgs a) {
           float4 bw[NT];
 #pragma unroll
           for (int t = 0; t < NT; ++t) bw[t] = s_w[(mm.fb * NT + t) * 64 + lane];
-          // element j of every fragment, then j + 1: 2 * NT independent accumulators between two MFMAs on the same one
+          // element j of every fragment, then j + 1: 2 * NT independent accumulators between two MFMAs on the same
+          // one.  Both cursors' steps and the refill's addresses go between the four groups of MFMAs, where the
+          // matrix pipe is busy, not between two blocks.
 #define PP_HEAD_MFMA(e)                                                                             \
   _Pragma("unroll") for (int t = 0; t < NT; ++t) _Pragma("unroll") for (int r = 0; r < 2; ++r)      \
       acc[r][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[r].e, bw[t].e, acc[r][t], 0, 0, 0)
+          gptr q[2];
           PP_HEAD_MFMA(x);
+          mm.advance(a.kb, kbp, s_desc);
           PP_HEAD_MFMA(y);
+          aim(q);
           PP_HEAD_MFMA(z);
           PP_HEAD_MFMA(w);
+          fetch(ring[i], q);
 #undef PP_HEAD_MFMA
+        } else {
+          mm.advance(a.kb, kbp, s_desc);
+          issue(ring[i]);
         }
-        mm.advance(a, kbp);
-        issue(ring[i]);
       }
     }
     // the tile is complete.  C/D layout: column (n) = lane & 15, row (pixel) = 4 * (lane >> 4) + register
@@ -230,7 +291,9 @@ extern "C" int pp_head1x1_nhwc_dev(pp_ctx_t *ctx, void *stream_, int64_t pixels,
     a.kb += c / 16;
   }
   const int nt = (out_channels + 15) / 16;
-  const size_t lds = ((size_t)a.kb * nt * 256 + (size_t)a.kb * 48) * sizeof(float);
+  const size_t lds = ((size_t)a.kb * nt * 256 + (size_t)a.kb * 48) * sizeof(float) + kHeadMaxSrc * 4 * sizeof(int64_t);
+  // (model.py's _head_fits leaves the 128 bytes of descriptors out of its sum; no shape it admits comes within
+  // 128 bytes of the limit -- the nearest, 73 blocks x 32 outputs, needs 163 520 of 163 840 -- so the two agree)
   if (lds > kHeadMaxLds) {
     set_error("pp_head1x1_nhwc_dev: %d input channels x %d outputs do not fit the kernel's LDS image (%zu > %zu "
               "bytes)", a.kb * 16, out_channels, lds, kHeadMaxLds);

@@ -14,11 +14,19 @@
 // ReLU is monotone, so max_n ReLU(z_n) = ReLU(max_n z_n) and min likewise; and a lane whose
 // BatchNorm scale is negative negates its weights and bias (fma(-w, x, -a) = -fma(w, x, a)
 // exactly), so min_n z_n = -max_n(-z_n): ONE running max per lane, no per-point ReLU.
-// 9 MACs x 64 channels per 4-byte input make this compute-bound, not HBM-bound (reading the
-// 173 MB of a 4-sweep step takes 42 us on this chip): as a VALU kernel (v_fma_f32 or
-// v_pk_fma_f32 alike, one or four channels per lane) it ran at ~55 TF/s = 98 us per step; the
-// f32 MFMA form below is the same fmaf chain bit for bit and measures 86 us -- its MFMAs
-// (130 per wave, 41 us in total) reach 45 % of the pipe (profiles/r01/NOTES.md).
+// 9 MACs x 64 channels per 4-byte input make a tensor without padding compute-bound, not
+// HBM-bound (reading the 173 MB of a 4-sweep step takes 42 us on this chip): as a VALU kernel
+// (v_fma_f32 or v_pk_fma_f32 alike, one or four channels per lane) it ran at ~55 TF/s = 98 us
+// per step; the f32 MFMA form below is the same fmaf chain bit for bit, 130 MFMAs per wave
+// (41 us in total), and measures 78 us when every tile is multiplied (profiles/r01/NOTES.md,
+// profiles/r23/NOTES.md).  A real dense tensor is mostly zero padding, and a tile of 32 rows
+// whose operands are all +0.0 gives the same value z0 in every accumulator register: the
+// kernel tests each tile (a wave-uniform ballot), skips the MFMAs and maxima of a zero tile
+// and folds z0 -- taken from the same MFMAs on a zero row, once per wave -- into the pillars
+// the tile covers.  The operands arrive in two groups of four tiles, each reloaded whole
+// while the other is worked on.  At bench.py's headline batch 69 % of the tiles are skipped
+// and the kernel takes 54 us (3.2 TB/s); on a tensor with no zero tile 80 us against the
+// 78 it took before the tests, inside that build's leg spread: profiles/r23/NOTES.md.
 
 #include "pp_common.h"
 
@@ -30,6 +38,7 @@ constexpr int kPfnKW = 4;        // pillars per wave
 constexpr int kPfnChunk = 256;   // points staged per pass (generic kernel)
 constexpr int kMfmaKW = 4;       // pillars per wave in the MFMA kernel (8 and 16 measured slower)
 constexpr int kPfnDepth = 8;     // operand tiles in flight per wave (MFMA kernel)
+constexpr int kPfnGroup = 4;     // ... loaded and reloaded this many at a time
 
 __device__ __forceinline__ void wave_sync() {
   // LDS operations of one wave execute in program order; this only stops the compiler
@@ -136,52 +145,110 @@ __global__ __launch_bounds__(kPfnWaves * 64) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
     for (int k = 0; k < kMfmaKW; ++k) m[nt][k] = -INFINITY;
 
-  // kPfnDepth tiles of operands in flight per wave: a tile is 10 MFMAs (~0.3 us), far less
-  // than an HBM round trip
+  // kPfnDepth tiles of operands in flight per wave, in two groups of kPfnGroup tiles: a
+  // group is loaded as a whole, with no condition (load_tile clamps: a tile past the end
+  // re-reads the wave's last point, one cache line, and is never multiplied), and reloaded
+  // as a whole once its tiles are done, while the other group is worked on.  Every path to
+  // a group's first tile has then issued the same loads in the same order, and the
+  // compiler's wait there is exact: the other group's loads stay in flight.  (With a refill
+  // per tile, under a condition or beside the zero test's branches, its waits drained the
+  // ring at a tile boundary: once per eight tiles at best, at every tile at worst, which on
+  // a tensor without zero tiles cost 6 us of 78: profiles/r23/NOTES.md.)
   float a[kPfnDepth][5];
 #pragma unroll
-  for (int i = 0; i < kPfnDepth; ++i)
-    if (i < tiles) load_tile(i, a[i]);
-  for (int t0 = 0; t0 < tiles; t0 += kPfnDepth) {
-#pragma unroll
-    for (int i = 0; i < kPfnDepth; ++i) {
-      const int t = t0 + i;
-      if (t >= tiles) break;  // wave-uniform
-      f32x16 acc[2];
+  for (int i = 0; i < kPfnDepth; ++i) {
+    load_tile(i, a[i]);
+    __builtin_amdgcn_sched_barrier(0);  // in the order the tiles are used, or the count means nothing
+  }
+
+  // a tile's 32 accumulator registers into the running maxima of the pillars its rows cover
+  auto fold = [&](int t, f32x16 (&acc)[2]) {
+    const int k_lo = pillar_of(t * 32), k_hi = pillar_of(t * 32 + 31);
+    if (k_lo == k_hi) {
+      // the common case (10 of 13 tiles at N = 100): all 16 registers feed one maximum
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt) {
+        float g = acc[nt][0];
 #pragma unroll
-        for (int v = 0; v < 16; ++v) acc[nt][v] = cb[nt];
+        for (int v = 1; v < 16; ++v) g = fmaxf(g, acc[nt][v]);
 #pragma unroll
-        for (int st = 0; st < 5; ++st)
-          acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][st], bw[nt][st], acc[nt], 0, 0, 0);
+        for (int k = 0; k < kMfmaKW; ++k)
+          if (k_lo == k) m[nt][k] = fmaxf(m[nt][k], g);  // k_lo is wave-uniform
       }
-      if (t + kPfnDepth < tiles) load_tile(t + kPfnDepth, a[i]);
-      const int k_lo = pillar_of(t * 32), k_hi = pillar_of(t * 32 + 31);
-      if (k_lo == k_hi) {
-        // the common case (10 of 13 tiles at N = 100): all 16 registers feed one maximum
+    } else {
+#pragma unroll
+      for (int vg = 0; vg < 4; ++vg) {
+        // rows vg*8 + h*4 .. +3 of the tile: inside one pillar because N % 4 == 0
+        const int pid = pillar_of(t * 32 + vg * 8 + h * 4);
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
-          float g = acc[nt][0];
+          const float g = fmaxf(fmaxf(acc[nt][4 * vg], acc[nt][4 * vg + 1]),
+                                fmaxf(acc[nt][4 * vg + 2], acc[nt][4 * vg + 3]));
 #pragma unroll
-          for (int v = 1; v < 16; ++v) g = fmaxf(g, acc[nt][v]);
-#pragma unroll
-          for (int k = 0; k < kMfmaKW; ++k)
-            if (k_lo == k) m[nt][k] = fmaxf(m[nt][k], g);  // k_lo is wave-uniform
+          for (int k = 0; k < kMfmaKW; ++k) m[nt][k] = (pid == k) ? fmaxf(m[nt][k], g) : m[nt][k];
         }
-      } else {
+      }
+    }
+  };
+  auto multiply = [&](const float (&v)[5], f32x16 (&acc)[2]) {
 #pragma unroll
-        for (int vg = 0; vg < 4; ++vg) {
-          // rows vg*8 + h*4 .. +3 of the tile: inside one pillar because N % 4 == 0
-          const int pid = pillar_of(t * 32 + vg * 8 + h * 4);
+    for (int nt = 0; nt < 2; ++nt) {
 #pragma unroll
-          for (int nt = 0; nt < 2; ++nt) {
-            const float g = fmaxf(fmaxf(acc[nt][4 * vg], acc[nt][4 * vg + 1]),
-                                  fmaxf(acc[nt][4 * vg + 2], acc[nt][4 * vg + 3]));
+      for (int q = 0; q < 16; ++q) acc[nt][q] = cb[nt];
 #pragma unroll
-            for (int k = 0; k < kMfmaKW; ++k) m[nt][k] = (pid == k) ? fmaxf(m[nt][k], g) : m[nt][k];
+      for (int st = 0; st < 5; ++st)
+        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[st], bw[nt][st], acc[nt], 0, 0, 0);
+    }
+  };
+  // A tile whose operands are all +0.0 bits (padding: most tiles of a real tensor) would leave
+  // the same value z0 in every accumulator register.  -0.0 is not zero here.  The lanes that
+  // hold a non-zero bit pattern, as a ballot (wave-uniform).
+  auto nonzero_lanes = [&](const float (&v)[5]) {
+    unsigned bits = 0;
+#pragma unroll
+    for (int st = 0; st < 5; ++st) bits |= __builtin_bit_cast(unsigned, v[st]);
+    return __builtin_amdgcn_ballot_w64(bits != 0u);
+  };
+  // z0: what a row of zeros gives, from the same five MFMAs per channel tile (not "the bias":
+  // a -0.0 bias or a non-finite weight makes them differ).  All 16 registers of a lane hold
+  // the same value, and lanes l and l + 32 (one channel) agree.  Computed when the wave meets
+  // its first zero tile: a tensor without one (a subtracted data mean) never pays for it.
+  float z0[2] = {0.0f, 0.0f};
+  bool have_z0 = false;  // wave-uniform
+  for (int t0 = 0; t0 < tiles; t0 += kPfnDepth) {
+#pragma unroll
+    for (int g = 0; g < kPfnDepth; g += kPfnGroup) {
+#pragma unroll
+      for (int i = g; i < g + kPfnGroup; ++i) {
+        const int t = t0 + i;
+        if (t < tiles) {  // wave-uniform; nothing in here touches memory
+          if (nonzero_lanes(a[i]) == 0ull) {
+            // no MFMAs, no maxima over registers: z0 goes to the pillars the tile's rows cover
+            if (!have_z0) {
+              const float zero[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+              f32x16 acc[2];
+              multiply(zero, acc);
+              z0[0] = acc[0][0];
+              z0[1] = acc[1][0];
+              have_z0 = true;
+            }
+            const int k_lo = pillar_of(t * 32), k_hi = pillar_of(t * 32 + 31);
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+              for (int k = 0; k < kMfmaKW; ++k)
+                if (k >= k_lo && k <= k_hi) m[nt][k] = fmaxf(m[nt][k], z0[nt]);  // wave-uniform
+          } else {
+            f32x16 acc[2];
+            multiply(a[i], acc);
+            fold(t, acc);
           }
         }
+      }
+#pragma unroll
+      for (int i = g; i < g + kPfnGroup; ++i) {
+        load_tile(t0 + kPfnDepth + i, a[i]);
+        __builtin_amdgcn_sched_barrier(0);
       }
     }
   }
