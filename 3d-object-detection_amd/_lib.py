@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("PP_HIP_LIB") or os.path.join(_HERE, "libpp_hip.so")
 SOURCES = [os.path.join(_HERE, "csrc", f)
-           for f in ("pp_runtime.hip", "pp_voxelize.hip", "pp_iou.hip", "pp_ingest.hip", "pp_decode.hip", "pp_epilogue.hip", "pp_pfn.hip", "pp_pfn_train.hip", "pp_bn_train.hip", "pp_eval.hip", "pp_wino.hip", "pp_conv_f16.hip", "pp_convt_f16.hip", "pp_conv_s2_f16.hip", "pp_stem.hip", "pp_head.hip", "pp_augment.hip", "pp_paste.hip")]
+           for f in ("pp_runtime.hip", "pp_voxelize.hip", "pp_iou.hip", "pp_ingest.hip", "pp_decode.hip", "pp_epilogue.hip", "pp_pfn.hip", "pp_pfn_train.hip", "pp_bn_train.hip", "pp_eval.hip", "pp_wino.hip", "pp_conv_f16.hip", "pp_convt_f16.hip", "pp_conv_s2_f16.hip", "pp_stem.hip", "pp_head.hip", "pp_augment.hip", "pp_paste.hip", "pp_loss.hip")]
 HEADERS = [os.path.join(_HERE, "csrc", "pp_common.h"), os.path.join(_HERE, "csrc", "pp_conv_f16_tile.h"),
            os.path.join(_HERE, "csrc", "pp_box_geom.h"),
            os.path.join(_ROOT, "include", "pp_hip.h")]
@@ -32,6 +32,7 @@ EXPORTS = [
     "pp_iou_check", "pp_make_ious_dev", "pp_assign_targets_dev", "pp_assign_targets_grid_dev", "pp_assign_targets_batch_dev", "pp_assign_targets_grid_batch_dev", "pp_ingest_dev", "pp_ingest_sweeps_dev", "pp_decode_dev", "pp_decode_strided_dev", "pp_decode_batch_dev", "pp_decode_nms_batch_dev", "pp_bias_relu_bn_dev", "pp_bias_relu_bn_nhwc_dev", "pp_conv3x3_wino_nhwc_dev", "pp_conv3x3_f16_nhwc_dev", "pp_convt3x3_f16_nhwc_dev", "pp_conv3x3_s2_f16_nhwc_dev", "pp_conv3x3_s2_pillars_nhwc_dev", "pp_head1x1_nhwc_dev", "pp_relu_bn_train_fwd_dev", "pp_relu_bn_train_bwd_dev", "pp_ctx_set_timing",
     "pp_ctx_read_emit_ms", "pp_ctx_read_kernel_ms", "pp_voxelize_check", "pp_host_pool_selftest",
     "pp_box3d_iou_dev", "pp_eval_match_batch_dev", "pp_augment_batch_dev", "pp_paste_batch_dev",
+    "pp_loss_workspace_bytes", "pp_loss_fwd_dev", "pp_loss_bwd_dev",
 ]
 
 
@@ -94,6 +95,17 @@ class PasteParams(ctypes.Structure):
     _fields_ = [("x_step", ctypes.c_double), ("y_step", ctypes.c_double),
                 ("x_min", ctypes.c_double), ("y_min", ctypes.c_double),
                 ("remove_scene_points", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+LOSS_NCHW, LOSS_NHWC = 0, 1     # PP_LOSS_*: pp_loss_params_t.layout
+
+
+class LossParams(ctypes.Structure):
+    """pp_loss_params_t: the shape and layout of the head's outputs and PPLoss's constants."""
+    _fields_ = [("batch", ctypes.c_int32), ("anchors_per_cell", ctypes.c_int32), ("classes", ctypes.c_int32),
+                ("height", ctypes.c_int32), ("width", ctypes.c_int32), ("layout", ctypes.c_int32),
+                ("gamma", ctypes.c_double), ("alpha", ctypes.c_double),
+                ("b_cls", ctypes.c_double), ("b_reg", ctypes.c_double), ("b_ort", ctypes.c_double)]
 
 
 def _compile(out, defines=(), force=False, verbose=False):
@@ -289,9 +301,13 @@ def _load(path):
                                        ctypes.POINTER(AugmentParams), vp, vp, vp, vp, vp, vp, vp, vp]
     L.pp_paste_batch_dev.argtypes = [vp, vp, ctypes.c_int32, vp, i64, pi32, pi32, pi32, vp, vp, vp, vp, i64, vp,
                                      ctypes.POINTER(PasteParams), vp, i64, pi32, vp]
+    L.pp_loss_workspace_bytes.argtypes = [ctypes.POINTER(LossParams)]
+    L.pp_loss_workspace_bytes.restype = i64
+    L.pp_loss_fwd_dev.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.POINTER(LossParams), vp, vp, vp, vp]
+    L.pp_loss_bwd_dev.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.POINTER(LossParams), vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
-        if name not in ("pp_last_error", "pp_version", "pp_ctx_destroy"):
+        if name not in ("pp_last_error", "pp_version", "pp_ctx_destroy", "pp_loss_workspace_bytes"):
             fn.restype = c_int
     return L
 

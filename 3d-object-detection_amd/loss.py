@@ -7,6 +7,8 @@ regression channel 6 is not written back in place into the model's output
 the reference's tanh touches channel 6 of the whole A_c*8 channel axis (the
 first anchor's dt only); that behaviour is kept.
 """
+import ctypes
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -52,3 +54,93 @@ class PPLoss(nn.Module):
         ort_loss = F.binary_cross_entropy_with_logits(ort_scores, ort_targets)
         total = self.b_cls * cls_loss + self.b_reg * reg_loss + self.b_ort * ort_loss
         return p, cls_loss, reg_loss, ort_loss, total
+
+
+class _FusedLoss(torch.autograd.Function):
+    """pp_loss_fwd_dev / pp_loss_bwd_dev (csrc/pp_loss.hip): three launches, nothing read back by the host."""
+
+    @staticmethod
+    def forward(ctx, cls, reg, cls_t, reg_t, mod):
+        from . import _lib
+        from .model import _call, _vp
+        dev = cls.device
+        B, cc, H, W = cls.shape
+        a_c = reg.shape[1] // mod.reg_dims
+        prm, workspace = mod._plan(dev, B, a_c, cc // a_c, H, W,
+                                   _lib.LOSS_NCHW if cls.is_contiguous() else _lib.LOSS_NHWC)
+        # per call, not cached: the backward of an earlier call may still need its n_pos
+        scalars = torch.empty((5,), dtype=torch.float64, device=dev)
+        losses = torch.empty((4,), dtype=torch.float32, device=dev)
+        p = torch.empty((B, H * W * cc), dtype=torch.float32, device=dev) if mod.return_p else None
+        _call("pp_loss_fwd_dev", dev, _vp(cls), _vp(reg), _vp(cls_t), _vp(reg_t), ctypes.byref(prm), _vp(workspace),
+              _vp(scalars), _vp(losses), _vp(p))
+        ctx.save_for_backward(cls, reg, cls_t, reg_t, scalars)
+        ctx.prm = prm
+        cl, rl, ol, tot = losses.unbind(0)
+        if p is None:
+            return cl, rl, ol, tot
+        ctx.mark_non_differentiable(p)
+        return cl, rl, ol, tot, p
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_cls, g_reg, g_ort, g_tot, *_):
+        from .model import _call, _vp
+        cls, reg, cls_t, reg_t, scalars = ctx.saved_tensors
+        grads4 = torch.stack((g_cls, g_reg, g_ort, g_tot)).to(torch.float32)
+        dcls, dreg = torch.empty_like(cls), torch.empty_like(reg)      # same layout as the inputs
+        _call("pp_loss_bwd_dev", cls.device, _vp(cls), _vp(reg), _vp(cls_t), _vp(reg_t), ctypes.byref(ctx.prm),
+              _vp(scalars), _vp(grads4), _vp(dcls), _vp(dreg))
+        return dcls, dreg, None, None, None
+
+
+class FusedPPLoss(PPLoss):
+    """PPLoss on the HIP loss kernels: the same five results and the same gradients, without the four
+    boolean-mask selections whose ``nonzero`` makes the host wait for the device, in three launches instead of
+    about thirty.  All four losses are differentiable outputs of ONE autograd node (``shard.global_batch_loss``
+    combines them with its own weights).  ``return_p=False`` skips the probabilities (``p`` is then ``None``).
+    Inputs: NCHW-contiguous or channels_last f32 on a GPU (anything else strided is made contiguous); inputs that
+    are not on a GPU or not f32 take the plain ``PPLoss`` forward."""
+
+    def __init__(self, b_ort=0.0, b_reg=1.0, b_cls=250.0, gamma=2.0, reg_dims=8, return_p=True):
+        super().__init__(b_ort, b_reg, b_cls, gamma, reg_dims)
+        if reg_dims != 8:
+            raise ValueError("FusedPPLoss: reg_dims is fixed at 8")
+        self.return_p = return_p
+        self._plans = {}       # (device, shape, layout) -> (LossParams, workspace)
+
+    def _plan(self, dev, B, a_c, C, H, W, layout):
+        from . import _lib
+        key = (dev, B, a_c, C, H, W, layout)
+        plan = self._plans.get(key)
+        # the weights are plain attributes: a plan built for other values is rebuilt
+        consts = (float(self.gamma), 25.0, float(self.b_cls), float(self.b_reg), float(self.b_ort))
+        if plan is None or plan[2] != consts:
+            prm = _lib.LossParams(B, a_c, C, H, W, layout, *consts)
+            nbytes = _lib.lib().pp_loss_workspace_bytes(ctypes.byref(prm))
+            if nbytes < 0:
+                _lib.check(int(nbytes), "pp_loss_workspace_bytes")
+            plan = self._plans[key] = (prm, torch.empty((nbytes // 8,), dtype=torch.float64, device=dev), consts)
+        return plan[0], plan[1]
+
+    def forward(self, cls_tensor, reg_tensor, cls_targets, reg_targets):
+        tensors = (cls_tensor, reg_tensor, cls_targets, reg_targets)
+        if not all(t.is_cuda and t.dtype == torch.float32 for t in tensors):
+            out = super().forward(*tensors)
+            return out if self.return_p else (None,) + tuple(out[1:])
+        if cls_tensor.dim() != 4 or reg_tensor.dim() != 4 or cls_tensor.shape[0] != reg_tensor.shape[0] \
+                or cls_tensor.shape[2:] != reg_tensor.shape[2:] or reg_tensor.shape[1] % self.reg_dims \
+                or cls_tensor.shape[1] % (reg_tensor.shape[1] // self.reg_dims):
+            raise ValueError(f"FusedPPLoss: cls {tuple(cls_tensor.shape)} / reg {tuple(reg_tensor.shape)}")
+        B, cc, H, W = cls_tensor.shape
+        a_c = reg_tensor.shape[1] // self.reg_dims
+        if cls_targets.numel() != B * H * W * cc or reg_targets.numel() != B * H * W * a_c * 9:
+            raise ValueError(f"FusedPPLoss: targets {tuple(cls_targets.shape)} / {tuple(reg_targets.shape)} "
+                             f"do not fit cls {tuple(cls_tensor.shape)}")
+        cl = torch.channels_last
+        if not ((cls_tensor.is_contiguous() and reg_tensor.is_contiguous()) or
+                (not cls_tensor.is_contiguous() and not reg_tensor.is_contiguous() and
+                 cls_tensor.is_contiguous(memory_format=cl) and reg_tensor.is_contiguous(memory_format=cl))):
+            cls_tensor, reg_tensor = cls_tensor.contiguous(), reg_tensor.contiguous()
+        out = _FusedLoss.apply(cls_tensor, reg_tensor, cls_targets.contiguous(), reg_targets.contiguous(), self)
+        return (out[4] if self.return_p else None,) + tuple(out[:4])

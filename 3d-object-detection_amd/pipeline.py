@@ -11,7 +11,7 @@ import torch
 
 from . import boxes
 from .augment import Augmenter, Paster, draw, draw_paste, extend_gts
-from .loss import PPLoss
+from .loss import FusedPPLoss, PPLoss
 from .model import PPModel, check_inference_precision
 from .targets import TargetAssigner
 from .voxelizer import PillarVoxelizer, VoxelConfig
@@ -21,7 +21,7 @@ class PillarPipeline:
     def __init__(self, vox_cfg: VoxelConfig, anchor_cfg: boxes.AnchorConfig = None,
                  feature_channels=64, num_classes=9, reg_dims=8, device=None, seed=0,
                  pos_thresh=0.6, with_targets=False, data_mean=None, precision="f32",
-                 strided=False, augment=None, paste=None):
+                 strided=False, augment=None, paste=None, fused_loss=False):
         """``augment``: an ``augment.AugmentConfig`` -- ``train_forward_backward(..., augment_rng=rng)`` then augments
         the points and the boxes on the device before the voxelizer and the assigner (needs ``with_targets``).
         ``paste``: ``(augment.GtBank, augment.PasteConfig)`` -- ground-truth sampling before that augmentation, so
@@ -29,7 +29,9 @@ class PillarPipeline:
         pasting alone pass ``AugmentConfig.identity()``).
         ``precision``: ``PPModel.set_inference_precision`` ("f32", "fp16" for fp16-operand MFMA in the
         backbone's stride-1 layers at inference, or "fp16-up" for those and the two strided transposed convolutions);
-        ``strided``: its keyword of the same name (the down blocks' stride-2 convolutions too; not with "f32")."""
+        ``strided``: its keyword of the same name (the down blocks' stride-2 convolutions too; not with "f32").
+        ``fused_loss``: ``train_forward_backward`` computes the loss and its gradients with ``loss.FusedPPLoss`` (three
+        HIP launches, no host wait) instead of ``PPLoss``."""
         check_inference_precision(precision, strided)      # before anything is built
         self.check_paste_argument(paste, augment)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -46,7 +48,7 @@ class PillarPipeline:
         self.model.set_inference_precision(precision, strided)
         # inference: the head reads the up blocks' outputs where they lie (PPDetectionHead.fused_parts)
         self.model.det_head.fused_parts = True
-        self.loss = PPLoss()
+        self.loss = FusedPPLoss(return_p=False) if fused_loss else PPLoss()
         self.assigner = None
         if with_targets:
             # anchors evaluated on the fly in the target kernels (no per-anchor arrays)

@@ -745,6 +745,48 @@ int pp_relu_bn_train_bwd_dev(pp_ctx_t *ctx, void *stream, const float *z_dev,
                              float *dbeta_dev, float *dbias_dev);
 
 /*
+ * PPLoss (model/loss.py:24-63) forward and backward without a host read-back: focal-weighted BCE over every
+ * classification logit, smooth-L1 over the 7 regression dims and BCE over the orientation logit of the
+ * POSITIVE anchors (reg_t[..., 0] == 1), total = b_cls*cls + b_reg*reg + b_ort*ort.
+ *   cls_dev      [batch][anchors_per_cell*classes][height][width] f32 logits
+ *   reg_dev      [batch][anchors_per_cell*8][height][width] f32
+ *                layout PP_LOSS_NCHW: both contiguous in that order; PP_LOSS_NHWC: the same tensors stored
+ *                channels-last ([batch][height][width][channels]); dcls_dev / dreg_dev come back in that layout
+ *   cls_t_dev    [batch][A][classes] f32, reg_t_dev [batch][A][9] f32 contiguous, A = height*width*anchors_per_cell
+ *                in (h, w, a) order: what pp_assign_targets_*batch_dev writes
+ *   forward      workspace_dev: pp_loss_workspace_bytes(params) bytes, 8-byte aligned (per-workgroup partial sums);
+ *                scalars_dev f64[5] = {cls, reg, ort, total, n_pos}; losses_dev f32[4] = the first four;
+ *                p_dev [batch][A*classes] f32 = sigmoid of the logits in the targets' order, or NULL.
+ *                Per element: p = sigmoid(x), w = (t == 1 ? alpha*(1 - p)^gamma : p^gamma), a constant for the
+ *                gradient; cls = sum w*bce(x, t) / (batch*A*classes).  reg / ort are means over 7*n_pos / n_pos
+ *                elements: NaN without a positive anchor, like the mean over an empty selection.  tanh is applied
+ *                to channel 6 of the whole anchors_per_cell*8 axis (the first anchor's dim 6 only), as the
+ *                reference does.  Sums across elements are f64 in a fixed order: bit-identical from call to call.
+ *   backward     grads4_dev f32[4]: the incoming gradients of (cls, reg, ort, total); scalars_dev from the forward
+ *                (only n_pos is read); every element of dcls_dev / dreg_dev is written; a non-positive anchor's
+ *                dreg is exactly +0.0 whatever grads4 holds.
+ * Three launches on `stream` (partial sums, finalize, backward); no allocation, no atomics, no synchronisation.
+ * PP_ERR_VALUE, before any HIP call: NULL arguments (p_dev excepted), sizes < 1, anchors_per_cell*9 or
+ * anchors_per_cell*classes > 95, an unknown layout, gamma < 0 (or NaN).
+ * pp_loss_workspace_bytes returns the byte count, or PP_ERR_VALUE for bad params.
+ */
+#define PP_LOSS_NCHW 0
+#define PP_LOSS_NHWC 1
+typedef struct pp_loss_params {
+  int32_t batch, anchors_per_cell, classes, height, width;
+  int32_t layout;             /* PP_LOSS_* */
+  double gamma, alpha;        /* focal exponent (2) and positive weight (25) */
+  double b_cls, b_reg, b_ort; /* total = b_cls*cls + b_reg*reg + b_ort*ort */
+} pp_loss_params_t;
+int64_t pp_loss_workspace_bytes(const pp_loss_params_t *params);
+int pp_loss_fwd_dev(pp_ctx_t *ctx, void *stream, const float *cls_dev, const float *reg_dev,
+                    const float *cls_t_dev, const float *reg_t_dev, const pp_loss_params_t *params,
+                    void *workspace_dev, double *scalars_dev, float *losses_dev, float *p_dev);
+int pp_loss_bwd_dev(pp_ctx_t *ctx, void *stream, const float *cls_dev, const float *reg_dev,
+                    const float *cls_t_dev, const float *reg_t_dev, const pp_loss_params_t *params,
+                    const double *scalars_dev, const float *grads4_dev, float *dcls_dev, float *dreg_dev);
+
+/*
  * The device entry points never synchronise.  pp_voxelize_check synchronises `stream` and
  * returns PP_ERR_HIP (with the runtime's message) if a launch on it failed, else PP_OK.  The
  * voxelizer kernels themselves have no failure mode of their own any more: no workgroup waits
