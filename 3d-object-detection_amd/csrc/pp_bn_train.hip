@@ -303,22 +303,12 @@ static int rbn_setup(const char *who, pp_ctx_t *ctx, int64_t batch, int channels
   const int64_t per_pass = (int64_t)kRbnThreads * (g->vec ? 4 : 1);
   ns = (int)std::min<int64_t>(ns, std::max<int64_t>(1, hw / per_pass));
   g->nsplit = std::max(1, std::min(ns, kRbnMaxSplit));
+  DeviceGuard guard(ctx->device);  // the scratch is allocated on the context's device
   int rc = ctx->pfn_ws.ensure((size_t)channels * kRbnMaxSplit * 5 * sizeof(double) + 4096);
   if (rc) return rc;
   *part = static_cast<double *>(ctx->pfn_ws.ptr);
   return PP_OK;
 }
-
-struct RbnDevice {
-  int prev = -1, dev;
-  explicit RbnDevice(int d) : dev(d) {
-    (void)hipGetDevice(&prev);
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~RbnDevice() {
-    if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-  }
-};
 
 }  // namespace pp
 
@@ -339,7 +329,7 @@ extern "C" int pp_relu_bn_train_fwd_dev(pp_ctx_t *ctx, void *stream_, const floa
   }
   int rc = rbn_setup("pp_relu_bn_train_fwd_dev", ctx, batch, channels, hw, {z_dev, y_dev}, &g, &part);
   if (rc) return rc;
-  RbnDevice guard(ctx->device);
+  DeviceGuard guard(ctx->device);
   hipStream_t st = static_cast<hipStream_t>(stream_);
   const dim3 grid((unsigned)channels, (unsigned)g.nsplit);
   hipLaunchKernelGGL(k_rbn_stats, grid, dim3(kRbnThreads), 0, st, z_dev, conv_bias_dev, part, g);
@@ -371,7 +361,7 @@ extern "C" int pp_relu_bn_train_bwd_dev(pp_ctx_t *ctx, void *stream_, const floa
   }
   g.dy_extra = dy_batch_stride - (int64_t)channels * hw;
   if (g.dy_extra % 4 != 0) g.vec = false;  // float4 alignment of the later batches of dy
-  RbnDevice guard(ctx->device);
+  DeviceGuard guard(ctx->device);
   hipStream_t st = static_cast<hipStream_t>(stream_);
   const dim3 grid((unsigned)channels, (unsigned)g.nsplit);
   hipLaunchKernelGGL(k_rbn_bwd_stats, grid, dim3(kRbnThreads), 0, st, z_dev, conv_bias_dev, dy_dev, mean_dev,

@@ -102,6 +102,15 @@ struct GridGeom {
 int make_grid(const pp_voxel_params_t *prm, GridGeom *g, int step_mode = 0);
 
 #ifdef __HIPCC__
+__device__ __forceinline__ void wave_sync() {
+  // LDS operations of one wave execute in program order; this only stops the compiler
+  // from moving LDS accesses across a cross-lane hand-off.
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ float sigmoid_f32(float x) { return 1.0f / (1.0f + expf(-x)); }
+
 // Inclusive prefix sum over the wave's 64 lanes on the DPP path (row shifts inside the rows of 16,
 // then the two row broadcasts of gfx9): 6 VALU adds with DPP operands instead of 6 ds_bpermute
 // round trips through the LDS pipeline.  ALL 64 lanes must be active at the call (a DPP read of an
@@ -211,4 +220,20 @@ struct pp_ctx {
 
 namespace pp {
 HostPool *host_pool(pp_ctx *ctx);  // the context's pool, created on first use
+
+// launch() on the context's device; kernel names it in the message of a failed launch.
+template <class Launch>
+int launch_on_device(const pp_ctx_t *ctx, const char *kernel, Launch &&launch) {
+  hipError_t e;
+  {
+    DeviceGuard guard(ctx->device);
+    launch();
+    e = hipGetLastError();      // the launch's, before the guard's own HIP call
+  }
+  if (e != hipSuccess) {
+    set_error("%s launch failed: %s", kernel, hipGetErrorString(e));
+    return PP_ERR_HIP;
+  }
+  return PP_OK;
 }
+}  // namespace pp

@@ -1,7 +1,7 @@
 // pp_conv_f16_tile.h -- what the fp16-operand MFMA convolutions (pp_conv_f16.hip, pp_convt_f16.hip,
 // pp_conv_s2_f16.hip) share:
 // the LDS image of one chunk of 16 input channels, the loader that stages it through registers, the
-// double-buffered chunk pipeline, the epilogue constants, and the host-side argument checks and launch.
+// double-buffered chunk pipeline, the epilogue constants, and the host-side argument checks.
 // A kernel brings its tile geometry, its MFMA role (which fragments feed which accumulators) and the
 // accumulator-to-pixel mapping of its stores.  Included by those three files only.
 //
@@ -200,22 +200,6 @@ inline int check_conv_f16_args(const char *fn, const pp_ctx_t *ctx, const float 
   if ((int64_t)height * width * in_channels > 0x7fffffff) {
     set_error("%s: tensor too large", fn);
     return PP_ERR_VALUE;
-  }
-  return PP_OK;
-}
-
-// launch() on the context's device; kernel names it in the message of a failed launch.
-template <class Launch>
-int launch_on_device(const pp_ctx_t *ctx, const char *kernel, Launch &&launch) {
-  hipError_t e;
-  {
-    DeviceGuard guard(ctx->device);
-    launch();
-    e = hipGetLastError();      // the launch's, before the guard's own HIP call
-  }
-  if (e != hipSuccess) {
-    set_error("%s launch failed: %s", kernel, hipGetErrorString(e));
-    return PP_ERR_HIP;
   }
   return PP_OK;
 }

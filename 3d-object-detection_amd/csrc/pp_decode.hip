@@ -78,8 +78,6 @@ __device__ __forceinline__ DecodeArgs sample_view(DecodeArgs d) {
   return d;
 }
 
-__device__ __forceinline__ float sigmoidf_ref(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // scores,classes = torch.max(torch.sigmoid(cls), dim=-1)   (evaluate.py:231-235)
 // torch.max propagates NaN: an anchor with a NaN class score has score NaN, which is above no threshold
 __device__ __forceinline__ void anchor_score(const DecodeArgs &d, int a, float &score, int &klass) {
@@ -89,7 +87,7 @@ __device__ __forceinline__ void anchor_score(const DecodeArgs &d, int a, float &
   klass = 0;
   bool poisoned = false;
   for (int c = 0; c < d.C; ++c) {
-    const float s = sigmoidf_ref(p[(int64_t)c * d.cls_sc]);
+    const float s = sigmoid_f32(p[(int64_t)c * d.cls_sc]);
     poisoned = poisoned || s != s;
     if (s > score) {  // first maximum wins
       score = s;
@@ -747,15 +745,7 @@ extern "C" int pp_decode_nms_batch_dev(pp_ctx_t *ctx, void *stream_, int32_t bat
     return PP_ERR_VALUE;
   }
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != ctx->device) (void)hipSetDevice(ctx->device);
-  struct Restore {
-    int prev, dev;
-    ~Restore() {
-      if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-  } restore{prev, ctx->device};
+  DeviceGuard guard(ctx->device);
   size_t cap = 1;
   while (cap < (size_t)A) cap <<= 1;
   // scratch: [0, 4096) candidate counters (zero between calls) | keys [batch][cap]

@@ -193,26 +193,17 @@ extern "C" int pp_scatter_canvas_dev(pp_ctx_t *ctx, void *stream_, const float *
               channels, max_pillars, canvas_h, canvas_w);
     return PP_ERR_VALUE;
   }
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != ctx->device) (void)hipSetDevice(ctx->device);
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  int rc = PP_OK;
-  hipError_t e = hipMemsetAsync(canvas_dev, 0,
-                                (size_t)batch * channels * canvas_h * canvas_w * sizeof(float), st);
-  if (e == hipSuccess) {
+  return launch_on_device(ctx, "pp_scatter_canvas_dev", [&] {
+    hipStream_t st = static_cast<hipStream_t>(stream_);
+    // a failed memset is the error reported: nothing is launched after it
+    if (hipMemsetAsync(canvas_dev, 0, (size_t)batch * channels * canvas_h * canvas_w * sizeof(float), st) !=
+        hipSuccess)
+      return;
     const dim3 grid((unsigned)((max_pillars + 255) / 256), (unsigned)((channels + 63) / 64), (unsigned)batch);
     hipLaunchKernelGGL(k_scatter_canvas, grid, dim3(256), 0, st, features_dev,
                        reinterpret_cast<const long long *>(indices_dev), canvas_dev, channels, max_pillars,
                        canvas_h, canvas_w, channels_last ? 1 : 0);
-    e = hipGetLastError();
-  }
-  if (prev >= 0 && prev != ctx->device) (void)hipSetDevice(prev);
-  if (e != hipSuccess) {
-    set_error("pp_scatter_canvas_dev failed: %s", hipGetErrorString(e));
-    rc = PP_ERR_HIP;
-  }
-  return rc;
+  });
 }
 
 extern "C" int pp_subtract_mean_dev(pp_ctx_t *ctx, void *stream_, float *pillars_dev, int batch,
@@ -225,22 +216,14 @@ extern "C" int pp_subtract_mean_dev(pp_ctx_t *ctx, void *stream_, float *pillars
     set_error("pp_subtract_mean_dev: bad sizes (batch=%d elems=%lld)", batch, (long long)elems_per_sweep);
     return PP_ERR_VALUE;
   }
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != ctx->device) (void)hipSetDevice(ctx->device);
   const bool vec = (elems_per_sweep % 4 == 0) &&
                    (((reinterpret_cast<uintptr_t>(pillars_dev) | reinterpret_cast<uintptr_t>(mean_dev)) & 15) == 0);
   const int64_t work = vec ? elems_per_sweep / 4 : elems_per_sweep;
   const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((work + 255) / 256, 4096));
-  hipLaunchKernelGGL(k_subtract_mean, dim3(gx, (unsigned)batch), dim3(256), 0,
-                     static_cast<hipStream_t>(stream_), pillars_dev, mean_dev, elems_per_sweep, vec);
-  hipError_t e = hipGetLastError();
-  if (prev >= 0 && prev != ctx->device) (void)hipSetDevice(prev);
-  if (e != hipSuccess) {
-    set_error("k_subtract_mean launch failed: %s", hipGetErrorString(e));
-    return PP_ERR_HIP;
-  }
-  return PP_OK;
+  return launch_on_device(ctx, "k_subtract_mean", [&] {
+    hipLaunchKernelGGL(k_subtract_mean, dim3(gx, (unsigned)batch), dim3(256), 0,
+                       static_cast<hipStream_t>(stream_), pillars_dev, mean_dev, elems_per_sweep, vec);
+  });
 }
 
 extern "C" int pp_bias_relu_bn_nhwc_dev(pp_ctx_t *ctx, void *stream_, float *x_dev, int64_t pixels,
@@ -264,9 +247,6 @@ extern "C" int pp_bias_relu_bn_nhwc_dev(pp_ctx_t *ctx, void *stream_, float *x_d
               (long long)y_channel_offset);
     return PP_ERR_VALUE;
   }
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != ctx->device) (void)hipSetDevice(ctx->device);
   const int c4 = channels / 4;
   const int64_t n4 = pixels * c4;
   // 256 CUs x 8 workgroups in flight; a grid stride that is a multiple of 256 keeps the lane's
@@ -274,19 +254,14 @@ extern "C" int pp_bias_relu_bn_nhwc_dev(pp_ctx_t *ctx, void *stream_, float *x_d
   const unsigned blocks = (unsigned)std::min<int64_t>((n4 + 255) / 256, 2048);
   float *y = y_dev + y_channel_offset;
   hipStream_t st = static_cast<hipStream_t>(stream_);
-  if (256 % c4 == 0)
-    hipLaunchKernelGGL(k_bias_relu_bn_nhwc<true>, dim3(blocks), dim3(256), 0, st,
-                       reinterpret_cast<const float4 *>(x_dev), y, c4, n4, y_channels, params_dev);
-  else
-    hipLaunchKernelGGL(k_bias_relu_bn_nhwc<false>, dim3(blocks), dim3(256), 0, st,
-                       reinterpret_cast<const float4 *>(x_dev), y, c4, n4, y_channels, params_dev);
-  hipError_t e = hipGetLastError();
-  if (prev >= 0 && prev != ctx->device) (void)hipSetDevice(prev);
-  if (e != hipSuccess) {
-    set_error("k_bias_relu_bn_nhwc launch failed: %s", hipGetErrorString(e));
-    return PP_ERR_HIP;
-  }
-  return PP_OK;
+  return launch_on_device(ctx, "k_bias_relu_bn_nhwc", [&] {
+    if (256 % c4 == 0)
+      hipLaunchKernelGGL(k_bias_relu_bn_nhwc<true>, dim3(blocks), dim3(256), 0, st,
+                         reinterpret_cast<const float4 *>(x_dev), y, c4, n4, y_channels, params_dev);
+    else
+      hipLaunchKernelGGL(k_bias_relu_bn_nhwc<false>, dim3(blocks), dim3(256), 0, st,
+                         reinterpret_cast<const float4 *>(x_dev), y, c4, n4, y_channels, params_dev);
+  });
 }
 
 extern "C" int pp_bias_relu_bn_dev(pp_ctx_t *ctx, void *stream_, float *x_dev, int64_t batch,
@@ -311,18 +286,10 @@ extern "C" int pp_bias_relu_bn_dev(pp_ctx_t *ctx, void *stream_, float *x_dev, i
     set_error("pp_bias_relu_bn_dev: need batch*channels in [1,65535], hw >= 1");
     return PP_ERR_VALUE;
   }
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != ctx->device) (void)hipSetDevice(ctx->device);
   const unsigned gx = (unsigned)std::min<int64_t>(((hw >> 2) + 255) / 256 + 1, 64);
-  hipLaunchKernelGGL(k_bias_relu_bn, dim3(gx, (unsigned)(batch * channels)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream_), x_dev, y_dev + y_channel_offset * hw, channels,
-                     hw, y_channels, params_dev);
-  hipError_t e = hipGetLastError();
-  if (prev >= 0 && prev != ctx->device) (void)hipSetDevice(prev);
-  if (e != hipSuccess) {
-    set_error("k_bias_relu_bn launch failed: %s", hipGetErrorString(e));
-    return PP_ERR_HIP;
-  }
-  return PP_OK;
+  return launch_on_device(ctx, "k_bias_relu_bn", [&] {
+    hipLaunchKernelGGL(k_bias_relu_bn, dim3(gx, (unsigned)(batch * channels)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream_), x_dev, y_dev + y_channel_offset * hw, channels,
+                       hw, y_channels, params_dev);
+  });
 }

@@ -290,18 +290,6 @@ __global__ __launch_bounds__(64) void k_eval_match(EvalArgs d) {
   if (lane < d.C) d.gt_per_class[(int64_t)b * d.C + lane] = s_cnt[lane];
 }
 
-// Select ctx's device for the scope of a call.
-struct DeviceScope {
-  int prev = -1, dev;
-  explicit DeviceScope(int d) : dev(d) {
-    (void)hipGetDevice(&prev);
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceScope() {
-    if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-  }
-};
-
 }  // namespace pp
 
 using namespace pp;
@@ -317,7 +305,7 @@ extern "C" int pp_box3d_iou_dev(pp_ctx_t *ctx, void *stream_, int64_t Na, const 
     return PP_ERR_VALUE;
   }
   if (Na == 0 || Nb == 0) return PP_OK;
-  DeviceScope scope(ctx->device);
+  DeviceGuard guard(ctx->device);
   const int64_t total = Na * Nb;
   const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 65536);
   hipLaunchKernelGGL(k_box3d_iou, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream_), Na, a_dev, Nb,
@@ -381,7 +369,7 @@ extern "C" int pp_eval_match_batch_dev(pp_ctx_t *ctx, void *stream_, int32_t bat
   d.max_iou = max_iou_out;
   d.argmax = argmax_out;
   d.gt_per_class = gt_per_class_out;
-  DeviceScope scope(ctx->device);
+  DeviceGuard guard(ctx->device);
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   hipLaunchKernelGGL(k_eval_iou, dim3((unsigned)((max_out + kRowsPerWg - 1) / kRowsPerWg), (unsigned)batch),
                      dim3(kEvalThreads), 0, stream, d);

@@ -103,18 +103,10 @@ extern "C" int pp_ingest_sweeps_dev(pp_ctx_t *ctx, void *stream_, int32_t n_swee
   }
   const int64_t total = sb.first[n_sweeps];
   if (total == 0) return PP_OK;
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != ctx->device) (void)hipSetDevice(ctx->device);
-  hipLaunchKernelGGL(k_ingest_sweeps, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream_), sb, min_dist, reinterpret_cast<float4 *>(points_out_dev));
-  hipError_t e = hipGetLastError();
-  if (prev >= 0 && prev != ctx->device) (void)hipSetDevice(prev);
-  if (e != hipSuccess) {
-    set_error("k_ingest_sweeps launch failed: %s", hipGetErrorString(e));
-    return PP_ERR_HIP;
-  }
-  return PP_OK;
+  return launch_on_device(ctx, "k_ingest_sweeps", [&] {
+    hipLaunchKernelGGL(k_ingest_sweeps, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream_), sb, min_dist, reinterpret_cast<float4 *>(points_out_dev));
+  });
 }
 
 extern "C" int pp_ingest_dev(pp_ctx_t *ctx, void *stream_, const float *raw_dev, int64_t n_points,
@@ -135,17 +127,9 @@ extern "C" int pp_ingest_dev(pp_ctx_t *ctx, void *stream_, const float *raw_dev,
   if (n_points == 0) return PP_OK;
   Xform t;
   for (int k = 0; k < 12; ++k) t.m[k] = transform_rowmajor4x4[k];
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != ctx->device) (void)hipSetDevice(ctx->device);
-  hipLaunchKernelGGL(k_ingest, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream_), raw_dev, n_points, raw_cols, t, min_dist,
-                     reinterpret_cast<float4 *>(points_out_dev));
-  hipError_t e = hipGetLastError();
-  if (prev >= 0 && prev != ctx->device) (void)hipSetDevice(prev);
-  if (e != hipSuccess) {
-    set_error("k_ingest launch failed: %s", hipGetErrorString(e));
-    return PP_ERR_HIP;
-  }
-  return PP_OK;
+  return launch_on_device(ctx, "k_ingest", [&] {
+    hipLaunchKernelGGL(k_ingest, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream_), raw_dev, n_points, raw_cols, t, min_dist,
+                       reinterpret_cast<float4 *>(points_out_dev));
+  });
 }

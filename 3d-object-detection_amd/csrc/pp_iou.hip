@@ -396,13 +396,6 @@ struct TailLds {
 static_assert(sizeof(TailLds) <= sizeof(TgtLds), "the tail reuses the workgroup's LDS");
 constexpr size_t kTgtLdsBytes = sizeof(TgtLds) > sizeof(TailLds) ? sizeof(TgtLds) : sizeof(TailLds);
 
-__device__ __forceinline__ void iou_wave_sync() {
-  // LDS operations of one wave execute in program order; this only stops the compiler from
-  // moving them across a cross-lane hand-off
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // shoelace_dev over a ring of n vertices in LDS (ring[0..n), this group's slots), lane v holding
 // vertex v in (x, y): the terms are formed in parallel, handed over through LDS (terms[0..8)) and
 // summed in the serial order by every lane.  (Neighbour vertices and the terms come from LDS reads,
@@ -412,7 +405,7 @@ __device__ __forceinline__ double group_shoelace(double x, double y, int n, int 
                                                  double *terms) {
   const double2 j = ring[(v + 1 >= n) ? 0 : v + 1];
   terms[v] = x * j.y - j.x * y;
-  iou_wave_sync();
+  wave_sync();
   double s = 0.0;
 #pragma unroll
   for (int k = 0; k < KMAX; k += 2) {
@@ -420,7 +413,7 @@ __device__ __forceinline__ double group_shoelace(double x, double y, int n, int 
     if (k < n) s = s + t2.x;
     if (k + 1 < n) s = s + t2.y;
   }
-  iou_wave_sync();
+  wave_sync();
   return 0.5 * s;
 }
 
@@ -440,7 +433,7 @@ __device__ __forceinline__ void clip_groups(double (&cx)[NP], double (&cy)[NP], 
   int n[NP];
 #pragma unroll
   for (int u = 0; u < NP; ++u) poly[u][v] = make_double2(cx[u], cy[u]);  // the anchor quad (v < 4; zeros beyond)
-  iou_wave_sync();
+  wave_sync();
 #pragma unroll
   for (int u = 0; u < NP; ++u) {
     area_a[u] = group_shoelace<4>(cx[u], cy[u], 4, v, poly[u], terms[u]);
@@ -484,7 +477,7 @@ __device__ __forceinline__ void clip_groups(double (&cx)[NP], double (&cy)[NP], 
     // spare slot.  (A ninth vertex cannot come from two convex quads; it would land there too.)
 #pragma unroll
     for (int u = 0; u < NP; ++u) tt[u] = dp[u] / (dp[u] - dc[u]);
-    iou_wave_sync();  // every lane has its predecessor: the ring may be overwritten
+    wave_sync();  // every lane has its predecessor: the ring may be overwritten
 #pragma unroll
     for (int u = 0; u < NP; ++u) {
       const int pos = __popc(cb[u] & below) + __popc(kb[u] & below);
@@ -494,7 +487,7 @@ __device__ __forceinline__ void clip_groups(double (&cx)[NP], double (&cy)[NP], 
       poly[u][pk] = make_double2(cx[u], cy[u]);
       n[u] = min(__popc(cb[u]) + __popc(kb[u]), kGroup);
     }
-    iou_wave_sync();
+    wave_sync();
 #pragma unroll
     for (int u = 0; u < NP; ++u) {
       const double2 c = poly[u][v];
@@ -1756,7 +1749,7 @@ __global__ __launch_bounds__(kTgtThreads) void k_targets_gt(TargetArgs t, Target
       else if (lane < 15) S.gv7[lane - 8] = ld0;
       else if (lane == 15) S.gcls[0] = ldi;
       else if (lane >= 32 && lane < 32 + t.per_cell) S.rc_ad[lane - 32] = sqrt(ld0 * ld0 + ld1 * ld1);  // box_utils.py:79
-      iou_wave_sync();
+      wave_sync();
       if (lane == 0) {
         double g8[8];
 #pragma unroll

@@ -46,8 +46,6 @@ struct LossGeom {
 
 // ---- per-element terms (f32, loss.py:31-36, 42-52) ----
 
-__device__ __forceinline__ float loss_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // focal weight, constant for the gradient: at * (1 - pt)^gamma
 __device__ __forceinline__ float loss_focal_weight(float p, float t, float gamma, float alpha) {
   const bool is_pos = (t == 1.0f);
@@ -118,7 +116,7 @@ __global__ __launch_bounds__(kLossThreads) void k_loss_fwd(const float *__restri
     const int n = npx * g.CC;
     for (int i = threadIdx.x; i < n; i += kLossThreads) {
       const float x = cls[base + i], t = cls_t[base + i];
-      const float p = loss_sigmoid(x);
+      const float p = sigmoid_f32(x);
       cls_sum += (double)(loss_focal_weight(p, t, g.gamma, g.alpha) * loss_bce_logits(x, t));
       if (p_out) p_out[base + i] = p;
     }
@@ -132,7 +130,7 @@ __global__ __launch_bounds__(kLossThreads) void k_loss_fwd(const float *__restri
       const float x = src[(int64_t)ch * g.HW + px];
       float *slot = &s_tile[px * g.CCp + ch];
       const float t = *slot;
-      const float p = loss_sigmoid(x);
+      const float p = sigmoid_f32(x);
       cls_sum += (double)(loss_focal_weight(p, t, g.gamma, g.alpha) * loss_bce_logits(x, t));
       *slot = p;  // this thread's own element: p leaves through the same rows
     }
@@ -246,13 +244,13 @@ __device__ __forceinline__ LossCoef loss_coefficients(const float *__restrict__ 
 }
 
 __device__ __forceinline__ float loss_dcls(float x, float t, const LossGeom &g, float coef) {
-  const float p = loss_sigmoid(x);
+  const float p = sigmoid_f32(x);
   return loss_focal_weight(p, t, g.gamma, g.alpha) * (p - t) * coef;
 }
 
 // gradient of one regression channel of a POSITIVE anchor; tr = its 9 targets
 __device__ __forceinline__ float loss_dreg(float v, int ach, int d, const float *tr, const LossCoef &c) {
-  if (d == 7) return (loss_sigmoid(v) - tr[8]) * c.ort;
+  if (d == 7) return (sigmoid_f32(v) - tr[8]) * c.ort;
   float chain = 1.0f;
   if (ach == 6) {
     v = tanhf(v);

@@ -40,13 +40,6 @@ constexpr int kMfmaKW = 4;       // pillars per wave in the MFMA kernel (8 and 1
 constexpr int kPfnDepth = 8;     // operand tiles in flight per wave (MFMA kernel)
 constexpr int kPfnGroup = 4;     // ... loaded and reloaded this many at a time
 
-__device__ __forceinline__ void wave_sync() {
-  // LDS operations of one wave execute in program order; this only stops the compiler
-  // from moving LDS accesses across a cross-lane hand-off.
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 struct PfnLane {
   float w[9], bias, scale, shift;  // w, bias already negated when scale < 0
 };
@@ -348,23 +341,15 @@ extern "C" int pp_pfn_dense_dev(pp_ctx_t *ctx, void *stream_, const float *pilla
     set_error("pp_pfn_dense_dev: tensors must be 16-byte aligned");
     return PP_ERR_VALUE;
   }
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != ctx->device) (void)hipSetDevice(ctx->device);
   const dim3 grid((unsigned)((P + kPfnWaves * kPfnKW - 1) / (kPfnWaves * kPfnKW)), (unsigned)batch);
   const dim3 grid_mfma((unsigned)((P + kPfnWaves * kMfmaKW - 1) / (kPfnWaves * kMfmaKW)), (unsigned)batch);
   hipStream_t st = static_cast<hipStream_t>(stream_);
-  if ((N & 3) == 0 && 36ll * P * N < (1ll << 31))  // the MFMA kernel's buffer descriptor is 32-bit
-    hipLaunchKernelGGL(k_pfn_dense_mfma, grid_mfma, dim3(kPfnWaves * 64), 0, st, pillars_dev,
-                       pfn_params_dev, features_dev, P, N);
-  else
-    hipLaunchKernelGGL(k_pfn_dense, grid, dim3(kPfnWaves * 64), 0, st, pillars_dev, pfn_params_dev,
-                       features_dev, P, N);
-  hipError_t e = hipGetLastError();
-  if (prev >= 0 && prev != ctx->device) (void)hipSetDevice(prev);
-  if (e != hipSuccess) {
-    set_error("k_pfn_dense launch failed: %s", hipGetErrorString(e));
-    return PP_ERR_HIP;
-  }
-  return PP_OK;
+  return launch_on_device(ctx, "k_pfn_dense", [&] {
+    if ((N & 3) == 0 && 36ll * P * N < (1ll << 31))  // the MFMA kernel's buffer descriptor is 32-bit
+      hipLaunchKernelGGL(k_pfn_dense_mfma, grid_mfma, dim3(kPfnWaves * 64), 0, st, pillars_dev,
+                         pfn_params_dev, features_dev, P, N);
+    else
+      hipLaunchKernelGGL(k_pfn_dense, grid, dim3(kPfnWaves * 64), 0, st, pillars_dev, pfn_params_dev,
+                         features_dev, P, N);
+  });
 }

@@ -35,11 +35,6 @@ constexpr int kTrStats = 21;   // cnt, sum r, sum r^2, S1[9], S2[9]
 constexpr int kTrBwd = 12;     // dbeta, dgamma, db(sparse), dW(sparse)[9]
 constexpr int kTrMaxWg = 1024;
 
-__device__ __forceinline__ void tr_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 struct TrLane {
   float w[9], bias;
 };
@@ -110,7 +105,7 @@ __global__ __launch_bounds__(kTrWaves * 64) void k_pfn_train_stats(const float *
 #pragma unroll
       for (int d = 0; d < 9; ++d) sx[d][i] = row[d * plane + i];
     }
-    tr_wave_sync();
+    wave_sync();
     for (int j = 0; j < cn; ++j) {
       float xv[9];
 #pragma unroll
@@ -128,7 +123,7 @@ __global__ __launch_bounds__(kTrWaves * 64) void k_pfn_train_stats(const float *
         acc[12 + d] = fmaf(r, xv[d], acc[12 + d]);
       }
     }
-    tr_wave_sync();
+    wave_sync();
   }
   s_red_d[wave][0][lane] = sum_d;
   s_red_d[wave][1][lane] = sq_d;
@@ -220,7 +215,7 @@ __global__ __launch_bounds__(kTrWaves * 64) void k_pfn_train_bwd(
 #pragma unroll
         for (int d = 0; d < 9; ++d) sx[d][i] = row[d * plane + n0 + i];
       }
-      tr_wave_sync();
+      wave_sync();
       for (int j = 0; j < cn; ++j) {
         float xv[9];
 #pragma unroll
@@ -230,7 +225,7 @@ __global__ __launch_bounds__(kTrWaves * 64) void k_pfn_train_bwd(
         best = better ? r : best;
         best_n = better ? n0 + j : best_n;
       }
-      tr_wave_sync();
+      wave_sync();
     }
     const float gv = g[((int64_t)b * kTrC + lane) * P + p];
     acc[0] += gv;                                   // dbeta
@@ -277,15 +272,7 @@ extern "C" int pp_pfn_train_stats_dev(pp_ctx_t *ctx, void *stream_, const float 
     set_error("the feature-net kernels are built for %d output channels (got %d)", kTrC, channels);
     return PP_ERR_VALUE;
   }
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != ctx->device) (void)hipSetDevice(ctx->device);
-  struct Restore {
-    int prev, dev;
-    ~Restore() {
-      if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-  } restore{prev, ctx->device};
+  DeviceGuard guard(ctx->device);
   hipStream_t st = static_cast<hipStream_t>(stream_);
   const int64_t span = (int64_t)max_pillars * max_points_per_pillar;
   const int nwg = tr_grid(((span + kTrChunk - 1) / kTrChunk) * batch);
@@ -318,15 +305,7 @@ extern "C" int pp_pfn_train_backward_dev(pp_ctx_t *ctx, void *stream_, const flo
     set_error("the feature-net kernels are built for %d output channels (got %d)", kTrC, channels);
     return PP_ERR_VALUE;
   }
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != ctx->device) (void)hipSetDevice(ctx->device);
-  struct Restore {
-    int prev, dev;
-    ~Restore() {
-      if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-  } restore{prev, ctx->device};
+  DeviceGuard guard(ctx->device);
   hipStream_t st = static_cast<hipStream_t>(stream_);
   const int nwg = tr_grid((int64_t)batch * max_pillars);
   rc = ctx->pfn_ws.ensure((size_t)kTrMaxWg * kTrStats * kTrC * sizeof(float));

@@ -219,8 +219,7 @@ extern "C" int pp_ctx_create(int device, pp_ctx_t **out) {
 
 extern "C" void pp_ctx_destroy(pp_ctx_t *ctx) {
   if (!ctx) return;
-  int prev = -1;
-  if (hipGetDevice(&prev) == hipSuccess && prev != ctx->device) (void)hipSetDevice(ctx->device);
+  DeviceGuard guard(ctx->device);
   (void)hipDeviceSynchronize();
   for (auto &w : ctx->vox_ws) w.release();
   ctx->stage_in.release();
@@ -241,7 +240,6 @@ extern "C" void pp_ctx_destroy(pp_ctx_t *ctx) {
     for (auto &e : ctx->ev_start[k]) (void)hipEventDestroy(e);
     for (auto &e : ctx->ev_stop[k]) (void)hipEventDestroy(e);
   }
-  if (prev >= 0 && prev != ctx->device) (void)hipSetDevice(prev);
   delete ctx;
 }
 
@@ -289,9 +287,7 @@ extern "C" int pp_ctx_set_timing(pp_ctx_t *ctx, int slots) {
     set_error("pp_ctx_set_timing: bad argument");
     return PP_ERR_VALUE;
   }
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != ctx->device) (void)hipSetDevice(ctx->device);
+  DeviceGuard guard(ctx->device);
   for (int k = 0; k < 3; ++k) {
     for (auto &e : ctx->ev_start[k]) (void)hipEventDestroy(e);
     for (auto &e : ctx->ev_stop[k]) (void)hipEventDestroy(e);
@@ -315,7 +311,6 @@ extern "C" int pp_ctx_set_timing(pp_ctx_t *ctx, int slots) {
     }
   }
   if (rc == PP_OK) ctx->ev_slots = slots;
-  if (prev >= 0 && prev != ctx->device) (void)hipSetDevice(prev);
   return rc;
 }
 

@@ -411,20 +411,17 @@ extern "C" int pp_conv3x3_s2_pillars_nhwc_dev(pp_ctx_t *ctx, void *stream_, cons
   int *map = static_cast<int *>(scratch_dev);
   float *rows = reinterpret_cast<float *>(static_cast<char *>(scratch_dev) + map_bytes);
   const long long *idx = reinterpret_cast<const long long *>(indices_dev);
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != ctx->device) (void)hipSetDevice(ctx->device);
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  // persistent: two workgroups per compute unit (what the <64> instance's registers allow), shared among the
-  // channel groups (never more than there are tiles)
-  const int groups = out_channels / 64;
-  const int64_t resident = std::max<int64_t>(1, (int64_t)2 * compute_units(ctx->device) / groups);
-  const dim3 grid((unsigned)std::min(blocks, resident), (unsigned)groups);
-  const dim3 pgrid((unsigned)((max_pillars + 255) / 256), (unsigned)((in_channels + 63) / 64), (unsigned)batch);
-  hipLaunchKernelGGL(k_stem_prepare, pgrid, dim3(256), 0, st, features_dev, idx, map, rows, in_channels,
-                     max_pillars, canvas_h, canvas_w);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) {
+  return launch_on_device(ctx, "pp_conv3x3_s2_pillars_nhwc_dev", [&] {
+    hipStream_t st = static_cast<hipStream_t>(stream_);
+    // persistent: two workgroups per compute unit (what the <64> instance's registers allow), shared among the
+    // channel groups (never more than there are tiles)
+    const int groups = out_channels / 64;
+    const int64_t resident = std::max<int64_t>(1, (int64_t)2 * compute_units(ctx->device) / groups);
+    const dim3 grid((unsigned)std::min(blocks, resident), (unsigned)groups);
+    const dim3 pgrid((unsigned)((max_pillars + 255) / 256), (unsigned)((in_channels + 63) / 64), (unsigned)batch);
+    hipLaunchKernelGGL(k_stem_prepare, pgrid, dim3(256), 0, st, features_dev, idx, map, rows, in_channels,
+                       max_pillars, canvas_h, canvas_w);
+    if (hipPeekAtLastError() != hipSuccess) return;  // reported by the caller; no conv over an unprepared map
     if (in_channels == 64)
       hipLaunchKernelGGL(k_stem_conv<64>, grid, dim3(256), 0, st, map, idx, rows, w_taps_dev, params_dev, y_dev,
                          max_pillars, canvas_h, canvas_w, oh, ow, in_channels, out_channels, (int)tiles_x,
@@ -433,12 +430,5 @@ extern "C" int pp_conv3x3_s2_pillars_nhwc_dev(pp_ctx_t *ctx, void *stream_, cons
       hipLaunchKernelGGL(k_stem_conv<0>, grid, dim3(256), 0, st, map, idx, rows, w_taps_dev, params_dev, y_dev,
                          max_pillars, canvas_h, canvas_w, oh, ow, in_channels, out_channels, (int)tiles_x,
                          (int)tiles_y, (long long)blocks);
-    e = hipGetLastError();
-  }
-  if (prev >= 0 && prev != ctx->device) (void)hipSetDevice(prev);
-  if (e != hipSuccess) {
-    set_error("pp_conv3x3_s2_pillars_nhwc_dev launch failed: %s", hipGetErrorString(e));
-    return PP_ERR_HIP;
-  }
-  return PP_OK;
+  });
 }

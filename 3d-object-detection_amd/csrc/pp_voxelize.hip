@@ -72,13 +72,6 @@ struct NPoints {
   int n[PP_MAX_BATCH];
 };
 
-__device__ __forceinline__ void wave_sync() {
-  // LDS operations of one wave execute in program order; this only stops the
-  // compiler from moving LDS accesses across a cross-lane hand-off.
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // x mod ncells for x < 2^60 without a 64-bit division: q = floor(x * floor(2^64/n) / 2^64)
 // is the quotient or one less (Barrett), so at most one correction.
 __device__ __forceinline__ int mod_ncells(u64 x, const GridGeom &g) {

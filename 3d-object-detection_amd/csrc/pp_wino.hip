@@ -447,17 +447,9 @@ extern "C" int pp_conv3x3_wino_nhwc_dev(pp_ctx_t *ctx, void *stream_, const floa
     set_error("pp_conv3x3_wino_nhwc_dev: tensor too large");
     return PP_ERR_VALUE;
   }
-  hipError_t e;
-  {
-    DeviceGuard guard(ctx->device);
+  return launch_on_device(ctx, "k_conv3x3_wino", [&] {
     hipLaunchKernelGGL(k_conv3x3_wino, dim3((unsigned)blocks, (unsigned)(out_channels / 64)), dim3(256), 0,
                        static_cast<hipStream_t>(stream_), x_dev, u_dev, params_dev, y_dev + y_channel_offset,
                        height, width, in_channels, out_channels, y_channels, (int)tiles_x, (int)tiles_y);
-    e = hipGetLastError();      // the launch's, before the guard's own HIP call
-  }
-  if (e != hipSuccess) {
-    set_error("k_conv3x3_wino launch failed: %s", hipGetErrorString(e));
-    return PP_ERR_HIP;
-  }
-  return PP_OK;
+  });
 }
