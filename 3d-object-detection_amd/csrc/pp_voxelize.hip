@@ -1988,6 +1988,7 @@ struct VoxLayout {
 };
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
 
 VoxLayout vox_layout(int B, int64_t max_points, const GridGeom &g, int P, int rec_bytes) {
   VoxLayout l;
@@ -2037,157 +2038,172 @@ int prepare_ws(pp_ctx *ctx, hipStream_t stream, int B, int64_t max_points,
   return PP_OK;
 }
 
-template <typename TIn>
-int launch_pipeline(pp_ctx *ctx, hipStream_t stream, const TIn *pts, int64_t sweep_stride,
-                    int64_t s0, int64_t s1, int contig, const NPoints &np, int B,
-                    int maxn, const GridGeom &g, int P, int N, const VoxLayout &l,
-                    int mode, float *out, long long *idx_out, double *feat_out,
-                    bool timed, const float *pfn_w = nullptr, float *pfn_out = nullptr,
-                    float *canvas = nullptr, int canvas_h = 0, int canvas_w = 0,
-                    int canvas_nhwc = 0, const long long *prev_idx = nullptr, int feat_pack = 0,
-                    int4 *meta_direct = nullptr, int2 *totals_direct = nullptr) {
-  constexpr int slot = 0;  // the plain calls' workspace (k_step's batches rotate through the others)
-  using Rec = typename Rec4<TIn>::type;
+// a slot's arrays: the one place that turns a layout into pointers (the point records, float4 or double4, stay untyped)
+struct SlotArrays {
+  int *kslot;
+  void *kpts, *sorted_pts;
+  int2 *mat, *totals, *otot;
+  int4 *tile_meta, *meta;
+  u64 *tile_agg;
+};
+SlotArrays slot_arrays(pp_ctx *ctx, int slot, const VoxLayout &l) {
   char *ws = static_cast<char *>(ctx->vox_ws[slot].ptr);
-  int *kslot = reinterpret_cast<int *>(ws + l.kslot);
-  Rec *kpts = reinterpret_cast<Rec *>(ws + l.kpts);
-  int2 *mat = reinterpret_cast<int2 *>(ws + l.mat);
-  Rec *sorted_pts = reinterpret_cast<Rec *>(ws + l.sorted_pts);
-  int4 *tile_meta = reinterpret_cast<int4 *>(ws + l.tile_meta);
-  u64 *tile_agg = reinterpret_cast<u64 *>(ws + l.tile_agg);
-  int4 *meta = reinterpret_cast<int4 *>(ws + l.meta);
-  int2 *totals = reinterpret_cast<int2 *>(ws + l.totals);
+  SlotArrays a;
+  a.kslot = reinterpret_cast<int *>(ws + l.kslot);
+  a.kpts = ws + l.kpts;
+  a.mat = reinterpret_cast<int2 *>(ws + l.mat);
+  a.sorted_pts = ws + l.sorted_pts;
+  a.tile_meta = reinterpret_cast<int4 *>(ws + l.tile_meta);
+  a.tile_agg = reinterpret_cast<u64 *>(ws + l.tile_agg);
+  a.totals = reinterpret_cast<int2 *>(ws + l.totals);
+  a.otot = reinterpret_cast<int2 *>(ws + l.otot);
+  a.meta = reinterpret_cast<int4 *>(ws + l.meta);
+  return a;
+}
 
+// how the dense [9,P,N] tensor is stored: four slots per lane where N allows it
+int dense_emit_mode(int N) { return (N % 4 == 0 && N <= 4096) ? kModeDenseVec4 : kModeDenseScalar; }
+
+// Store policy of the dense tensor, by the bytes a launch of `sweeps` sweeps writes.  Write-through (sc1) stores leave
+// no dirty lines for the end-of-kernel write-back: on k_emit's store pattern alone (profiles/r02/NOTES.md) 43.2 MB take
+// 6.3 us against 7.4 us plain, 172.8 MB 20.8 / 22.6 us, 432 MB (beyond the Infinity Cache) 84 / 80 us.
+// In k_emit itself: 43.2 MB 10.4 / 11.5 us, 108 MB 21.5 / 22.0 us, 172.8 MB 29.3 / 29.0 us -- the
+// larger launches are not bound by their tail.  Write-through up to 128 MB.
+bool write_through(int sweeps, int P, int N) { return (size_t)sweeps * 36u * (size_t)P * (size_t)N <= kSc1MaxBytes; }
+
+// One dispatch per kernel family: f(the instance, its index within the family).
+template <typename TIn, class F>
+auto with_k_tile(int waves, F &&f) {
+  if (waves == 4) return f(&k_tile<TIn, 4>, 0);
+  if (waves == 8) return f(&k_tile<TIn, 8>, 1);
+  return f(&k_tile<TIn, 16>, 2);
+}
+template <typename TIn, class F>
+auto with_k_emit(int mode, bool sc1, F &&f) {
+  switch (mode) {
+    case kModeDenseVec4:
+      return sc1 ? f(&k_emit<TIn, kModeDenseVec4, kAuxSc1>, 0) : f(&k_emit<TIn, kModeDenseVec4, kAuxPlain>, 1);
+    case kModeDenseScalar: return f(&k_emit<TIn, kModeDenseScalar>, 2);
+    case kModePfn: return f(&k_emit<TIn, kModePfn>, 3);
+    default: return f(&k_emit<TIn, kModeCompact>, 4);
+  }
+}
+template <class F>
+auto with_k_step(int mode, bool sc1, F &&f) {
+  if (mode == kModePfn) return f(&k_step<kModePfn, kAuxPlain>, 0);
+  if (mode == kModeDenseScalar) return f(&k_step<kModeDenseScalar, kAuxPlain>, 1);
+  return sc1 ? f(&k_step<kModeDenseVec4, kAuxSc1>, 2) : f(&k_step<kModeDenseVec4, kAuxPlain>, 3);
+}
+
+// Dynamic LDS beyond 64 KiB needs the attribute.  hipFuncSetAttribute acts on the kernel function of
+// the DEVICE, whatever context asks: every instance is set ONCE per process and device, to its worst
+// case (the largest tile / the most split bins), so no context can ever lower another one's limit.
+// A device's word: bit = [f64 input][k_tile 4/8/16 waves | k_split], from kArmStep on k_step's four instances.
+enum { kArmSplit = 3, kArmF64 = 4, kArmStep = 8 };
+std::atomic<unsigned> lds_armed[64];  // per device
+int arm_dynamic_lds(const void *fn, unsigned bit, size_t worst_bytes, std::atomic<unsigned> &armed) {
+  if (armed.load(std::memory_order_acquire) & bit) return PP_OK;
+  PP_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)worst_bytes));
+  armed.fetch_or(bit, std::memory_order_release);
+  return PP_OK;
+}
+
+// Timing ring: the next entry, claimed for a call that records `columns` (bits PP_KERNEL_*).  The count starts again
+// when the ring held the other kind of call: a k_step entry has no split / tile pair and is no k_emit duration.
+int claim_timing_entry(pp_ctx *ctx, int columns) {
+  if (ctx->ev_columns != columns) ctx->ev_count = 0;
+  ctx->ev_columns = columns;
+  const int at = ctx->ev_next;
+  ctx->ev_next = (ctx->ev_next + 1) % ctx->ev_slots;
+  ctx->ev_count = std::min(ctx->ev_count + 1, ctx->ev_slots);
+  return at;
+}
+
+// After a launch.  On a failure whatever it was to write is unknown: `slot` is laid out (and cleared) again on the
+// next call; slot < 0 (k_step's launch): every batch in flight is dropped.
+int launch_result(pp_ctx *ctx, int slot) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return PP_OK;
+  if (slot >= 0) std::memset(ctx->vox_layout_key[slot], 0, sizeof ctx->vox_layout_key[slot]);
+  else for (auto &sb : ctx->step_batch) sb.valid = false;
+  set_error("voxelizer launch failed: %s", hipGetErrorString(e));
+  return PP_ERR_HIP;
+}
+
+// clearing the pixels that the batch with indices prev_idx wrote into canvas (all zero: nothing to clear)
+UnscatterArgs unscatter_args(const long long *prev_idx, float *canvas, int P, int h, int w, int nhwc) {
+  if (!canvas || !prev_idx) return UnscatterArgs{};
+  return UnscatterArgs{prev_idx, canvas, P, h, w, nhwc, (P + kUnscatterPixels - 1) / kUnscatterPixels};
+}
+
+// What varies between launch_pipeline's callers.  They zero-initialise it and fill, by name, the mode and in `e` that
+// mode's outputs (out / idx_out; feat_out, feat_pack, *_host; pfn_*, canvas*); launch_pipeline fills the rest of `e`.
+struct PipelineCall {
+  int mode;                   // kMode*
+  bool timed;                 // takes an entry of the timing ring (when the ring is armed)
+  const long long *prev_idx;  // fused feature-net form: the indices of the batch that filled e.canvas, or NULL
+  int32_t *num_cells;         // if not NULL: receives {cells, points} per sweep behind the launches
+  EmitArgs e;
+};
+
+// a plain call's three dependent launches, on workspace slot 0 (k_step's batches rotate through the others)
+template <typename TIn>
+int launch_pipeline(pp_ctx *ctx, hipStream_t stream, const TIn *pts, int64_t sweep_stride, const NPoints &np, int B,
+                    int maxn, const GridGeom &g, int P, int N, const VoxLayout &l, PipelineCall &c) {
+  constexpr int slot = 0;
+  constexpr unsigned arm_base = sizeof(TIn) == 8 ? kArmF64 : 0;
+  using Rec = typename Rec4<TIn>::type;
+  const SlotArrays w = slot_arrays(ctx, slot, l);
+  Rec *kpts = static_cast<Rec *>(w.kpts), *sorted_pts = static_cast<Rec *>(w.sorted_pts);
   // k_tile geometry: waves per tile from the mean population of a tile
   const long long per_tile = ((long long)maxn + g.ntiles - 1) / g.ntiles;
   const int tw = per_tile <= 96 ? 4 : per_tile <= (g.order == PP_ORDER_ROW_MAJOR ? 640 : 1024) ? 8 : 16;
-  const int wi = tw == 4 ? 0 : tw == 8 ? 1 : 2;
   const size_t lds_split = split_lds_bytes(g.ntiles);
   const size_t lds_tile = tile_lds_bytes(1 << g.tile_shift, tw);
-  // Dynamic LDS beyond 64 KiB needs the attribute.  hipFuncSetAttribute acts on the kernel function of
-  // the DEVICE, whatever context asks: every instance is set ONCE per process and device, to its worst
-  // case (the largest tile / the most split bins), so no context can ever lower another one's limit.
-  {
-    static std::atomic<unsigned> armed_mask[64];   // per device: bit = [f64 input][k_tile 4/8/16 waves | k_split]
-    const int dev = ctx->device & 63;
-    const unsigned bit_tile = 1u << ((sizeof(TIn) == 8 ? 4 : 0) + wi);
-    const unsigned bit_split = 1u << ((sizeof(TIn) == 8 ? 4 : 0) + 3);
-    if (!(armed_mask[dev].load(std::memory_order_acquire) & bit_tile)) {
-      const void *fn = tw == 4 ? reinterpret_cast<const void *>(&k_tile<TIn, 4>)
-                     : tw == 8 ? reinterpret_cast<const void *>(&k_tile<TIn, 8>)
-                               : reinterpret_cast<const void *>(&k_tile<TIn, 16>);
-      PP_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)tile_lds_bytes(kMaxTileSlots, tw)));
-      armed_mask[dev].fetch_or(bit_tile, std::memory_order_release);
-    }
-    if (!(armed_mask[dev].load(std::memory_order_acquire) & bit_split)) {
-      PP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_split<TIn>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)split_lds_bytes(kMaxTiles)));
-      armed_mask[dev].fetch_or(bit_split, std::memory_order_release);
-    }
-  }
+  std::atomic<unsigned> &armed = lds_armed[ctx->device & 63];
+  int rc = with_k_tile<TIn>(tw, [&](auto kern, int idx) {
+    return arm_dynamic_lds(reinterpret_cast<const void *>(kern), 1u << (arm_base + idx), tile_lds_bytes(kMaxTileSlots, tw),
+                           armed);
+  });
+  if (rc) return rc;
+  rc = arm_dynamic_lds(reinterpret_cast<const void *>(&k_split<TIn>), 1u << (arm_base + kArmSplit), split_lds_bytes(kMaxTiles),
+                       armed);
+  if (rc) return rc;
   const int nchunks = std::max(1, (maxn + kChunk - 1) / kChunk);
   // When the timing ring is armed every launch carries its own start/stop events
   // (hipExtLaunchKernelGGL binds them to the dispatch packet, so a pair brackets the
   // kernel alone, like a profiler's kernel trace, not the gaps around it).
   hipEvent_t ev0[3] = {nullptr, nullptr, nullptr}, ev1[3] = {nullptr, nullptr, nullptr};
-  if (timed && ctx->ev_slots > 0) {
-    for (int k = 0; k < 3; ++k) {
-      ev0[k] = ctx->ev_start[k][ctx->ev_next];
-      ev1[k] = ctx->ev_stop[k][ctx->ev_next];
-    }
-    if (ctx->ev_columns != 7) ctx->ev_count = 0;  // the ring held k_step launches: their entries have no split / tile pair
-    ctx->ev_next = (ctx->ev_next + 1) % ctx->ev_slots;
-    ctx->ev_count = std::min(ctx->ev_count + 1, ctx->ev_slots);
-    ctx->ev_columns = 7;  // all three kernels recorded
+  if (c.timed && ctx->ev_slots > 0) {
+    const int at = claim_timing_entry(ctx, 7);  // all three kernels recorded
+    for (int k = 0; k < 3; ++k) ev0[k] = ctx->ev_start[k][at], ev1[k] = ctx->ev_stop[k][at];
   }
   hipExtLaunchKernelGGL((k_split<TIn>), dim3((unsigned)nchunks, (unsigned)B), dim3(kSplitThreads),
                         lds_split, stream, ev0[PP_KERNEL_SPLIT], ev1[PP_KERNEL_SPLIT], 0, pts,
-                        sweep_stride, s0, s1, contig, np, g, l.ncap, l.nchunks_cap, kslot, kpts, mat);
-  UnscatterArgs un;
-  std::memset(&un, 0, sizeof un);
-  if (canvas && prev_idx) {
-    un.prev_idx = prev_idx;
-    un.canvas = canvas;
-    un.P = P;
-    un.h = canvas_h;
-    un.w = canvas_w;
-    un.nhwc = canvas_nhwc;
-    un.nblocks = (P + kUnscatterPixels - 1) / kUnscatterPixels;
-  }
-  auto launch_tile = [&](auto kern) {
+                        sweep_stride, 4, 1, 1, np, g, l.ncap, l.nchunks_cap, w.kslot, kpts, w.mat);
+  const UnscatterArgs un = unscatter_args(c.prev_idx, c.e.canvas, P, c.e.canvas_h, c.e.canvas_w, c.e.canvas_nhwc);
+  with_k_tile<TIn>(tw, [&](auto kern, int) {
     hipExtLaunchKernelGGL(kern, dim3((unsigned)(g.ntiles + un.nblocks), (unsigned)B), dim3(tw * kWave), lds_tile,
                           stream, ev0[PP_KERNEL_TILE], ev1[PP_KERNEL_TILE], 0, np, g, l.ncap,
-                          l.nchunks_cap, kslot, kpts, mat, sorted_pts, tile_meta, tile_agg, un);
-  };
-  if (tw == 4) launch_tile(&k_tile<TIn, 4>);
-  else if (tw == 8) launch_tile(&k_tile<TIn, 8>);
-  else launch_tile(&k_tile<TIn, 16>);
-  EmitArgs a;
+                          l.nchunks_cap, w.kslot, kpts, w.mat, sorted_pts, w.tile_meta, w.tile_agg, un);
+  });
+  EmitArgs &a = c.e;
   a.g = g;
   a.np = np;
   a.P = P;
   a.N = N;
   a.ncap = l.ncap;
-  a.tile_meta = tile_meta;
-  a.tile_agg = tile_agg;
-  a.pillar_meta = meta;
-  a.ordered_meta = nullptr;
-  a.ordered_totals = nullptr;
-  a.totals = totals;
+  a.tile_meta = w.tile_meta;
+  a.tile_agg = w.tile_agg;
+  a.pillar_meta = w.meta;
+  a.totals = w.totals;
   a.sorted_pts = sorted_pts;
-  a.out = out;
-  a.idx_out = idx_out;
-  a.feat_out = feat_out;
-  a.feat_pack = feat_pack;
-  a.pillar_meta_host = meta_direct;
-  a.totals_host = totals_direct;
-  a.pfn_w = pfn_w;
-  a.pfn_out = pfn_out;
-  a.canvas = canvas;
-  a.canvas_h = canvas_h;
-  a.canvas_w = canvas_w;
-  a.canvas_nhwc = canvas_nhwc;
   const dim3 grid_emit((unsigned)((P + KW * kEmitWaves - 1) / (KW * kEmitWaves)), (unsigned)B);
-  switch (mode) {
-    case kModeDenseVec4: {
-      // Store policy of the dense tensor.  Write-through (sc1) stores leave no dirty lines for the
-      // end-of-kernel write-back: on k_emit's store pattern alone (profiles/r02/NOTES.md) 43.2 MB take
-      // 6.3 us against 7.4 us plain, 172.8 MB 20.8 / 22.6 us, 432 MB (beyond the Infinity Cache) 84 / 80 us.
-      // In k_emit itself: 43.2 MB 10.4 / 11.5 us, 108 MB 21.5 / 22.0 us, 172.8 MB 29.3 / 29.0 us -- the
-      // larger launches are not bound by their tail.  Write-through up to 128 MB.
-      const bool sc1 = (size_t)B * 36u * (size_t)P * (size_t)N <= kSc1MaxBytes;
-      if (sc1)
-        hipExtLaunchKernelGGL((k_emit<TIn, kModeDenseVec4, kAuxSc1>), grid_emit, dim3(kEmitThreads), 0, stream,
-                              ev0[PP_KERNEL_EMIT], ev1[PP_KERNEL_EMIT], 0, a);
-      else
-        hipExtLaunchKernelGGL((k_emit<TIn, kModeDenseVec4, kAuxPlain>), grid_emit, dim3(kEmitThreads), 0, stream,
-                              ev0[PP_KERNEL_EMIT], ev1[PP_KERNEL_EMIT], 0, a);
-      break;
-    }
-    case kModeDenseScalar:
-      hipExtLaunchKernelGGL((k_emit<TIn, kModeDenseScalar>), grid_emit, dim3(kEmitThreads), 0, stream,
-                            ev0[PP_KERNEL_EMIT], ev1[PP_KERNEL_EMIT], 0, a);
-      break;
-    case kModePfn:
-      hipExtLaunchKernelGGL((k_emit<TIn, kModePfn>), grid_emit, dim3(kEmitThreads), 0, stream,
-                            ev0[PP_KERNEL_EMIT], ev1[PP_KERNEL_EMIT], 0, a);
-      break;
-    default:
-      hipExtLaunchKernelGGL((k_emit<TIn, kModeCompact>), grid_emit, dim3(kEmitThreads), 0, stream,
-                            ev0[PP_KERNEL_EMIT], ev1[PP_KERNEL_EMIT], 0, a);
-      break;
-  }
-  {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-      // whatever the slot holds is unknown now: lay it out (and clear it) again on the next call
-      std::memset(ctx->vox_layout_key[slot], 0, sizeof ctx->vox_layout_key[slot]);
-      set_error("voxelizer launch failed: %s", hipGetErrorString(e));
-      return PP_ERR_HIP;
-    }
-  }
+  with_k_emit<TIn>(c.mode, write_through(B, P, N), [&](auto kern, int) {
+    hipExtLaunchKernelGGL(kern, grid_emit, dim3(kEmitThreads), 0, stream, ev0[PP_KERNEL_EMIT], ev1[PP_KERNEL_EMIT], 0, a);
+  });
+  if ((rc = launch_result(ctx, slot)) != PP_OK) return rc;
+  if (c.num_cells) PP_HIP_TRY(hipMemcpyAsync(c.num_cells, w.totals, (size_t)B * 8, hipMemcpyDeviceToDevice, stream));
   return PP_OK;
 }
 
@@ -2218,6 +2234,49 @@ __global__ __launch_bounds__(kCopyThreads) void k_records_to_host(const int2 *to
   if (tid == 1 && a1 < b1) *reinterpret_cast<uint2 *>(dst + a1) = *reinterpret_cast<const uint2 *>(src + a1);
   for (long long o = a0 + tid * 16; o < a1; o += nthr * 16)
     *reinterpret_cast<uint4 *>(dst + o) = *reinterpret_cast<const uint4 *>(src + o);
+}
+
+// The points side of a device-pointer call -- batch, P and N, points_stride, n_points[], examined in that order --
+// into np and maxn.  dense: the call builds the [B,9,P,N] tensor, whose P*N is bounded (the fused forms never build it).
+int check_points_args(const char *what, int batch, const pp_voxel_params_t *prm, int64_t points_stride,
+                      const int32_t *n_points, bool dense, NPoints *np, int *maxn) {
+  if (batch < 1 || batch > PP_MAX_BATCH) {
+    set_error("%s: batch must be in [1,%d], got %d", what, PP_MAX_BATCH, batch);
+    return PP_ERR_VALUE;
+  }
+  const int P = prm->max_pillars, N = prm->max_points_per_pillar;
+  if (P < 1 || N < 1 || N > 65536 || (dense && (long long)P * N > 100000000ll)) {
+    set_error(dense ? "%s: need 1 <= max_pillars, 1 <= max_points_per_pillar <= 65536 and P*N <= 1e8 (got P=%d N=%d)"
+                    : "%s: need max_pillars >= 1 and 1 <= max_points_per_pillar <= 65536 (got P=%d N=%d)", what, P, N);
+    return PP_ERR_VALUE;
+  }
+  if (points_stride < 0 || points_stride > INT_MAX / 2) {
+    set_error("%s: points_stride out of range", what);
+    return PP_ERR_VALUE;
+  }
+  std::memset(np, 0, sizeof *np);
+  *maxn = 0;
+  for (int b = 0; b < batch; ++b) {
+    if (n_points[b] < 0 || n_points[b] > points_stride) {
+      set_error("%s: n_points[%d]=%d outside [0, points_stride=%lld]", what, b, n_points[b], (long long)points_stride);
+      return PP_ERR_VALUE;
+    }
+    np->n[b] = n_points[b];
+    *maxn = std::max(*maxn, n_points[b]);
+  }
+  return PP_OK;
+}
+
+// ... and its pointers by class: accessed 16 bytes a lane (points, pillars, features), 8-byte elements (indices,
+// num_cells), floats (the feature net's parameters); `which` names them in the message.  NULL passes: checked apart.
+bool misaligned(const void *p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
+int check_alignment(const char *what, const char *which, const void *vec_a, const void *vec_b, const void *i64_a,
+                    const void *i64_b, const void *f32 = nullptr) {
+  if (misaligned(vec_a, 16) || misaligned(vec_b, 16) || misaligned(i64_a, 8) || misaligned(i64_b, 8) || misaligned(f32, 4)) {
+    set_error("%s: device pointers must be %s aligned", what, which);
+    return PP_ERR_VALUE;
+  }
+  return PP_OK;
 }
 
 }  // namespace
@@ -2272,119 +2331,29 @@ extern "C" int pp_voxelize_dev(pp_ctx_t *ctx, void *stream_, const float *points
     set_error("pp_voxelize_dev: NULL argument");
     return PP_ERR_VALUE;
   }
-  if (batch < 1 || batch > PP_MAX_BATCH) {
-    set_error("batch must be in [1,%d], got %d", PP_MAX_BATCH, batch);
-    return PP_ERR_VALUE;
-  }
-  const int P = prm->max_pillars, N = prm->max_points_per_pillar;
-  if (P < 1 || N < 1 || N > 65536 || (long long)P * N > 100000000ll) {
-    set_error("need 1 <= max_pillars, 1 <= max_points_per_pillar <= 65536 and P*N <= 1e8 "
-              "(got P=%d N=%d)", P, N);
-    return PP_ERR_VALUE;
-  }
-  if (points_stride < 0 || points_stride > INT_MAX / 2) {
-    set_error("points_stride out of range");
-    return PP_ERR_VALUE;
-  }
   NPoints np;
-  std::memset(&np, 0, sizeof np);
   int maxn = 0;
-  for (int b = 0; b < batch; ++b) {
-    if (n_points[b] < 0 || n_points[b] > points_stride) {
-      set_error("n_points[%d]=%d outside [0, points_stride=%lld]", b, n_points[b],
-                (long long)points_stride);
-      return PP_ERR_VALUE;
-    }
-    np.n[b] = n_points[b];
-    maxn = std::max(maxn, n_points[b]);
-  }
-  if ((reinterpret_cast<uintptr_t>(points_dev) & 15) || (reinterpret_cast<uintptr_t>(pillars_dev) & 15) ||
-      (reinterpret_cast<uintptr_t>(indices_dev) & 7)) {
-    set_error("device pointers must be 16-byte (points, pillars) / 8-byte (indices) aligned");
-    return PP_ERR_VALUE;
-  }
+  const char *what = "pp_voxelize_dev";
+  if (int rc = check_points_args(what, batch, prm, points_stride, n_points, true, &np, &maxn)) return rc;
+  if (int rc = check_alignment(what, "16-byte (points, pillars) / 8-byte (indices)", points_dev, pillars_dev, indices_dev, nullptr))
+    return rc;
+  const int P = prm->max_pillars, N = prm->max_points_per_pillar;
   GridGeom g;
-  int rc = make_grid(prm, &g);
-  if (rc) return rc;
+  if (int rc = make_grid(prm, &g)) return rc;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   DeviceGuard guard(ctx->device);
   VoxLayout l;
-  rc = prepare_ws(ctx, stream, batch, std::max<int64_t>(points_stride, 1), g, P, 16, &l);
-  if (rc) return rc;
-  const int mode = (N % 4 == 0 && N <= 4096) ? kModeDenseVec4 : kModeDenseScalar;
-  rc = launch_pipeline<float>(ctx, stream, points_dev, points_stride, 4, 1, 1, np, batch, maxn,
-                              g, P, N, l, mode, pillars_dev,
-                              reinterpret_cast<long long *>(indices_dev), nullptr, true);
-  if (rc) return rc;
-  if (num_cells_dev) {
-    char *ws = static_cast<char *>(ctx->vox_ws[0].ptr);
-    PP_HIP_TRY(hipMemcpyAsync(num_cells_dev, ws + l.totals, (size_t)batch * 8,
-                              hipMemcpyDeviceToDevice, stream));
-  }
-  return PP_OK;
-}
-
-static int check_dev_args(const char *what, int batch, const pp_voxel_params_t *prm, int64_t points_stride,
-                          const int32_t *n_points, NPoints *np, int *maxn) {
-  if (batch < 1 || batch > PP_MAX_BATCH) {
-    set_error("%s: batch must be in [1,%d], got %d", what, PP_MAX_BATCH, batch);
-    return PP_ERR_VALUE;
-  }
-  const int P = prm->max_pillars, N = prm->max_points_per_pillar;
-  if (P < 1 || N < 1 || N > 65536 || (long long)P * N > 100000000ll) {
-    set_error("%s: need 1 <= max_pillars, 1 <= max_points_per_pillar <= 65536 and P*N <= 1e8 "
-              "(got P=%d N=%d)", what, P, N);
-    return PP_ERR_VALUE;
-  }
-  if (points_stride < 0 || points_stride > INT_MAX / 2) {
-    set_error("%s: points_stride out of range", what);
-    return PP_ERR_VALUE;
-  }
-  std::memset(np, 0, sizeof *np);
-  *maxn = 0;
-  for (int b = 0; b < batch; ++b) {
-    if (n_points[b] < 0 || n_points[b] > points_stride) {
-      set_error("%s: n_points[%d]=%d outside [0, points_stride=%lld]", what, b, n_points[b],
-                (long long)points_stride);
-      return PP_ERR_VALUE;
-    }
-    np->n[b] = n_points[b];
-    *maxn = std::max(*maxn, n_points[b]);
-  }
-  return PP_OK;
+  if (int rc = prepare_ws(ctx, stream, batch, std::max<int64_t>(points_stride, 1), g, P, 16, &l)) return rc;
+  PipelineCall c{};
+  c.mode = dense_emit_mode(N);
+  c.timed = true;
+  c.e.out = pillars_dev;
+  c.e.idx_out = reinterpret_cast<long long *>(indices_dev);
+  c.num_cells = num_cells_dev;
+  return launch_pipeline<float>(ctx, stream, points_dev, points_stride, np, batch, maxn, g, P, N, l, c);
 }
 
 /* ---- software-pipelined mode: one k_step launch per call ---- */
-namespace {
-struct SlotArrays {
-  int *kslot;
-  float4 *kpts, *sorted_pts;
-  int2 *mat, *totals, *otot;
-  int4 *tile_meta, *meta;
-  u64 *tile_agg;
-};
-SlotArrays slot_arrays(pp_ctx *ctx, int slot, const VoxLayout &l) {
-  char *ws = static_cast<char *>(ctx->vox_ws[slot].ptr);
-  SlotArrays a;
-  a.kslot = reinterpret_cast<int *>(ws + l.kslot);
-  a.kpts = reinterpret_cast<float4 *>(ws + l.kpts);
-  a.mat = reinterpret_cast<int2 *>(ws + l.mat);
-  a.sorted_pts = reinterpret_cast<float4 *>(ws + l.sorted_pts);
-  a.tile_meta = reinterpret_cast<int4 *>(ws + l.tile_meta);
-  a.tile_agg = reinterpret_cast<u64 *>(ws + l.tile_agg);
-  a.totals = reinterpret_cast<int2 *>(ws + l.totals);
-  a.otot = reinterpret_cast<int2 *>(ws + l.otot);
-  a.meta = reinterpret_cast<int4 *>(ws + l.meta);
-  return a;
-}
-int step_geometry(const pp_step_batch &sb, GridGeom *g, VoxLayout *l) {
-  int rc = make_grid(&sb.prm, g, 1);
-  if (rc) return rc;
-  *l = vox_layout(sb.batch, std::max<int64_t>(sb.points_stride, 1), *g, sb.prm.max_pillars, 16);
-  return PP_OK;
-}
-}  // namespace
-
 namespace {
 // the emit role as the fused feature net (pp_voxelize_step_pfn_canvas_dev): canvas instead of the dense tensor
 struct StepPfn {
@@ -2395,11 +2364,274 @@ struct StepPfn {
   const int64_t *clear_indices;   // ... and the indices of the batch that filled it: its non-zero pixels
   int clear_batch;
 };
-}  // namespace
+// a call's arguments, in the entry points' order: the new batch (points NULL: none) and where the due batch goes
+struct StepCall {
+  const float *points;
+  int64_t points_stride;
+  const int32_t *n_points;
+  int batch;
+  const pp_voxel_params_t *prm;
+  float *pillars;        // the dense form's tensor, or ...
+  const StepPfn *pfn;    // ... the fused feature net's canvases
+  int64_t *indices;
+  int32_t *num_cells;
+};
+struct StepSlot { GridGeom g; VoxLayout l; SlotArrays w; };  // a batch's grid, its slot's layout and arrays
+// lay_out (the new batch): the slot's last batch was emitted by the previous launch, so resizing / clearing it is
+// stream-ordered
+int step_slot(pp_ctx *ctx, const pp_step_batch &sb, StepSlot *s, bool lay_out = false, hipStream_t stream = nullptr) {
+  int rc = make_grid(&sb.prm, &s->g, 1);
+  if (rc) return rc;
+  const int64_t max_points = std::max<int64_t>(sb.points_stride, 1);
+  s->l = vox_layout(sb.batch, max_points, s->g, sb.prm.max_pillars, 16);
+  VoxLayout same;
+  if (lay_out && (rc = prepare_ws(ctx, stream, sb.batch, max_points, s->g, sb.prm.max_pillars, 16, &same, sb.slot))) return rc;
+  s->w = slot_arrays(ctx, sb.slot, s->l);
+  return PP_OK;
+}
 
-static int step_impl(pp_ctx_t *ctx, void *stream_, const float *points_dev, int64_t points_stride,
-                     const int32_t *n_points, int batch, const pp_voxel_params_t *prm, float *pillars_dev,
-                     int64_t *indices_dev, int32_t *num_cells_dev, int *emitted, const StepPfn *pfn) {
+// Refusals by the batches in flight.  (ctx->step_stream is set where the call can no longer be refused: every
+// PP_ERR_VALUE of step_impl leaves the context as it was.)
+int step_check_in_flight(const pp_ctx *ctx, hipStream_t stream, const StepCall &c) {
+  const pp_step_batch &sb_tile = ctx->step_batch[0], &sb_order = ctx->step_batch[1], &sb_emit = ctx->step_batch[2];
+  // Stream order is what carries a batch from one role to the next: a call on another stream while batches
+  // are in flight would race with the launch that wrote what it reads.
+  if ((sb_tile.valid || sb_order.valid || sb_emit.valid) && stream != ctx->step_stream) {
+    set_error("pp_voxelize_step_dev: pipeline in flight on another stream (drain it, or pp_voxelize_step_reset)");
+    return PP_ERR_VALUE;
+  }
+  const StepPfn *pfn = c.pfn;
+  if (!sb_emit.valid) return PP_OK;
+  if (!(pfn ? (void *)pfn->canvas : (void *)c.pillars) || !c.indices) {
+    set_error("pp_voxelize_step*_dev: a batch is due, its output buffers are NULL");
+    return PP_ERR_VALUE;
+  }
+  if (pfn && (!pfn->params || misaligned(pfn->canvas, 16) || pfn->h < 1 || pfn->w < 1 ||
+              (double)pfn->h != sb_emit.prm.canvas_height)) {
+    set_error("pp_voxelize_step_pfn_canvas_dev: canvas %dx%d: height must equal the due batch's canvas_height=%g "
+              "(16-byte aligned tensor, parameters not NULL)", pfn->h, pfn->w, sb_emit.prm.canvas_height);
+    return PP_ERR_VALUE;
+  }
+  return check_alignment("pp_voxelize_step*_dev", "16-byte (pillars) / 8-byte (indices, num_cells)", c.pillars, nullptr,
+                         c.indices, c.num_cells);
+}
+
+// the new batch's record from the call's arguments (left invalid: the call brings none), or the refusal
+int step_new_batch(const pp_ctx *ctx, const StepCall &c, pp_step_batch *sb) {
+  if (!c.points) return PP_OK;
+  if (!c.n_points || !c.prm) {
+    set_error("pp_voxelize_step_dev: NULL argument");
+    return PP_ERR_VALUE;
+  }
+  const char *what = "pp_voxelize_step_dev";
+  if (int rc = check_alignment(what, "16-byte (points)", c.points, nullptr, nullptr, nullptr)) return rc;
+  NPoints np;
+  if (int rc = check_points_args(what, c.batch, c.prm, c.points_stride, c.n_points, true, &np, &sb->maxn)) return rc;
+  sb->valid = true;
+  sb->batch = c.batch;
+  std::memcpy(sb->n_points, np.n, sizeof sb->n_points);
+  sb->points_stride = c.points_stride;
+  sb->prm = *c.prm;
+  sb->slot = ctx->step_next_slot;
+  return PP_OK;
+}
+
+// The role fillers: a batch's geometry and slot arrays, once, into its role of the launch; *lds grows to the role's
+// need.  A batch that is not valid leaves its role empty.
+int fill_split_role(pp_ctx *ctx, hipStream_t stream, const pp_step_batch &sb, const float *points, StepArgs *a, size_t *lds) {
+  if (!sb.valid) return PP_OK;
+  StepSlot s;
+  if (int rc = step_slot(ctx, sb, &s, true, stream)) return rc;
+  a->s.pts = points;
+  a->s.sweep_stride = sb.points_stride;
+  std::memcpy(a->s.np.n, sb.n_points, sizeof a->s.np.n);
+  a->s.g = s.g;
+  a->s.ncap = s.l.ncap;
+  a->s.nchunks_cap = s.l.nchunks_cap;
+  a->s.nchunks = std::max(1, (sb.maxn + kChunk - 1) / kChunk);
+  a->s.kslot = s.w.kslot;
+  a->s.kpts = s.w.kpts;
+  a->s.mat = s.w.mat;
+  a->n_split_blocks = a->s.nchunks * sb.batch;
+  *lds = std::max(*lds, split_lds_bytes(s.g.ntiles));
+  return PP_OK;
+}
+int fill_tile_role(pp_ctx *ctx, const pp_step_batch &sb, StepArgs *a, size_t *lds) {
+  if (!sb.valid) return PP_OK;
+  StepSlot s;
+  if (int rc = step_slot(ctx, sb, &s)) return rc;
+  std::memcpy(a->t.np.n, sb.n_points, sizeof a->t.np.n);
+  a->t.g = s.g;
+  a->t.ncap = s.l.ncap;
+  a->t.nchunks_cap = s.l.nchunks_cap;
+  a->t.kslot = s.w.kslot;
+  a->t.kpts = s.w.kpts;
+  a->t.mat = s.w.mat;
+  a->t.sorted_pts = s.w.sorted_pts;
+  a->t.tile_meta = s.w.tile_meta;
+  a->t.tile_agg = s.w.tile_agg;
+  a->n_tile_blocks = s.g.ntiles * sb.batch;
+  *lds = std::max(*lds, tile_lds_bytes(1 << s.g.tile_shift, kStepWaves));
+  return PP_OK;
+}
+int fill_order_role(pp_ctx *ctx, const pp_step_batch &sb, StepArgs *a) {  // (no LDS)
+  if (!sb.valid) return PP_OK;
+  StepSlot s;
+  if (int rc = step_slot(ctx, sb, &s)) return rc;
+  a->o.g = s.g;
+  a->o.P = sb.prm.max_pillars;
+  a->o.B = sb.batch;
+  a->o.tile_meta = s.w.tile_meta;
+  a->o.tile_agg = s.w.tile_agg;
+  a->o.ordered_meta = s.w.meta;
+  a->o.ordered_totals = s.w.otot;
+  a->n_order_blocks = (s.g.ntiles * sb.batch + kEmitWaves - 1) / kEmitWaves;   // one wave per (sweep, tile)
+  return PP_OK;
+}
+// ... the emit role, into the call's outputs; *mode: which k_step instance emits
+int fill_emit_role(pp_ctx *ctx, const pp_step_batch &sb, const StepCall &c, StepArgs *a, size_t *lds, int *mode) {
+  if (!sb.valid) return PP_OK;
+  StepSlot s;
+  if (int rc = step_slot(ctx, sb, &s)) return rc;
+  const StepPfn *pfn = c.pfn;
+  const int P = sb.prm.max_pillars, N = sb.prm.max_points_per_pillar;
+  a->e.g = s.g;
+  std::memcpy(a->e.np.n, sb.n_points, sizeof a->e.np.n);
+  a->e.P = P;
+  a->e.N = N;
+  a->e.ncap = s.l.ncap;
+  a->e.tile_meta = s.w.tile_meta;
+  a->e.tile_agg = s.w.tile_agg;
+  a->e.totals = c.num_cells ? reinterpret_cast<int2 *>(c.num_cells) : s.w.totals;
+  a->e.ordered_meta = s.w.meta;
+  a->e.ordered_totals = s.w.otot;
+  a->e.sorted_pts = s.w.sorted_pts;
+  a->e.out = c.pillars;
+  a->e.idx_out = reinterpret_cast<long long *>(c.indices);
+  a->emit_nbx = (P + KW * kEmitWaves - 1) / (KW * kEmitWaves);
+  *mode = dense_emit_mode(N);
+  *lds = std::max(*lds, pfn ? sizeof(WaveLds<float, emit_cap(kModePfn)>) * kEmitWaves : sizeof(WaveLds<float>) * kEmitWaves);
+  if (pfn) {
+    *mode = kModePfn;
+    a->e.out = nullptr;
+    a->e.pfn_w = pfn->params;
+    a->e.pfn_out = nullptr;
+    a->e.canvas = pfn->canvas;
+    a->e.canvas_h = pfn->h;
+    a->e.canvas_w = pfn->w;
+    a->e.canvas_nhwc = pfn->nhwc;
+  }
+  return PP_OK;
+}
+// ... and the fused feature-net form's clear role
+int fill_clear_role(const StepPfn *pfn, const pp_step_batch &sb_emit, StepArgs *a) {
+  if (!(pfn && pfn->clear_canvas && pfn->clear_indices && pfn->clear_batch > 0)) return PP_OK;
+  // the other canvas: only the pixels its last batch wrote are non-zero (same geometry as the due batch's)
+  if (misaligned(pfn->clear_canvas, 16) || misaligned(pfn->clear_indices, 8) || pfn->clear_batch > PP_MAX_BATCH ||
+      !sb_emit.valid) {
+    set_error("pp_voxelize_step_pfn_canvas_dev: bad clear arguments (alignment, batch <= %d, and a batch must be due "
+              "whose shapes describe the canvas)", PP_MAX_BATCH);
+    return PP_ERR_VALUE;
+  }
+  a->un = unscatter_args(reinterpret_cast<const long long *>(pfn->clear_indices), pfn->clear_canvas,
+                         sb_emit.prm.max_pillars, pfn->h, pfn->w, pfn->nhwc);
+  a->n_unscatter_blocks = a->un.nblocks * pfn->clear_batch;
+  return PP_OK;
+}
+
+// A call CAN go out as several launches of a few sweeps each (sweeps are independent, so every role's
+// batch splits the same way).  Round 3's driver line suggested it should when the dense output exceeds the
+// 256 MB Infinity Cache: per sweep, one 172.8 MB sweep per launch ran at 0.73 of the roofline, four in
+// one launch at 0.64.  Measured in round 4 (profiles/r04/NOTES.md): four launches of one sweep each take
+// 154 us against 146 us for the one launch -- the one-sweep figure came from re-writing the SAME 172.8 MB
+// buffer call after call, which the memory-side cache absorbs; four launches writing four different
+// regions go to HBM like the single launch does, and pay three more launch ramps.  Default: one launch.
+int step_launch_count(const pp_step_batch &sb_emit, bool pfn) {
+  // PP_STEP_SUB_MB: dense MB per launch (0 = never split); the test of the split form sets it
+  static const size_t sub_bytes = (size_t)std::max(0, env_int("PP_STEP_SUB_MB", (int)(kStepLaunchBytes >> 20))) << 20;
+  if (!sb_emit.valid || !sub_bytes || pfn) return 1;
+  const size_t per_sweep = 36u * (size_t)sb_emit.prm.max_pillars * (size_t)sb_emit.prm.max_points_per_pillar;
+  const int per_launch = (int)std::max<size_t>(1, sub_bytes / std::max<size_t>(per_sweep, 1));
+  return (sb_emit.batch + per_launch - 1) / per_launch;
+}
+
+// The share of launch k of n_launch, from the whole call's arguments into a: sweeps [lo, lo + n) of each role's batch
+// (split, tile, order, emit), the roles' block counts and the prefetch list.  Returns the emit role's sweeps.
+int step_share(const StepArgs &whole, const pp_step_batch *const (&role)[4], int k, int n_launch, StepArgs &a) {
+  int lo[4], n[4];
+  for (int r = 0; r < 4; ++r) {
+    lo[r] = role[r]->valid ? (int)((long long)role[r]->batch * k / n_launch) : 0;
+    n[r] = role[r]->valid ? (int)((long long)role[r]->batch * (k + 1) / n_launch) - lo[r] : 0;
+  }
+  a = whole;
+  a.split_b0 = lo[0];
+  a.n_split_blocks = role[0]->valid ? whole.s.nchunks * n[0] : 0;
+  a.tile_b0 = lo[1];
+  a.n_tile_blocks = (role[1]->valid ? whole.t.g.ntiles : 0) * n[1];
+  a.o.b0 = lo[2];
+  a.o.B = n[2];
+  a.n_order_blocks = ((role[2]->valid ? whole.o.g.ntiles : 0) * n[2] + kEmitWaves - 1) / kEmitWaves;   // one wave per (sweep, tile)
+  a.emit_b0 = lo[3];
+  int r = 0;
+  auto add = [&](const void *ptr, size_t per_sweep) {
+    a.pf.ptr[r] = static_cast<const char *>(ptr) + per_sweep * (size_t)lo[3];
+    a.pf.n16[r] = (unsigned)(per_sweep * (size_t)n[3] / 16);
+    ++r;
+  };
+  std::memset(&a.pf, 0, sizeof a.pf);
+  // Only the EMIT role's arrays are worth it (round 4, profiles/r04/NOTES.md): its blocks start after the
+  // binning blocks, so the lines are there when they ask.  The binning roles' own inputs (the order role's
+  // lists, the tile role's split arrays, the split role's points) were in this list while binning and emit
+  // blocks alternated; with the binning blocks FIRST they start in the same microsecond as the prefetch
+  // blocks and fetch for themselves -- the prefetch only doubled that traffic (headline 34.9 -> 33.7 us
+  // without, C5 B=4 111-118 -> 104-109 us).
+  if (n[3] > 0) {   // what the emit role reads
+    add(a.e.ordered_meta, (size_t)a.e.P * 16);
+    add(a.e.sorted_pts, (size_t)a.e.ncap * 16);
+  }
+  a.n_pref_blocks = r > 0 ? kStepPrefetchBlocks : 0;
+  return n[3];
+}
+
+// block-order policy of a launch with n_emit emit blocks: a.mix, a.mix_groups
+void step_block_order(StepArgs &a, int n_emit) {
+  const int nbin = a.n_tile_blocks + a.n_order_blocks + a.n_split_blocks;
+  // Default: every binning block ahead of the emit blocks.  After a network pass (the real caller: a GiB of
+  // activations between two launches) the binning roles' chains run on cold lines and are the launch's
+  // tail unless they start first: 39 -> 35 us in bench.py's end-to-end loop; in a voxelizer-only loop, where
+  // their inputs are still cached, the 1:1 interleave (mix 2) was 2 us better (42.4 vs 40.6 us, round 4).
+  // More binning blocks than the chip holds at once (5 workgroups per CU): "first" would mean rounds of
+  // binning with no store in flight -- they are spread evenly over the launch instead, one per
+  // n_emit / nbin emit blocks (C5 B=4, 3 400 binning blocks against 7 500: one per two, 117-121 -> 104-109 us;
+  // one per one and one per three are both worse).
+  const int mix_auto = nbin > kStepChipSlots && n_emit > 0 ? std::max(2, n_emit / nbin + 1) : 1;
+  a.mix = mix_auto;
+  a.mix_groups = a.mix > 1 ? std::min(nbin, n_emit / (a.mix - 1)) : 0;
+  if (a.mix < 2) a.mix = 2, a.mix_groups = 0;
+}
+
+// one k_step launch of nblocks workgroups, the first and / or last of its call
+int launch_step(pp_ctx *ctx, hipStream_t stream, const StepArgs &a, int mode, bool sc1, size_t lds, long long nblocks,
+                bool first, bool last) {
+  return with_k_step(mode, sc1, [&](auto kern, int idx) -> int {
+    // dynamic LDS beyond 64 KiB (16.7 M-cell grids) needs the attribute: once per process, device and
+    // instance, at the worst case
+    const size_t worst = std::max(std::max(tile_lds_bytes(kMaxTileSlots, kStepWaves), split_lds_bytes(kMaxTiles)),
+                                  sizeof(WaveLds<float>) * kEmitWaves);
+    std::atomic<unsigned> &armed = lds_armed[ctx->device & 63];
+    if (int rc = arm_dynamic_lds(reinterpret_cast<const void *>(kern), 1u << (kArmStep + idx), worst, armed)) return rc;
+    // timing ring: ONE entry per call -- the start event rides on the call's first launch, the stop event on
+    // its last, so the entry is what the call's launches took together (bench.py's per-call duration); it is claimed
+    // with the last launch, the first one's start event is that of the entry to come
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (ctx->ev_slots > 0 && first) e0 = ctx->ev_start[PP_KERNEL_EMIT][ctx->ev_next];
+    if (ctx->ev_slots > 0 && last) e1 = ctx->ev_stop[PP_KERNEL_EMIT][claim_timing_entry(ctx, 1 << PP_KERNEL_EMIT)];
+    hipExtLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(kStepThreads), lds, stream, e0, e1, 0, a);
+    return launch_result(ctx, -1);
+  });
+}
+
+int step_impl(pp_ctx_t *ctx, void *stream_, const StepCall &c, int *emitted) {
   if (emitted) *emitted = 0;
   if (!ctx) {
     set_error("ctx is NULL");
@@ -2408,251 +2640,36 @@ static int step_impl(pp_ctx_t *ctx, void *stream_, const float *points_dev, int6
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   DeviceGuard guard(ctx->device);
   pp_step_batch &sb_tile = ctx->step_batch[0], &sb_order = ctx->step_batch[1], &sb_emit = ctx->step_batch[2];
-  // Stream order is what carries a batch from one role to the next: a call on another stream while batches
-  // are in flight would race with the launch that wrote what it reads.
-  if ((sb_tile.valid || sb_order.valid || sb_emit.valid) && stream != ctx->step_stream) {
-    set_error("pp_voxelize_step_dev: pipeline in flight on another stream (drain it, or pp_voxelize_step_reset)");
-    return PP_ERR_VALUE;
-  }
-  // (ctx->step_stream is set where the call can no longer be refused: every PP_ERR_VALUE below leaves the context as it was)
-  if (sb_emit.valid) {
-    if (!(pfn ? (void *)pfn->canvas : (void *)pillars_dev) || !indices_dev) {
-      set_error("pp_voxelize_step*_dev: a batch is due, its output buffers are NULL");
-      return PP_ERR_VALUE;
-    }
-    if (pfn && (!pfn->params || (reinterpret_cast<uintptr_t>(pfn->canvas) & 15) || pfn->h < 1 || pfn->w < 1 ||
-                (double)pfn->h != sb_emit.prm.canvas_height)) {
-      set_error("pp_voxelize_step_pfn_canvas_dev: canvas %dx%d: height must equal the due batch's canvas_height=%g "
-                "(16-byte aligned tensor, parameters not NULL)", pfn->h, pfn->w, sb_emit.prm.canvas_height);
-      return PP_ERR_VALUE;
-    }
-    if ((reinterpret_cast<uintptr_t>(pillars_dev) & 15) || (reinterpret_cast<uintptr_t>(indices_dev) & 7) ||
-        (reinterpret_cast<uintptr_t>(num_cells_dev) & 7)) {
-      set_error("device pointers must be 16-byte (pillars) / 8-byte (indices, num_cells) aligned");
-      return PP_ERR_VALUE;
-    }
-  }
-  StepArgs a;
-  std::memset(&a, 0, sizeof a);
-  size_t lds = 0;
-  int rc;
-  // split role: the new batch
   pp_step_batch sb_new;
-  if (points_dev) {
-    if (!n_points || !prm) {
-      set_error("pp_voxelize_step_dev: NULL argument");
-      return PP_ERR_VALUE;
-    }
-    if (reinterpret_cast<uintptr_t>(points_dev) & 15) {
-      set_error("device pointers must be 16-byte aligned (points)");
-      return PP_ERR_VALUE;
-    }
-    NPoints np;
-    int maxn = 0;
-    rc = check_dev_args("pp_voxelize_step_dev", batch, prm, points_stride, n_points, &np, &maxn);
-    if (rc) return rc;
-    sb_new.valid = true;
-    sb_new.batch = batch;
-    sb_new.maxn = maxn;
-    std::memcpy(sb_new.n_points, np.n, sizeof sb_new.n_points);
-    sb_new.points_stride = points_stride;
-    sb_new.prm = *prm;
-    sb_new.slot = ctx->step_next_slot;
-    GridGeom g;
-    VoxLayout l;
-    rc = step_geometry(sb_new, &g, &l);
-    if (rc) return rc;
-    // the slot's last batch was emitted by the previous launch: resizing / clearing it is stream-ordered
-    VoxLayout l2;
-    rc = prepare_ws(ctx, stream, batch, std::max<int64_t>(points_stride, 1), g, prm->max_pillars, 16, &l2,
-                    sb_new.slot);
-    if (rc) return rc;
-    const SlotArrays w = slot_arrays(ctx, sb_new.slot, l);
-    a.s.pts = points_dev;
-    a.s.sweep_stride = points_stride;
-    a.s.np = np;
-    a.s.g = g;
-    a.s.ncap = l.ncap;
-    a.s.nchunks_cap = l.nchunks_cap;
-    a.s.nchunks = std::max(1, (maxn + kChunk - 1) / kChunk);
-    a.s.kslot = w.kslot;
-    a.s.kpts = w.kpts;
-    a.s.mat = w.mat;
-    a.n_split_blocks = a.s.nchunks * batch;
-    lds = std::max(lds, split_lds_bytes(g.ntiles));
-  }
-  if (sb_tile.valid) {
-    GridGeom g;
-    VoxLayout l;
-    rc = step_geometry(sb_tile, &g, &l);
-    if (rc) return rc;
-    const SlotArrays w = slot_arrays(ctx, sb_tile.slot, l);
-    std::memcpy(a.t.np.n, sb_tile.n_points, sizeof a.t.np.n);
-    a.t.g = g;
-    a.t.ncap = l.ncap;
-    a.t.nchunks_cap = l.nchunks_cap;
-    a.t.kslot = w.kslot;
-    a.t.kpts = w.kpts;
-    a.t.mat = w.mat;
-    a.t.sorted_pts = w.sorted_pts;
-    a.t.tile_meta = w.tile_meta;
-    a.t.tile_agg = w.tile_agg;
-    a.n_tile_blocks = g.ntiles * sb_tile.batch;
-    lds = std::max(lds, tile_lds_bytes(1 << g.tile_shift, kStepWaves));
-  }
-  if (sb_order.valid) {
-    GridGeom g;
-    VoxLayout l;
-    rc = step_geometry(sb_order, &g, &l);
-    if (rc) return rc;
-    const SlotArrays w = slot_arrays(ctx, sb_order.slot, l);
-    a.o.g = g;
-    a.o.P = sb_order.prm.max_pillars;
-    a.o.B = sb_order.batch;
-    a.o.tile_meta = w.tile_meta;
-    a.o.tile_agg = w.tile_agg;
-    a.o.ordered_meta = w.meta;
-    a.o.ordered_totals = w.otot;
-    a.n_order_blocks = (g.ntiles * sb_order.batch + kEmitWaves - 1) / kEmitWaves;   // one wave per (sweep, tile)
-  }
+  int rc = step_check_in_flight(ctx, stream, c);
+  if (rc) return rc;
+  if ((rc = step_new_batch(ctx, c, &sb_new)) != PP_OK) return rc;
+  StepArgs whole, a;
+  std::memset(&whole, 0, sizeof whole);
+  size_t lds = 0;
   int mode = kModeDenseVec4;
-  bool sc1 = false;  // write-through stores: decided per launch, by the bytes it writes
-  if (sb_emit.valid) {
-    GridGeom g;
-    VoxLayout l;
-    rc = step_geometry(sb_emit, &g, &l);
-    if (rc) return rc;
-    const SlotArrays w = slot_arrays(ctx, sb_emit.slot, l);
-    const int P = sb_emit.prm.max_pillars, N = sb_emit.prm.max_points_per_pillar;
-    a.e.g = g;
-    std::memcpy(a.e.np.n, sb_emit.n_points, sizeof a.e.np.n);
-    a.e.P = P;
-    a.e.N = N;
-    a.e.ncap = l.ncap;
-    a.e.tile_meta = w.tile_meta;
-    a.e.tile_agg = w.tile_agg;
-    a.e.totals = num_cells_dev ? reinterpret_cast<int2 *>(num_cells_dev) : w.totals;
-    a.e.ordered_meta = w.meta;
-    a.e.ordered_totals = w.otot;
-    a.e.sorted_pts = w.sorted_pts;
-    a.e.out = pillars_dev;
-    a.e.idx_out = reinterpret_cast<long long *>(indices_dev);
-    a.emit_nbx = (P + KW * kEmitWaves - 1) / (KW * kEmitWaves);
-    mode = (N % 4 == 0 && N <= 4096) ? kModeDenseVec4 : kModeDenseScalar;
-    lds = std::max(lds, pfn ? sizeof(WaveLds<float, emit_cap(kModePfn)>) * kEmitWaves : sizeof(WaveLds<float>) * kEmitWaves);
-    if (pfn) {
-      mode = kModePfn;
-      a.e.out = nullptr;
-      a.e.pfn_w = pfn->params;
-      a.e.pfn_out = nullptr;
-      a.e.canvas = pfn->canvas;
-      a.e.canvas_h = pfn->h;
-      a.e.canvas_w = pfn->w;
-      a.e.canvas_nhwc = pfn->nhwc;
-    }
-  }
-  if (pfn && pfn->clear_canvas && pfn->clear_indices && pfn->clear_batch > 0) {
-    // the other canvas: only the pixels its last batch wrote are non-zero (same geometry as the due batch's)
-    if ((reinterpret_cast<uintptr_t>(pfn->clear_canvas) & 15) || (reinterpret_cast<uintptr_t>(pfn->clear_indices) & 7) ||
-        pfn->clear_batch > PP_MAX_BATCH || !sb_emit.valid) {
-      set_error("pp_voxelize_step_pfn_canvas_dev: bad clear arguments (alignment, batch <= %d, and a batch must be due "
-                "whose shapes describe the canvas)", PP_MAX_BATCH);
-      return PP_ERR_VALUE;
-    }
-    a.un.prev_idx = reinterpret_cast<const long long *>(pfn->clear_indices);
-    a.un.canvas = pfn->clear_canvas;
-    a.un.P = sb_emit.prm.max_pillars;
-    a.un.h = pfn->h;
-    a.un.w = pfn->w;
-    a.un.nhwc = pfn->nhwc;
-    a.un.nblocks = (a.un.P + kUnscatterPixels - 1) / kUnscatterPixels;
-    a.n_unscatter_blocks = a.un.nblocks * pfn->clear_batch;
-  }
-  if (a.emit_nbx == 0) a.emit_nbx = 1;
+  if ((rc = fill_split_role(ctx, stream, sb_new, c.points, &whole, &lds)) != PP_OK) return rc;
+  if ((rc = fill_tile_role(ctx, sb_tile, &whole, &lds)) != PP_OK) return rc;
+  if ((rc = fill_order_role(ctx, sb_order, &whole)) != PP_OK) return rc;
+  if ((rc = fill_emit_role(ctx, sb_emit, c, &whole, &lds, &mode)) != PP_OK) return rc;
+  if ((rc = fill_clear_role(c.pfn, sb_emit, &whole)) != PP_OK) return rc;
+  if (whole.emit_nbx == 0) whole.emit_nbx = 1;
+  if (mode != kModePfn) whole.n_unscatter_blocks = 0;
   // The tile role takes its tiles XCD by XCD (tile_of_block) once its gathers are beyond what the L2s keep anyway: at
   // BASELINE config 5 (800k points per launch: 16 MB of split records) k_step's FETCH_SIZE halves, 56.9 -> 29.0 MiB, and the
   // launch is 1.5-4 us shorter (five alternations on two boxes, profiles/r06/NOTES.md section 5); at configs[1]'s
   // 240k points (4.8 MB, which every XCD's 4 MB L2 nearly holds) it measures the same to 0.2-0.4 us worse: tile = block.
-  a.tile_xcd_map = sb_tile.valid && (size_t)sb_tile.batch * (size_t)sb_tile.maxn * 20u > kTileXcdMapBytes;
-  // A call CAN go out as several launches of a few sweeps each (sweeps are independent, so every role's
-  // batch splits the same way).  Round 3's driver line suggested it should when the dense output exceeds the
-  // 256 MB Infinity Cache: per sweep, one 172.8 MB sweep per launch ran at 0.73 of the roofline, four in
-  // one launch at 0.64.  Measured in round 4 (profiles/r04/NOTES.md): four launches of one sweep each take
-  // 154 us against 146 us for the one launch -- the one-sweep figure came from re-writing the SAME 172.8 MB
-  // buffer call after call, which the memory-side cache absorbs; four launches writing four different
-  // regions go to HBM like the single launch does, and pay three more launch ramps.  Default: one launch.
-  static const size_t sub_bytes = [] {  // PP_STEP_SUB_MB: dense MB per launch (0 = never split); the test of the split form sets it
-    const char *e = getenv("PP_STEP_SUB_MB");
-    return e ? (size_t)std::max(0, atoi(e)) << 20 : kStepLaunchBytes;
-  }();
-  int n_launch = 1;
-  if (sb_emit.valid && sub_bytes && !pfn) {
-    const size_t per_sweep = 36u * (size_t)sb_emit.prm.max_pillars * (size_t)sb_emit.prm.max_points_per_pillar;
-    const int per_launch = (int)std::max<size_t>(1, sub_bytes / std::max<size_t>(per_sweep, 1));
-    n_launch = (sb_emit.batch + per_launch - 1) / per_launch;
-  }
-  const StepArgs whole = a;
-  const int nt_t = sb_tile.valid ? whole.t.g.ntiles : 0, nt_o = sb_order.valid ? whole.o.g.ntiles : 0;
+  whole.tile_xcd_map = sb_tile.valid && (size_t)sb_tile.batch * (size_t)sb_tile.maxn * 20u > kTileXcdMapBytes;
+  const pp_step_batch *const role[4] = {&sb_new, &sb_tile, &sb_order, &sb_emit};
+  const int n_launch = step_launch_count(sb_emit, c.pfn != nullptr);
   ctx->step_stream = stream;  // every argument check has passed: from here on a failure is not a refusal
   for (int k = 0; k < n_launch; ++k) {
-    auto part = [&](bool valid, int B, int *lo, int *n) {  // role's share of launch k: sweeps [lo, lo + n)
-      *lo = valid ? (int)((long long)B * k / n_launch) : 0;
-      *n = valid ? (int)((long long)B * (k + 1) / n_launch) - *lo : 0;
-    };
-    int tb, tn, ob, on, sb, sn, eb, en;
-    part(sb_tile.valid, sb_tile.batch, &tb, &tn);
-    part(sb_order.valid, sb_order.batch, &ob, &on);
-    part(sb_new.valid, sb_new.batch, &sb, &sn);
-    part(sb_emit.valid, sb_emit.batch, &eb, &en);
-    a = whole;
-    a.tile_b0 = tb;
-    a.n_tile_blocks = nt_t * tn;
-    a.o.b0 = ob;
-    a.o.B = on;
-    a.n_order_blocks = (nt_o * on + kEmitWaves - 1) / kEmitWaves;   // one wave per (sweep, tile)
-    a.split_b0 = sb;
-    a.n_split_blocks = sb_new.valid ? whole.s.nchunks * sn : 0;
-    a.emit_b0 = eb;
-    const int n_emit = whole.emit_nbx * en;
-    if (sb_emit.valid && !pfn) sc1 = (size_t)en * 36u * (size_t)a.e.P * (size_t)a.e.N <= kSc1MaxBytes;
-    {
-      int r = 0;
-      auto add = [&](const void *ptr, size_t per_sweep, int lo, int n) {
-        a.pf.ptr[r] = static_cast<const char *>(ptr) + per_sweep * (size_t)lo;
-        a.pf.n16[r] = (unsigned)(per_sweep * (size_t)n / 16);
-        ++r;
-      };
-      std::memset(&a.pf, 0, sizeof a.pf);
-      // Only the EMIT role's arrays are worth it (round 4, profiles/r04/NOTES.md): its blocks start after the
-      // binning blocks, so the lines are there when they ask.  The binning roles' own inputs (the order role's
-      // lists, the tile role's split arrays, the split role's points) were in this list while binning and emit
-      // blocks alternated; with the binning blocks FIRST they start in the same microsecond as the prefetch
-      // blocks and fetch for themselves -- the prefetch only doubled that traffic (headline 34.9 -> 33.7 us
-      // without, C5 B=4 111-118 -> 104-109 us).
-      if (en > 0) {   // what the emit role reads
-        add(a.e.ordered_meta, (size_t)a.e.P * 16, eb, en);
-        add(a.e.sorted_pts, (size_t)a.e.ncap * 16, eb, en);
-      }
-      a.n_pref_blocks = r > 0 ? kStepPrefetchBlocks : 0;
-    }
-    if (mode != kModePfn) a.n_unscatter_blocks = 0;
+    const int en = step_share(whole, role, k, n_launch, a), n_emit = whole.emit_nbx * en;
+    // write-through stores: decided per launch, by the bytes it writes
+    const bool sc1 = sb_emit.valid && !c.pfn && write_through(en, a.e.P, a.e.N);
+    step_block_order(a, n_emit);
     const long long nblocks = (long long)a.n_pref_blocks + a.n_unscatter_blocks + a.n_tile_blocks + a.n_order_blocks +
                               a.n_split_blocks + n_emit;
-    {
-      const int nbin = a.n_tile_blocks + a.n_order_blocks + a.n_split_blocks;
-      // Default: every binning block ahead of the emit blocks.  After a network pass (the real caller: a GiB of
-      // activations between two launches) the binning roles' chains run on cold lines and are the launch's
-      // tail unless they start first: 39 -> 35 us in bench.py's end-to-end loop; in a voxelizer-only loop, where
-      // their inputs are still cached, the 1:1 interleave (mix 2) was 2 us better (42.4 vs 40.6 us, round 4).
-      // More binning blocks than the chip holds at once (5 workgroups per CU): "first" would mean rounds of
-      // binning with no store in flight -- they are spread evenly over the launch instead, one per
-      // n_emit / nbin emit blocks (C5 B=4, 3 400 binning blocks against 7 500: one per two, 117-121 -> 104-109 us;
-      // one per one and one per three are both worse).
-      const int mix_auto = nbin > kStepChipSlots && n_emit > 0 ? std::max(2, n_emit / nbin + 1) : 1;
-      a.mix = mix_auto;
-      a.mix_groups = a.mix > 1 ? std::min(nbin, n_emit / (a.mix - 1)) : 0;
-      if (a.mix < 2) a.mix = 2, a.mix_groups = 0;
-    }
     if (nblocks <= 0) continue;
     if (nblocks > INT_MAX) {
       // (PP_ERR_VALUE means "refused, nothing launched, no state changed" to every caller -- voxelizer.py keeps its
@@ -2661,53 +2678,7 @@ static int step_impl(pp_ctx_t *ctx, void *stream_, const float *points_dev, int6
       set_error("pp_voxelize_step_dev: grid too large");
       return PP_ERR_INTERNAL;
     }
-    const void *fn = mode == kModePfn          ? reinterpret_cast<const void *>(&k_step<kModePfn, kAuxPlain>)
-                     : mode == kModeDenseScalar ? reinterpret_cast<const void *>(&k_step<kModeDenseScalar, kAuxPlain>)
-                     : sc1                      ? reinterpret_cast<const void *>(&k_step<kModeDenseVec4, kAuxSc1>)
-                                                : reinterpret_cast<const void *>(&k_step<kModeDenseVec4, kAuxPlain>);
-    {
-      // dynamic LDS beyond 64 KiB (16.7 M-cell grids) needs the attribute: once per process, device and
-      // instance, at the worst case
-      static std::atomic<unsigned> armed[64];
-      const unsigned bit = mode == kModePfn ? 8u : mode == kModeDenseScalar ? 1u : sc1 ? 2u : 4u;
-      const int dev = ctx->device & 63;
-      if (!(armed[dev].load(std::memory_order_acquire) & bit)) {
-        const size_t worst = std::max(std::max(tile_lds_bytes(kMaxTileSlots, kStepWaves), split_lds_bytes(kMaxTiles)),
-                                      sizeof(WaveLds<float>) * kEmitWaves);
-        PP_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)worst));
-        armed[dev].fetch_or(bit, std::memory_order_release);
-      }
-    }
-    // timing ring: ONE entry per call -- the start event rides on the call's first launch, the stop event on
-    // its last, so the entry is what the call's launches took together (bench.py's per-call duration)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (ctx->ev_slots > 0) {
-      if (k == 0) {
-        if (ctx->ev_columns != (1 << PP_KERNEL_EMIT)) ctx->ev_count = 0;  // the ring held three-launch calls: do not
-        ctx->ev_columns = 1 << PP_KERNEL_EMIT;                              // mix k_emit and k_step durations
-        e0 = ctx->ev_start[PP_KERNEL_EMIT][ctx->ev_next];
-      }
-      if (k == n_launch - 1) {
-        e1 = ctx->ev_stop[PP_KERNEL_EMIT][ctx->ev_next];
-        ctx->ev_next = (ctx->ev_next + 1) % ctx->ev_slots;
-        ctx->ev_count = std::min(ctx->ev_count + 1, ctx->ev_slots);
-      }
-    }
-    const dim3 grid((unsigned)nblocks), block(kStepThreads);
-    if (mode == kModePfn)
-      hipExtLaunchKernelGGL((k_step<kModePfn, kAuxPlain>), grid, block, lds, stream, e0, e1, 0, a);
-    else if (mode == kModeDenseScalar)
-      hipExtLaunchKernelGGL((k_step<kModeDenseScalar, kAuxPlain>), grid, block, lds, stream, e0, e1, 0, a);
-    else if (sc1)
-      hipExtLaunchKernelGGL((k_step<kModeDenseVec4, kAuxSc1>), grid, block, lds, stream, e0, e1, 0, a);
-    else
-      hipExtLaunchKernelGGL((k_step<kModeDenseVec4, kAuxPlain>), grid, block, lds, stream, e0, e1, 0, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-      for (auto &sb : ctx->step_batch) sb.valid = false;
-      set_error("voxelizer launch failed: %s", hipGetErrorString(e));
-      return PP_ERR_HIP;
-    }
+    if ((rc = launch_step(ctx, stream, a, mode, sc1, lds, nblocks, k == 0, k == n_launch - 1)) != PP_OK) return rc;
   }
   if (sb_emit.valid && emitted) *emitted = 1;
   // the batches move on: ordered -> due at the next call, tiled -> to be ordered, split -> to be tiled, new -> split
@@ -2720,13 +2691,14 @@ static int step_impl(pp_ctx_t *ctx, void *stream_, const float *points_dev, int6
   if (sb_new.valid) ctx->step_next_slot = ctx->step_next_slot % (pp_ctx::kVoxSlots - 1) + 1;
   return PP_OK;
 }
+}  // namespace
 
 extern "C" int pp_voxelize_step_dev(pp_ctx_t *ctx, void *stream_, const float *points_dev,
                                     int64_t points_stride, const int32_t *n_points, int batch,
                                     const pp_voxel_params_t *prm, float *pillars_dev,
                                     int64_t *indices_dev, int32_t *num_cells_dev, int *emitted) {
-  return step_impl(ctx, stream_, points_dev, points_stride, n_points, batch, prm, pillars_dev, indices_dev,
-                   num_cells_dev, emitted, nullptr);
+  const StepCall c{points_dev, points_stride, n_points, batch, prm, pillars_dev, nullptr, indices_dev, num_cells_dev};
+  return step_impl(ctx, stream_, c, emitted);
 }
 
 extern "C" int pp_voxelize_step_pfn_canvas_dev(pp_ctx_t *ctx, void *stream_, const float *points_dev,
@@ -2740,17 +2712,10 @@ extern "C" int pp_voxelize_step_pfn_canvas_dev(pp_ctx_t *ctx, void *stream_, con
     set_error("the fused feature net is built for %d output channels (got %d)", kPfnChannels, channels);
     return PP_ERR_VALUE;
   }
-  StepPfn pfn;
-  pfn.params = pfn_params_dev;
-  pfn.canvas = canvas_dev;
-  pfn.h = canvas_h;
-  pfn.w = canvas_w;
-  pfn.nhwc = channels_last ? 1 : 0;
-  pfn.clear_canvas = clear_canvas_dev;
-  pfn.clear_indices = clear_indices_dev;
-  pfn.clear_batch = clear_batch;
-  return step_impl(ctx, stream_, points_dev, points_stride, n_points, batch, prm, nullptr, indices_dev,
-                   num_cells_dev, emitted, &pfn);
+  const StepPfn pfn{pfn_params_dev, canvas_dev, canvas_h, canvas_w, channels_last ? 1 : 0, clear_canvas_dev, clear_indices_dev,
+                    clear_batch};
+  const StepCall c{points_dev, points_stride, n_points, batch, prm, nullptr, &pfn, indices_dev, num_cells_dev};
+  return step_impl(ctx, stream_, c, emitted);
 }
 
 extern "C" int pp_voxelize_step_kernel_name(const pp_voxel_params_t *prm, int batch, char *name, int cap) {
@@ -2758,11 +2723,9 @@ extern "C" int pp_voxelize_step_kernel_name(const pp_voxel_params_t *prm, int ba
     set_error("pp_voxelize_step_kernel_name: bad argument");
     return PP_ERR_VALUE;
   }
-  const int N = prm->max_points_per_pillar;
-  const int mode = (N % 4 == 0 && N <= 4096) ? kModeDenseVec4 : kModeDenseScalar;
-  // the same rule as step_impl's (one launch per call, PP_STEP_SUB_MB aside)
-  const bool sc1 = mode == kModeDenseVec4 &&
-                   (size_t)batch * 36u * (size_t)prm->max_pillars * (size_t)N <= kSc1MaxBytes;
+  // what step_impl launches for these shapes (one launch per call, PP_STEP_SUB_MB aside)
+  const int N = prm->max_points_per_pillar, mode = dense_emit_mode(N);
+  const bool sc1 = mode == kModeDenseVec4 && write_through(batch, prm->max_pillars, N);
   std::snprintf(name, (size_t)cap, "pp::k_step<%d, %d>", mode, sc1 ? kAuxSc1 : kAuxPlain);
   return PP_OK;
 }
@@ -2776,14 +2739,12 @@ extern "C" int pp_voxelize_step_reset(pp_ctx_t *ctx) {
   return PP_OK;                                         // what an earlier launch of ITS batch wrote
 }
 
-static int voxelize_pfn_impl(pp_ctx_t *ctx, void *stream_, const float *points_dev,
-                             int64_t points_stride, const int32_t *n_points, int batch,
-                             const pp_voxel_params_t *prm, const float *pfn_params_dev,
-                             int channels, float *features_dev, int64_t *indices_dev,
-                             int32_t *num_cells_dev, float *canvas_dev, int canvas_h, int canvas_w,
-                             int channels_last, const int64_t *prev_indices_dev = nullptr) {
-  if (!ctx || !points_dev || !n_points || !prm || !pfn_params_dev || !indices_dev ||
-      (!features_dev && !canvas_dev)) {
+static int voxelize_pfn_impl(pp_ctx_t *ctx, void *stream_, const float *points_dev, int64_t points_stride,
+                             const int32_t *n_points, int batch, const pp_voxel_params_t *prm, const float *pfn_params_dev,
+                             int channels, float *features_dev, int64_t *indices_dev, int32_t *num_cells_dev,
+                             float *canvas_dev, int canvas_h, int canvas_w, int channels_last,
+                             const int64_t *prev_indices_dev = nullptr) {
+  if (!ctx || !points_dev || !n_points || !prm || !pfn_params_dev || !indices_dev || (!features_dev && !canvas_dev)) {
     set_error("pp_voxelize_pfn*_dev: NULL argument");
     return PP_ERR_VALUE;
   }
@@ -2791,76 +2752,49 @@ static int voxelize_pfn_impl(pp_ctx_t *ctx, void *stream_, const float *points_d
     set_error("the fused feature net is built for %d output channels (got %d)", kPfnChannels, channels);
     return PP_ERR_VALUE;
   }
-  if (batch < 1 || batch > PP_MAX_BATCH) {
-    set_error("batch must be in [1,%d], got %d", PP_MAX_BATCH, batch);
-    return PP_ERR_VALUE;
-  }
-  const int P = prm->max_pillars, N = prm->max_points_per_pillar;
-  if (P < 1 || N < 1 || N > 65536) {
-    set_error("need max_pillars >= 1 and 1 <= max_points_per_pillar <= 65536 (got P=%d N=%d)", P, N);
-    return PP_ERR_VALUE;
-  }
-  if (points_stride < 0 || points_stride > INT_MAX / 2) {
-    set_error("points_stride out of range");
-    return PP_ERR_VALUE;
-  }
   NPoints np;
-  std::memset(&np, 0, sizeof np);
   int maxn = 0;
-  for (int b = 0; b < batch; ++b) {
-    if (n_points[b] < 0 || n_points[b] > points_stride) {
-      set_error("n_points[%d]=%d outside [0, points_stride=%lld]", b, n_points[b],
-                (long long)points_stride);
-      return PP_ERR_VALUE;
-    }
-    np.n[b] = n_points[b];
-    maxn = std::max(maxn, n_points[b]);
-  }
-  if ((reinterpret_cast<uintptr_t>(points_dev) & 15) || (reinterpret_cast<uintptr_t>(features_dev) & 15) ||
-      (reinterpret_cast<uintptr_t>(indices_dev) & 7) || (reinterpret_cast<uintptr_t>(pfn_params_dev) & 3)) {
-    set_error("device pointers must be 16-byte (points, features) / 8-byte (indices) aligned");
-    return PP_ERR_VALUE;
-  }
+  const char *what = "pp_voxelize_pfn*_dev";
+  if (int rc = check_points_args(what, batch, prm, points_stride, n_points, false, &np, &maxn)) return rc;
+  if (int rc = check_alignment(what, "16-byte (points, features) / 8-byte (indices)", points_dev, features_dev, indices_dev,
+                               nullptr, pfn_params_dev))
+    return rc;
+  const int P = prm->max_pillars, N = prm->max_points_per_pillar;
   GridGeom g;
-  int rc = make_grid(prm, &g);
-  if (rc) return rc;
+  if (int rc = make_grid(prm, &g)) return rc;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   DeviceGuard guard(ctx->device);
   VoxLayout l;
-  rc = prepare_ws(ctx, stream, batch, std::max<int64_t>(points_stride, 1), g, P, 16, &l);
-  if (rc) return rc;
+  if (int rc = prepare_ws(ctx, stream, batch, std::max<int64_t>(points_stride, 1), g, P, 16, &l)) return rc;
   if (canvas_dev) {
     // rows are (H-1) - fy with H = canvas_height (pillars.cpp:280).  The cell grid carries one
     // guard row/column for the rounding of (x - x_min)/x_step at the upper edge (never
     // populated by f32 input); a pillar whose pixel is outside the canvas is not written.
-    if ((double)canvas_h != g.canvas_height || canvas_h < 1 || canvas_w < 1 ||
-        (reinterpret_cast<uintptr_t>(canvas_dev) & 15)) {
+    if ((double)canvas_h != g.canvas_height || canvas_h < 1 || canvas_w < 1 || misaligned(canvas_dev, 16)) {
       set_error("canvas %dx%d: height must equal canvas_height=%g (and the tensor be 16-byte "
                 "aligned)", canvas_h, canvas_w, g.canvas_height);
       return PP_ERR_VALUE;
     }
-    if (prev_indices_dev && (reinterpret_cast<uintptr_t>(prev_indices_dev) & 7)) {
+    if (misaligned(prev_indices_dev, 8)) {
       set_error("prev_indices_dev must be 8-byte aligned");
       return PP_ERR_VALUE;
     }
     if (!prev_indices_dev)   // an unknown canvas: all of it
-      PP_HIP_TRY(hipMemsetAsync(canvas_dev, 0,
-                                (size_t)batch * kPfnChannels * canvas_h * canvas_w * sizeof(float),
-                                stream));
+      PP_HIP_TRY(hipMemsetAsync(canvas_dev, 0, (size_t)batch * kPfnChannels * canvas_h * canvas_w * sizeof(float), stream));
   }
-  rc = launch_pipeline<float>(ctx, stream, points_dev, points_stride, 4, 1, 1, np, batch, maxn,
-                              g, P, N, l, kModePfn, nullptr,
-                              reinterpret_cast<long long *>(indices_dev), nullptr, true,
-                              pfn_params_dev, features_dev, canvas_dev, canvas_h, canvas_w,
-                              channels_last ? 1 : 0,
-                              canvas_dev ? reinterpret_cast<const long long *>(prev_indices_dev) : nullptr);
-  if (rc) return rc;
-  if (num_cells_dev) {
-    char *ws = static_cast<char *>(ctx->vox_ws[0].ptr);
-    PP_HIP_TRY(hipMemcpyAsync(num_cells_dev, ws + l.totals, (size_t)batch * 8,
-                              hipMemcpyDeviceToDevice, stream));
-  }
-  return PP_OK;
+  PipelineCall c{};
+  c.mode = kModePfn;
+  c.timed = true;
+  c.prev_idx = canvas_dev ? reinterpret_cast<const long long *>(prev_indices_dev) : nullptr;
+  c.e.idx_out = reinterpret_cast<long long *>(indices_dev);
+  c.e.pfn_w = pfn_params_dev;
+  c.e.pfn_out = features_dev;
+  c.e.canvas = canvas_dev;
+  c.e.canvas_h = canvas_h;
+  c.e.canvas_w = canvas_w;
+  c.e.canvas_nhwc = channels_last ? 1 : 0;
+  c.num_cells = num_cells_dev;
+  return launch_pipeline<float>(ctx, stream, points_dev, points_stride, np, batch, maxn, g, P, N, l, c);
 }
 
 extern "C" int pp_voxelize_pfn_dev(pp_ctx_t *ctx, void *stream_, const float *points_dev,
@@ -2909,6 +2843,321 @@ extern "C" int pp_voxelize_pfn_canvas_reuse_dev(pp_ctx_t *ctx, void *stream_, co
                            canvas_dev, canvas_h, canvas_w, channels_last, prev_indices_dev);
 }
 
+/* ---- host drop-in: pp_create_pillars_f64, phase by phase ---- */
+namespace {
+// The shape of the host path is what measured best (profiles/r06/NOTES.md: 8 threads, one host-to-device copy, the
+// features back in two chunks, polled waits, f32 transport of f32-valued clouds: 0.36 -> 0.19 ms per call; sending the
+// features AHEAD of the descriptors, sized by the previous call's count, measured no gain).
+constexpr int kChunks = 2;  // pieces the features come back in: one is scattered while the next is on its way
+constexpr int kMaxEv = (int)(sizeof(pp_ctx::chunk_ev) / sizeof(hipEvent_t));  // (the last one: the descriptors' event)
+
+// A call waits for the device two or three times, for tens of microseconds each: polled, not slept on (an interrupt-driven
+// wake-up costs about as much as the wait itself).
+hipError_t wait_event(hipEvent_t ev) {
+  for (;;) {
+    const hipError_t e = hipEventQuery(ev);
+    if (e != hipErrorNotReady) return e;
+    __builtin_ia32_pause();
+  }
+}
+
+// From the first enqueue on the call's kernels and copies read pin_in and write pin_meta / pin_out through the stream:
+// however the call leaves, they have finished (the header's promise -- the next call's gather into pin_in would overlap
+// them).  The successful exits have waited already and disarm; every failing one synchronises here.
+struct StreamSyncOnExit {
+  hipStream_t stream;
+  bool armed;
+  ~StreamSyncOnExit() { if (armed && hipStreamSynchronize(stream) != hipSuccess) (void)hipGetLastError(); }
+};
+
+// PP_DROPIN_PACK=0: the features come back as nine doubles, never packed (the transport test compares both)
+bool dropin_pack() { static const bool k_pack = env_int("PP_DROPIN_PACK", 1) != 0; return k_pack; }
+// Two small transfers need no copy engine at all (PP_DROPIN_DIRECT, bit mask; f32-valued clouds): 1 -- k_split reads
+// the gathered points straight from the pinned staging (each point is read once, coalesced: the kernel runs at the
+// link's rate and the copy's start-up and completion hand-over fall away); 2 -- k_emit writes the descriptors and the
+// totals, which nothing on the device reads back, straight into pinned memory: they are there when the kernel is.
+// 4 -- the features' way back is k_records_to_host, enqueued behind the kernels and sized on the device.
+int dropin_direct() { static const int k_direct = env_int("PP_DROPIN_DIRECT", 7); return k_direct; }
+
+// one call's state, handed from phase to phase
+struct PillarsCall {
+  pp_ctx *ctx;
+  hipStream_t stream;
+  const char *src_pts;     // the caller's (arbitrarily strided) float64 points ...
+  int64_t ps0, ps1;
+  char *tp, *ip;           // ... its tensor and its indices
+  const int64_t *t_shape, *t_strides, *i_shape, *i_strides;
+  GridGeom g;
+  VoxLayout l;
+  int n, P, N, max_pillars;
+  bool as_f32, packed;     // the cloud takes the f32-input kernels; its features come back as kPackedFeat-byte records
+  int64_t rec;             // bytes of a point's features on the way back
+  char *pm;                // pinned: pillar_meta[P] and, behind it as in the workspace, the totals
+  size_t meta_bytes;
+  int4 *meta_host;         // the same through the device's mapping, written by k_emit itself; NULL: a copy brings them
+  int2 *totals_host;
+  int64_t cb[kMaxEv + 1];  // chunk c of the features = compact points [cb[c], cb[c + 1])
+  int nch, direct_pieces;
+  const int4 *meta;        // once the descriptors are on the host: them, the pillars and points emitted, the features
+  int npil;
+  int64_t end;
+  const char *feat;
+
+  // `live` points' features from compact position `at` into a dense [live][9] run of doubles
+  void copy_rows(char *dst, int64_t at, int live) const {
+    if (!packed) {
+      std::memcpy(dst, feat + at * 72, (size_t)live * 72);
+      return;
+    }
+    const char *src = feat + at * kPackedFeat;
+    for (int k = 0; k < live; ++k, src += kPackedFeat, dst += 72) {
+      float head[4];
+      std::memcpy(head, src, 16);
+      const double wide[4] = {(double)head[0], (double)head[1], (double)head[2], (double)head[3]};
+      std::memcpy(dst, wide, 32);
+      std::memcpy(dst + 32, src + 16, 40);
+    }
+  }
+  void write_index_row(int p) const {  // pillars.cpp:389-391
+    int cell = meta[p].x;
+    if (g.order != PP_ORDER_ROW_MAJOR)
+      cell = (int)(((unsigned long long)cell * g.mult_inv) % (unsigned long long)g.ncells);
+    const double canvas_x = (double)(cell % g.nx);
+    const double fy = (double)((g.ny - 1) - cell / g.nx);
+    const double canvas_y = (g.canvas_height - 1) - fy;
+    const double one = 1.0;
+    std::memcpy(ip + p * i_strides[0] + 0 * i_strides[1], &one, 8);
+    std::memcpy(ip + p * i_strides[0] + 1 * i_strides[1], &canvas_x, 8);
+    std::memcpy(ip + p * i_strides[0] + 2 * i_strides[1], &canvas_y, 8);
+  }
+};
+
+// the caller's points into pinned staging as T; *lossy (float only): a value did not survive double -> float -> double
+template <typename T>
+void gather_points(const PillarsCall &c, std::atomic<int> *lossy) {
+  T *dst = static_cast<T *>(c.ctx->pin_in.ptr);
+  host_pool(c.ctx)->run([&](int part, int parts) {
+    const int64_t i0 = (int64_t)c.n * part / parts, i1 = (int64_t)c.n * (part + 1) / parts;
+    int bad = 0;
+    for (int64_t i = i0; i < i1; ++i)
+      for (int k = 0; k < 4; ++k) {
+        double v;
+        std::memcpy(&v, c.src_pts + i * c.ps0 + k * c.ps1, 8);
+        const T f = (T)v;
+        bad |= ((double)f != v) & (v == v);
+        dst[i * 4 + k] = f;
+      }
+    if (bad && lossy) lossy->store(1, std::memory_order_relaxed);
+  });
+}
+
+// Phase 1: gather the (arbitrarily strided) points into pinned staging and decide as_f32.
+// The reference's caller hands over float64 points that ARE float32 values (the lidar files are f32, the SDK keeps the
+// transformed points in an f32 array, np.hstack widens them: data/dataset.py:51-88) -- and a point cloud whose every
+// value survives double -> float -> double goes through the f32-input kernels, which widen it again on the device:
+// the same bits in, half the bytes over PCIe (0.96 instead of 1.92 MB at BASELINE config 2's 60 000 points).  The
+// test rides on the gather; one value that does not survive (or a first gather that found one) and the call takes
+// the f64-input kernels as before.  (NaN compares unequal to itself and counts as surviving: both kernel families
+// drop the point.)
+// ... and on the way back such a cloud's x, y, z, intensity columns travel as the floats they are (56 bytes a point
+// instead of 72; the scatter widens them): store_compact_features.
+int pillars_gather(PillarsCall &c) {
+  if (int rc = c.ctx->pin_in.ensure((size_t)c.n * 32)) return rc;
+  for (int k = 0; k < kMaxEv; ++k)
+    if (!c.ctx->chunk_ev[k]) PP_HIP_TRY(hipEventCreateWithFlags(&c.ctx->chunk_ev[k], hipEventDisableTiming));
+  std::atomic<int> lossy{0};
+  gather_points<float>(c, &lossy);
+  c.as_f32 = lossy.load() == 0;
+  c.packed = c.as_f32 && dropin_pack();
+  c.rec = c.packed ? kPackedFeat : 72;
+  return PP_OK;
+}
+
+// Phase 2: workspace, staging and the pinned descriptors' mapping.  Nothing that touches pinned memory is enqueued yet.
+int pillars_transport(PillarsCall &c) {
+  pp_ctx *ctx = c.ctx;
+  if (int rc = prepare_ws(ctx, c.stream, 1, c.n, c.g, c.P, c.as_f32 ? 16 : 32, &c.l)) return rc;
+  if (int rc = ctx->stage_in.ensure((size_t)c.l.ncap * 32)) return rc;
+  if (int rc = ctx->stage_out.ensure((size_t)c.l.ncap * 72)) return rc;
+  c.meta_bytes = (c.l.totals - c.l.meta) + 8;
+  if (int rc = ctx->pin_meta.ensure(c.meta_bytes)) return rc;
+  c.pm = static_cast<char *>(ctx->pin_meta.ptr);
+  void *pm_dev = nullptr;
+  const bool meta_direct = (dropin_direct() & 2) && hipHostGetDevicePointer(&pm_dev, c.pm, 0) == hipSuccess && pm_dev;
+  (void)hipGetLastError();  // (a refused mapping is not an error of this call: the copies are used)
+  c.meta_host = meta_direct ? reinterpret_cast<int4 *>(pm_dev) : nullptr;
+  c.totals_host = meta_direct ? reinterpret_cast<int2 *>(static_cast<char *>(pm_dev) + (c.l.totals - c.l.meta)) : nullptr;
+  return PP_OK;
+}
+
+// Phase 3: all the device does for the call, enqueued -- the points in, the three kernels, the descriptors' copy and
+// event and (PP_DROPIN_DIRECT & 4) the features' pieces.
+int pillars_enqueue(PillarsCall &c) {
+  pp_ctx *ctx = c.ctx;
+  hipStream_t stream = c.stream;
+  const VoxLayout &l = c.l;
+  NPoints np{};
+  np.n[0] = c.n;
+  PipelineCall pc{};
+  pc.mode = kModeCompact;
+  pc.e.feat_out = static_cast<double *>(ctx->stage_out.ptr);
+  pc.e.feat_pack = c.packed ? 1 : 0;
+  pc.e.pillar_meta_host = c.meta_host;
+  pc.e.totals_host = c.totals_host;
+  const void *pts_dev = ctx->stage_in.ptr;
+  void *mapped = nullptr;
+  if (c.as_f32 && (dropin_direct() & 1) && hipHostGetDevicePointer(&mapped, ctx->pin_in.ptr, 0) == hipSuccess && mapped) {
+    pts_dev = mapped;
+  } else {
+    // (f64) the caller's points are a strided view (data/dataset.py:88 passes the transpose of a [4, n] array): rows split
+    // across the pool's threads, then one host-to-device copy
+    if (!c.as_f32) gather_points<double>(c, nullptr);
+    const size_t bytes = (size_t)c.n * (c.as_f32 ? 16 : 32);
+    PP_HIP_TRY(hipMemcpyAsync(ctx->stage_in.ptr, ctx->pin_in.ptr, bytes, hipMemcpyHostToDevice, stream));
+  }
+  (void)hipGetLastError();
+  auto launch = [&](auto *pts) { return launch_pipeline(ctx, stream, pts, l.ncap, np, 1, c.n, c.g, c.P, c.N, l, pc); };
+  if (int rc = c.as_f32 ? launch(static_cast<const float *>(pts_dev)) : launch(static_cast<const double *>(pts_dev))) return rc;
+  // descriptors back in ONE copy: pillar_meta[P] (pillar order, written by k_emit in compact mode) and, behind it in the
+  // workspace, the totals
+  if (int rc = ctx->pin_out.ensure((size_t)l.ncap * 72)) return rc;
+  const SlotArrays w = slot_arrays(ctx, 0, l);
+  if (!c.meta_host) PP_HIP_TRY(hipMemcpyAsync(c.pm, w.meta, c.meta_bytes, hipMemcpyDeviceToHost, stream));
+  PP_HIP_TRY(hipEventRecord(ctx->chunk_ev[kMaxEv - 1], stream));
+  // The features follow in chunks: chunk k is scattered while chunk k + 1 is on its way.  How many points the call emits
+  // is only known from the descriptors: the device reads them itself (the direct pieces), or the copies are issued once
+  // the host has them.
+  // (PP_DROPIN_DIRECT & 4) the pieces go out right here, behind the kernels, sized on the device by k_records_to_host
+  void *out_dev = nullptr;
+  if ((dropin_direct() & 4) && c.N > 0 && hipHostGetDevicePointer(&out_dev, ctx->pin_out.ptr, 0) == hipSuccess && out_dev) {
+    c.direct_pieces = (int64_t)c.n * c.rec >= (256 << 10) ? kChunks : 1;
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(256, ((int64_t)c.n * c.rec / c.direct_pieces + 16 * kCopyThreads - 1) /
+                                                                             (16 * kCopyThreads)));
+    for (int k = 0; k < c.direct_pieces; ++k) {
+      hipLaunchKernelGGL(k_records_to_host, dim3((unsigned)blocks), dim3(kCopyThreads), 0, stream, w.totals, w.meta, c.P,
+                         c.max_pillars, (int)c.rec, static_cast<const char *>(ctx->stage_out.ptr), static_cast<char *>(out_dev),
+                         k, c.direct_pieces);
+      PP_HIP_TRY(hipGetLastError());
+      PP_HIP_TRY(hipEventRecord(ctx->chunk_ev[k], stream));
+    }
+  }
+  (void)hipGetLastError();
+  return PP_OK;
+}
+
+// Phase 4: wait for the descriptors -- how many pillars and points the call emitted
+int pillars_read_descriptors(PillarsCall &c, int64_t *num_cells) {
+  PP_HIP_TRY(wait_event(c.ctx->chunk_ev[kMaxEv - 1]));
+  int tot[2];
+  std::memcpy(tot, c.pm + (c.l.totals - c.l.meta), 8);
+  if (num_cells) *num_cells = tot[0];
+  c.npil = std::min(tot[0], std::min(c.P, c.max_pillars));
+  c.meta = reinterpret_cast<const int4 *>(c.pm);
+  c.end = c.npil > 0 ? (int64_t)c.meta[c.npil - 1].y + c.meta[c.npil - 1].z : 0;
+  c.feat = static_cast<const char *>(c.ctx->pin_out.ptr);
+  return PP_OK;
+}
+// ... and, where the device has not sent the features itself, issue their copies (in kChunks pieces when `chunked`)
+int pillars_issue_chunks(PillarsCall &c, bool chunked) {
+  if (c.direct_pieces) {  // the device cut [0, end) at the same places
+    c.nch = c.direct_pieces;
+    for (int k = 0; k <= c.nch; ++k) c.cb[k] = piece_begin(c.end, k, c.nch);
+    return PP_OK;
+  }
+  if (c.N <= 0 || c.end <= 0) return PP_OK;
+  const int pieces = chunked && c.end * c.rec >= (256 << 10) ? kChunks : 1;
+  for (int k = 0; k < pieces && c.nch < kMaxEv - 2; ++k) {
+    const int64_t b0 = c.cb[c.nch], b1 = c.end * (k + 1) / pieces;
+    if (b1 <= b0) continue;
+    PP_HIP_TRY(hipMemcpyAsync(static_cast<char *>(c.ctx->pin_out.ptr) + b0 * c.rec,
+                              static_cast<const char *>(c.ctx->stage_out.ptr) + b0 * c.rec, (size_t)(b1 - b0) * c.rec,
+                              hipMemcpyDeviceToHost, c.stream));
+    PP_HIP_TRY(hipEventRecord(c.ctx->chunk_ev[c.nch], c.stream));
+    c.cb[++c.nch] = b1;
+  }
+  return PP_OK;
+}
+
+// Phase 5, the usual caller's layout.
+// The usual caller hands in a C-contiguous [P,N,9] tensor (np.zeros, data/dataset.py:89): a pillar's live points are
+// then ONE contiguous run of live * 72 bytes -- but 7200 bytes from the next pillar's, in an 86 MB array that no CPU
+// cache holds: the scatter is a chain of 12 000 cache misses (195 us of round 4's 360 us call on one thread; 150-178
+// with the next pillars' lines prefetched for writing).  Nothing can go out of range in that layout once the shapes
+// hold the call's pillars, so the rows -- disjoint -- are split across the pool's threads.
+int pillars_scatter_dense(PillarsCall &c) {
+  const int4 *meta = c.meta;
+  const int npil = c.npil, nch = c.nch, N = c.N;
+  const int64_t t_stride0 = c.t_strides[0];
+  char *tp = c.tp;
+  int p_done = 0;
+  for (int k = 0; k < std::max(nch, 1); ++k) {
+    if (nch) PP_HIP_TRY(wait_event(c.ctx->chunk_ev[k]));
+    // the pillars whose points have all arrived: start + count <= cb[k + 1]
+    int p_hi = npil;
+    if (nch && c.cb[k + 1] < c.end) {
+      int lo = p_done, hi = npil;
+      while (lo < hi) {
+        const int mid = (lo + hi) / 2;
+        if ((int64_t)meta[mid].y + meta[mid].z <= c.cb[k + 1]) lo = mid + 1; else hi = mid;
+      }
+      p_hi = lo;
+    } else if (k + 1 < nch) {
+      continue;  // everything needed is here already; the later events are waited for at the end
+    }
+    const int p0 = p_done, p1 = p_hi;
+    p_done = p_hi;
+    if (p1 <= p0) continue;
+    host_pool(c.ctx)->run([&](int part, int parts) {
+      const int q0 = p0 + (int)((int64_t)(p1 - p0) * part / parts), q1 = p0 + (int)((int64_t)(p1 - p0) * (part + 1) / parts);
+      constexpr int kAhead = 8;
+      for (int p = q0; p < q1; ++p) {
+        if (p + kAhead < q1) {
+          const char *nx = tp + (int64_t)(p + kAhead) * t_stride0;
+          const int nl = std::min(meta[p + kAhead].z, N) * 72;
+          for (int o = 0; o < nl; o += 64) __builtin_prefetch(nx + o, 1, 0);
+          if (nl > 0) __builtin_prefetch(nx + nl - 1, 1, 0);
+        }
+        const int live = std::min(meta[p].z, N);
+        if (live > 0) c.copy_rows(tp + (int64_t)p * t_stride0, meta[p].y, live);
+        c.write_index_row(p);
+      }
+    });
+  }
+  if (nch) PP_HIP_TRY(wait_event(c.ctx->chunk_ev[nch - 1]));  // (the loop may have skipped the later events)
+  return PP_OK;
+}
+
+// Phase 6, any other layout (strided views, undersized arrays), the device having finished: one thread, element by
+// element with pybind11 .mutable_at()'s bounds checks, pillar by pillar like pillars.cpp:335-396 -- the writes made
+// before an IndexError persist, nothing behind it is touched
+int pillars_scatter_checked(const PillarsCall &c, bool dense_t) {
+  const int4 *meta = c.meta;
+  for (int p = 0; p < c.npil; ++p) {
+    const int live = std::min(meta[p].z, c.N);
+    if (dense_t) {
+      if (live > 0) c.copy_rows(c.tp + (int64_t)p * c.t_strides[0], meta[p].y, live);
+    } else
+    for (int k = 0; k < live; ++k) {
+      double f[9];
+      c.copy_rows(reinterpret_cast<char *>(f), (int64_t)meta[p].y + k, 1);
+      for (int d = 0; d < 9; ++d) {
+        if (!c.tp || p >= c.t_shape[0] || k >= c.t_shape[1] || d >= c.t_shape[2]) {
+          set_error("create_pillars: tensor index (%d,%d,%d) out of range", p, k, d);
+          return PP_ERR_INDEX;
+        }
+        std::memcpy(c.tp + p * c.t_strides[0] + k * c.t_strides[1] + d * c.t_strides[2], &f[d], 8);
+      }
+    }
+    if (!c.ip || p >= c.i_shape[0] || 2 >= c.i_shape[1]) {
+      set_error("create_pillars: indices index (%d,2) out of range", p);
+      return PP_ERR_INDEX;
+    }
+    c.write_index_row(p);
+  }
+  return PP_OK;
+}
+}  // namespace
+
 extern "C" int pp_create_pillars_f64(pp_ctx_t *ctx, const void *points, int64_t n_points,
                                      int64_t ps0, int64_t ps1, void *tensor,
                                      const int64_t t_shape[3], const int64_t t_strides[3],
@@ -2924,290 +3173,37 @@ extern "C" int pp_create_pillars_f64(pp_ctx_t *ctx, const void *points, int64_t 
     set_error("n_points out of range");
     return PP_ERR_VALUE;
   }
-  GridGeom g;
-  int rc = make_grid(prm, &g);
-  if (rc) return rc;
+  PillarsCall c{ctx, nullptr, static_cast<const char *>(points), ps0, ps1, static_cast<char *>(tensor),
+                static_cast<char *>(indices), t_shape, t_strides, i_shape, i_strides};  // (the rest: zero)
+  if (int rc = make_grid(prm, &c.g)) return rc;
   if (num_cells) *num_cells = 0;
   if (n_points == 0) return PP_OK;
-  const int n = (int)n_points;
-  const int max_pillars = std::max(prm->max_pillars, 0);
-  const int N = std::max(prm->max_points_per_pillar, 0);
+  c.n = (int)n_points;
+  c.max_pillars = std::max(prm->max_pillars, 0);
+  c.N = std::max(prm->max_points_per_pillar, 0);
   // there are at most min(n, ncells) non-empty cells
-  const int P = std::max(1, std::min(max_pillars, std::min(n, g.ncells)));
+  c.P = std::max(1, std::min(c.max_pillars, std::min(c.n, c.g.ncells)));
   DeviceGuard guard(ctx->device);
-  hipStream_t stream = nullptr;
-  // gather the (arbitrarily strided) points into pinned staging
-  rc = ctx->pin_in.ensure((size_t)n * 32);
-  if (rc) return rc;
-  HostPool *pool = host_pool(ctx);
-  // The shape of the host path is what measured best (profiles/r06/NOTES.md: 8 threads, one host-to-device copy, the
-  // features back in two chunks, polled waits, f32 transport of f32-valued clouds: 0.36 -> 0.19 ms per call; sending the
-  // features AHEAD of the descriptors, sized by the previous call's count, measured no gain).
-  constexpr int kChunks = 2;  // pieces the features come back in: one is scattered while the next is on its way
-  // A call waits for the device two or three times, for tens of microseconds each: polled, not slept on (an interrupt-driven
-  // wake-up costs about as much as the wait itself).
-  auto wait_event = [&](hipEvent_t ev) -> hipError_t {
-    for (;;) {
-      const hipError_t e = hipEventQuery(ev);
-      if (e != hipErrorNotReady) return e;
-      __builtin_ia32_pause();
-    }
-  };
-  constexpr int kMaxEv = (int)(sizeof ctx->chunk_ev / sizeof ctx->chunk_ev[0]);
-  for (int c = 0; c < kMaxEv; ++c)
-    if (!ctx->chunk_ev[c]) PP_HIP_TRY(hipEventCreateWithFlags(&ctx->chunk_ev[c], hipEventDisableTiming));
-  // The reference's caller hands over float64 points that ARE float32 values (the lidar files are f32, the SDK keeps the
-  // transformed points in an f32 array, np.hstack widens them: data/dataset.py:51-88) -- and a point cloud whose every
-  // value survives double -> float -> double goes through the f32-input kernels, which widen it again on the device:
-  // the same bits in, half the bytes over PCIe (0.96 instead of 1.92 MB at BASELINE config 2's 60 000 points).  The
-  // test rides on the gather; one value that does not survive (or a first gather that found one) and the call takes
-  // the f64-input kernels as before.  (NaN compares unequal to itself and counts as surviving: both kernel families
-  // drop the point.)
-  // ... and on the way back such a cloud's x, y, z, intensity columns travel as the floats they are (56 bytes a point
-  // instead of 72; the scatter widens them): store_compact_features.  PP_DROPIN_PACK=0: nine doubles (the transport test
-  // compares both).
-  static const bool k_pack = [] { const char *e = getenv("PP_DROPIN_PACK"); return e ? atoi(e) != 0 : true; }();
-  const char *src_pts = static_cast<const char *>(points);
-  bool as_f32;
-  {
-    float *dst = static_cast<float *>(ctx->pin_in.ptr);
-    std::atomic<int> lossy{0};
-    pool->run([&](int part, int parts) {
-      const int64_t i0 = (int64_t)n * part / parts, i1 = (int64_t)n * (part + 1) / parts;
-      int bad = 0;
-      for (int64_t i = i0; i < i1; ++i)
-        for (int c = 0; c < 4; ++c) {
-          double v;
-          std::memcpy(&v, src_pts + i * ps0 + c * ps1, 8);
-          const float f = (float)v;
-          bad |= ((double)f != v) & (v == v);
-          dst[i * 4 + c] = f;
-        }
-      if (bad) lossy.store(1, std::memory_order_relaxed);
-    });
-    as_f32 = lossy.load() == 0;
-  }
-  VoxLayout l;
-  rc = prepare_ws(ctx, stream, 1, n, g, P, as_f32 ? 16 : 32, &l);
-  if (rc) return rc;
-  rc = ctx->stage_in.ensure((size_t)l.ncap * 32);
-  if (rc) return rc;
-  rc = ctx->stage_out.ensure((size_t)l.ncap * 72);
-  if (rc) return rc;
-  // Two small transfers need no copy engine at all (PP_DROPIN_DIRECT, bit mask; f32-valued clouds): 1 -- k_split reads
-  // the gathered points straight from the pinned staging (each point is read once, coalesced: the kernel runs at the
-  // link's rate and the copy's start-up and completion hand-over fall away); 2 -- k_emit writes the descriptors and the
-  // totals, which nothing on the device reads back, straight into pinned memory: they are there when the kernel is.
-  // 4 -- the features' way back is k_records_to_host, enqueued behind the kernels and sized on the device.
-  static const int k_direct = [] { const char *e = getenv("PP_DROPIN_DIRECT"); return e ? atoi(e) : 7; }();
-  const size_t meta_bytes = (l.totals - l.meta) + 8;
-  rc = ctx->pin_meta.ensure(meta_bytes);
-  if (rc) return rc;
-  char *pm = static_cast<char *>(ctx->pin_meta.ptr);
-  void *pm_dev = nullptr;
-  const bool meta_direct = (k_direct & 2) && hipHostGetDevicePointer(&pm_dev, pm, 0) == hipSuccess && pm_dev;
-  (void)hipGetLastError();  // (a refused mapping is not an error of this call: the copies are used)
-  int4 *meta_host = meta_direct ? reinterpret_cast<int4 *>(pm_dev) : nullptr;
-  int2 *totals_host = meta_direct ? reinterpret_cast<int2 *>(static_cast<char *>(pm_dev) + (l.totals - l.meta)) : nullptr;
-  NPoints np;
-  std::memset(&np, 0, sizeof np);
-  np.n[0] = n;
-  if (as_f32) {
-    const float *pts_dev = static_cast<const float *>(ctx->stage_in.ptr);
-    void *mapped = nullptr;
-    if ((k_direct & 1) && hipHostGetDevicePointer(&mapped, ctx->pin_in.ptr, 0) == hipSuccess && mapped)
-      pts_dev = static_cast<const float *>(mapped);
-    else
-      PP_HIP_TRY(hipMemcpyAsync(ctx->stage_in.ptr, ctx->pin_in.ptr, (size_t)n * 16, hipMemcpyHostToDevice, stream));
-    (void)hipGetLastError();
-    rc = launch_pipeline<float>(ctx, stream, pts_dev, l.ncap, 4, 1, 1, np, 1, n, g, P,
-                                N, l, kModeCompact, nullptr, nullptr, static_cast<double *>(ctx->stage_out.ptr), false,
-                                nullptr, nullptr, nullptr, 0, 0, 0, nullptr, k_pack ? 1 : 0, meta_host, totals_host);
-    if (rc) return rc;
-  } else {
-    // the caller's points are a strided view (data/dataset.py:88 passes the transpose of a [4, n] array): rows split
-    // across the pool's threads, then one host-to-device copy
-    double *dst = static_cast<double *>(ctx->pin_in.ptr);
-    pool->run([&](int part, int parts) {
-      const int64_t i0 = (int64_t)n * part / parts, i1 = (int64_t)n * (part + 1) / parts;
-      for (int64_t i = i0; i < i1; ++i)
-        for (int c = 0; c < 4; ++c)
-          std::memcpy(&dst[i * 4 + c], src_pts + i * ps0 + c * ps1, 8);
-    });
-    PP_HIP_TRY(hipMemcpyAsync(ctx->stage_in.ptr, dst, (size_t)n * 32, hipMemcpyHostToDevice, stream));
-    rc = launch_pipeline<double>(ctx, stream, static_cast<const double *>(ctx->stage_in.ptr),
-                                 l.ncap, 4, 1, 1, np, 1, n, g, P, N, l, kModeCompact, nullptr,
-                                 nullptr, static_cast<double *>(ctx->stage_out.ptr), false,
-                                 nullptr, nullptr, nullptr, 0, 0, 0, nullptr, 0, meta_host, totals_host);
-    if (rc) return rc;
-  }
-  // descriptors back in ONE copy: pillar_meta[P] (pillar order, written by k_emit in compact mode) and, behind it in the
-  // workspace, the totals
-  rc = ctx->pin_out.ensure((size_t)l.ncap * 72);
-  if (rc) return rc;
-  char *ws = static_cast<char *>(ctx->vox_ws[0].ptr);
-  if (!meta_direct) PP_HIP_TRY(hipMemcpyAsync(pm, ws + l.meta, meta_bytes, hipMemcpyDeviceToHost, stream));
-  hipEvent_t ev_meta = ctx->chunk_ev[kMaxEv - 1];
-  PP_HIP_TRY(hipEventRecord(ev_meta, stream));
-  // The features follow in chunks: chunk k is scattered while chunk k + 1 is on its way.  How many points the call emits
-  // is only known from the descriptors: the device reads them itself (the direct pieces), or the copies are issued once
-  // the host has them.
-  const bool packed = as_f32 && k_pack;
-  const int64_t rec = packed ? kPackedFeat : 72;  // bytes of a point's features on the way back
-  int64_t cb[kMaxEv + 1];  // chunk c = compact points [cb[c], cb[c + 1])
-  int nch = 0;
-  cb[0] = 0;
-  // (PP_DROPIN_DIRECT & 4) the pieces go out right here, behind the kernels, sized on the device by k_records_to_host
-  int direct_pieces = 0;
-  {
-    void *out_dev = nullptr;
-    if ((k_direct & 4) && N > 0 && hipHostGetDevicePointer(&out_dev, ctx->pin_out.ptr, 0) == hipSuccess && out_dev) {
-      direct_pieces = (int64_t)n * rec >= (256 << 10) ? kChunks : 1;
-      const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(256, ((int64_t)n * rec / direct_pieces + 16 * kCopyThreads - 1) /
-                                                                               (16 * kCopyThreads)));
-      for (int c = 0; c < direct_pieces; ++c) {
-        hipLaunchKernelGGL(k_records_to_host, dim3((unsigned)blocks), dim3(kCopyThreads), 0, stream,
-                           reinterpret_cast<const int2 *>(ws + l.totals), reinterpret_cast<const int4 *>(ws + l.meta), P,
-                           max_pillars, (int)rec, static_cast<const char *>(ctx->stage_out.ptr), static_cast<char *>(out_dev),
-                           c, direct_pieces);
-        PP_HIP_TRY(hipGetLastError());
-        PP_HIP_TRY(hipEventRecord(ctx->chunk_ev[c], stream));
-      }
-    }
-    (void)hipGetLastError();
-  }
-  auto issue_chunks = [&](int64_t upto, int pieces) -> int {
-    const int64_t from = cb[nch];
-    for (int c = 0; c < pieces && nch < kMaxEv - 2; ++c) {
-      const int64_t b1 = from + (upto - from) * (c + 1) / pieces;
-      if (b1 <= cb[nch]) continue;
-      PP_HIP_TRY(hipMemcpyAsync(static_cast<char *>(ctx->pin_out.ptr) + cb[nch] * rec,
-                                static_cast<const char *>(ctx->stage_out.ptr) + cb[nch] * rec, (size_t)(b1 - cb[nch]) * rec,
-                                hipMemcpyDeviceToHost, stream));
-      PP_HIP_TRY(hipEventRecord(ctx->chunk_ev[nch], stream));
-      cb[++nch] = b1;
-    }
-    return PP_OK;
-  };
-  PP_HIP_TRY(wait_event(ev_meta));
-  int tot[2];
-  std::memcpy(tot, pm + (l.totals - l.meta), 8);
-  if (num_cells) *num_cells = tot[0];
-  const int npil = std::min(tot[0], std::min(P, max_pillars));
-  if (npil == 0) {
-    if (direct_pieces) PP_HIP_TRY(hipStreamSynchronize(stream));  // the pieces sent ahead still target the pinned buffer
+  if (int rc = pillars_gather(c)) return rc;
+  if (int rc = pillars_transport(c)) return rc;
+  StreamSyncOnExit sync{c.stream, true};  // armed ahead of the first enqueue: a failure part-way through it is covered too
+  if (int rc = pillars_enqueue(c)) return rc;
+  if (int rc = pillars_read_descriptors(c, num_cells)) return rc;
+  if (c.npil == 0) {
+    if (c.direct_pieces) PP_HIP_TRY(hipStreamSynchronize(c.stream));  // the pieces sent ahead still target the pinned buffer
+    sync.armed = false;
     return PP_OK;
   }
-  const int4 *meta = reinterpret_cast<const int4 *>(pm);
-  const int64_t end = (int64_t)meta[npil - 1].y + meta[npil - 1].z;
-  const char *feat = static_cast<const char *>(ctx->pin_out.ptr);
-  // `live` points' features from compact position `at` into a dense [live][9] run of doubles
-  auto copy_rows = [&](char *dst, int64_t at, int live) {
-    if (!packed) {
-      std::memcpy(dst, feat + at * 72, (size_t)live * 72);
-      return;
-    }
-    const char *src = feat + at * kPackedFeat;
-    for (int k = 0; k < live; ++k, src += kPackedFeat, dst += 72) {
-      float head[4];
-      std::memcpy(head, src, 16);
-      const double wide[4] = {(double)head[0], (double)head[1], (double)head[2], (double)head[3]};
-      std::memcpy(dst, wide, 32);
-      std::memcpy(dst + 32, src + 16, 40);
-    }
-  };
-  char *tp = static_cast<char *>(tensor);
-  char *ip = static_cast<char *>(indices);
-  auto write_index_row = [&](int p) {  // pillars.cpp:389-391
-    int cell = meta[p].x;
-    if (g.order != PP_ORDER_ROW_MAJOR)
-      cell = (int)(((unsigned long long)cell * g.mult_inv) % (unsigned long long)g.ncells);
-    const double canvas_x = (double)(cell % g.nx);
-    const double fy = (double)((g.ny - 1) - cell / g.nx);
-    const double canvas_y = (g.canvas_height - 1) - fy;
-    const double one = 1.0;
-    std::memcpy(ip + p * i_strides[0] + 0 * i_strides[1], &one, 8);
-    std::memcpy(ip + p * i_strides[0] + 1 * i_strides[1], &canvas_x, 8);
-    std::memcpy(ip + p * i_strides[0] + 2 * i_strides[1], &canvas_y, 8);
-  };
-  // The usual caller hands in a C-contiguous [P,N,9] tensor (np.zeros, data/dataset.py:89): a pillar's live points are
-  // then ONE contiguous run of live * 72 bytes -- but 7200 bytes from the next pillar's, in an 86 MB array that no CPU
-  // cache holds: the scatter is a chain of 12 000 cache misses (195 us of round 4's 360 us call on one thread; 150-178
-  // with the next pillars' lines prefetched for writing).  Nothing can go out of range in that layout once the shapes
-  // hold the call's pillars, so the rows -- disjoint -- are split across the pool's threads.
-  const bool dense_t = tensor && t_strides[2] == 8 && t_strides[1] == 72 && t_shape[2] >= 9 && t_shape[1] >= N &&
-                       t_shape[0] >= npil;
-  const bool dense_all = dense_t && indices && i_shape[0] >= npil && i_shape[1] >= 3;
-  if (direct_pieces) {  // the device cut [0, end) at the same places
-    nch = direct_pieces;
-    for (int c = 0; c <= nch; ++c) cb[c] = piece_begin(end, c, nch);
-  } else if (N > 0 && end > 0) {
-    rc = issue_chunks(end, (dense_all && end * rec >= (256 << 10)) ? kChunks : 1);
-    if (rc) return rc;
-  }
+  const bool dense_t = tensor && t_strides[2] == 8 && t_strides[1] == 72 && t_shape[2] >= 9 && t_shape[1] >= c.N &&
+                       t_shape[0] >= c.npil;
+  const bool dense_all = dense_t && indices && i_shape[0] >= c.npil && i_shape[1] >= 3;
+  if (int rc = pillars_issue_chunks(c, dense_all)) return rc;
   if (dense_all) {
-    int p_done = 0;
-    for (int c = 0; c < std::max(nch, 1); ++c) {
-      if (nch) PP_HIP_TRY(wait_event(ctx->chunk_ev[c]));
-      // the pillars whose points have all arrived: start + count <= cb[c + 1]
-      int p_hi = npil;
-      if (nch && cb[c + 1] < end) {
-        int lo = p_done, hi = npil;
-        while (lo < hi) {
-          const int mid = (lo + hi) / 2;
-          if ((int64_t)meta[mid].y + meta[mid].z <= cb[c + 1]) lo = mid + 1; else hi = mid;
-        }
-        p_hi = lo;
-      } else if (c + 1 < nch) {
-        continue;  // everything needed is here already; the later events are waited for at the end
-      }
-      const int p0 = p_done, p1 = p_hi;
-      p_done = p_hi;
-      if (p1 <= p0) continue;
-      pool->run([&](int part, int parts) {
-        const int q0 = p0 + (int)((int64_t)(p1 - p0) * part / parts), q1 = p0 + (int)((int64_t)(p1 - p0) * (part + 1) / parts);
-        constexpr int kAhead = 8;
-        for (int p = q0; p < q1; ++p) {
-          if (p + kAhead < q1) {
-            const char *nx = tp + (int64_t)(p + kAhead) * t_strides[0];
-            const int nl = std::min(meta[p + kAhead].z, N) * 72;
-            for (int o = 0; o < nl; o += 64) __builtin_prefetch(nx + o, 1, 0);
-            if (nl > 0) __builtin_prefetch(nx + nl - 1, 1, 0);
-          }
-          const int live = std::min(meta[p].z, N);
-          if (live > 0) copy_rows(tp + (int64_t)p * t_strides[0], meta[p].y, live);
-          write_index_row(p);
-        }
-      });
-    }
-    if (nch) PP_HIP_TRY(wait_event(ctx->chunk_ev[nch - 1]));  // (the loop may have skipped the later events)
+    if (int rc = pillars_scatter_dense(c)) return rc;  // (returns with the last chunk's event waited for)
+    sync.armed = false;
     return PP_OK;
   }
-  if (nch) PP_HIP_TRY(hipStreamSynchronize(stream));
-  // any other layout (strided views, undersized arrays): one thread, element by element with pybind11 .mutable_at()'s
-  // bounds checks, pillar by pillar like pillars.cpp:335-396 -- the writes made before an IndexError persist, nothing
-  // behind it is touched
-  for (int p = 0; p < npil; ++p) {
-    const int live = std::min(meta[p].z, N);
-    if (dense_t) {
-      if (live > 0) copy_rows(tp + (int64_t)p * t_strides[0], meta[p].y, live);
-    } else
-    for (int k = 0; k < live; ++k) {
-      double f[9];
-      copy_rows(reinterpret_cast<char *>(f), (int64_t)meta[p].y + k, 1);
-      for (int d = 0; d < 9; ++d) {
-        if (!tensor || p >= t_shape[0] || k >= t_shape[1] || d >= t_shape[2]) {
-          set_error("create_pillars: tensor index (%d,%d,%d) out of range", p, k, d);
-          return PP_ERR_INDEX;
-        }
-        std::memcpy(tp + p * t_strides[0] + k * t_strides[1] + d * t_strides[2], &f[d], 8);
-      }
-    }
-    if (!indices || p >= i_shape[0] || 2 >= i_shape[1]) {
-      set_error("create_pillars: indices index (%d,2) out of range", p);
-      return PP_ERR_INDEX;
-    }
-    write_index_row(p);
-  }
-  return PP_OK;
+  if (c.nch) PP_HIP_TRY(hipStreamSynchronize(c.stream));
+  sync.armed = false;  // nothing is in flight any more: a PP_ERR_INDEX below needs no second wait
+  return pillars_scatter_checked(c, dense_t);
 }
