@@ -276,10 +276,14 @@ def test_training_feature_net_matches_pytorch_autograd(gpu):
 
 def test_training_pipeline_step_uses_hip_feature_net(gpu):
     """train_forward_backward with the HIP training feature net vs the same step on the
-    PyTorch modules.  The forward agrees to f32 rounding (losses to 1e-5); the gradients of a
-    deep f32 network with batch-statistics BatchNorm amplify that rounding (two PyTorch runs
-    differ by up to 3e-2 of a tensor's scale from MIOpen's atomics alone), so they are compared
-    by direction: cosine >= 0.999 per tensor group and overall."""
+    PyTorch modules.  The forward agrees to f32 rounding (losses to 1e-5).  The backward of a deep
+    ReLU network is discontinuous: a pre-activation within that rounding of zero takes the other
+    branch, and one such flip moves every gradient upstream of it by up to 1e-1 of a tensor's scale
+    (tests/test_train_step_reference.py).  MIOpen's run-to-run spread is not the cause: two PyTorch
+    runs of such a step differ by 2.6e-6 (tests/test_gpu_loss_fused.py), and on equal masks either
+    leg is within 2.4e-5 of f64 (tests/test_gpu_train_step.py, which gates every tensor).  The two
+    legs here take their own masks, so they are compared by direction: cosine >= 0.999 per tensor
+    group and overall."""
     import torch
     from pp_amd import synth
     from pp_amd.pipeline import PillarPipeline
