@@ -108,6 +108,9 @@ int pp_voxelize_dev(pp_ctx_t *ctx, void *stream, const float *points_dev,
  * carries a batch from one stage to the next): a call on another stream while batches are in flight is
  * refused with PP_ERR_VALUE and changes nothing (drain first, or pp_voxelize_step_reset); plain calls on
  * the same context are unaffected (own workspace).
+ * Workspace: the batches in flight rotate through four workspace slots of the context, each sized on first use and
+ * again when a later batch needs more (pp_voxelize_reserve sizes the plain calls' workspace only).  A call that sizes
+ * a slot allocates, and an allocation may wait for the device; after four batches of the largest shape no call does.
  * HIP graphs: a single call must NOT be captured and replayed -- the workspace slot of every stage
  * rotates from call to call on the host, and a replay would repeat one call's slots.  (The plain
  * pp_voxelize_dev is the capturable form.)
@@ -805,6 +808,8 @@ int pp_voxelize_check(pp_ctx_t *ctx, void *stream);
  *                             holds 16 bytes per cell and sweep for the tiles' descriptor lists
  *   max_points_per_pillar  <= 65536; dense output: max_pillars * max_points_per_pillar <= 1e8
  *   fused feature net      exactly 64 output channels (model/model.py:28)
+ *   alignment              points_dev, pillars_dev, features_dev and canvas_dev 16 bytes (they are accessed 16
+ *                          bytes a lane); indices_dev, prev_indices_dev, clear_indices_dev and num_cells_dev 8 bytes
  * One context per HIP stream: calls on one context must be stream-ordered.
  */
 
