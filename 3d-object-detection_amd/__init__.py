@@ -11,6 +11,7 @@ Layout (only what the hot path needs):
   targets.py     device-resident anchor-target assignment
   boxes.py       anchors / box geometry as flat arrays
   model.py loss.py   PyTorch-ROCm counterpart of model/model.py, model/loss.py
+  optim.py       FusedAdam: the reference's Adam step on csrc/pp_optim.hip (include/pp_optim.h)
   shard.py       one-process-per-GPU sweep sharding (torch.distributed / RCCL)
   synth.py       synthetic clouds and boxes
   evaluate.py    device-resident validation mAP over 3D IoU thresholds (MapEvaluator)

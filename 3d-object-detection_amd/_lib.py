@@ -12,10 +12,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("PP_HIP_LIB") or os.path.join(_HERE, "libpp_hip.so")
 SOURCES = [os.path.join(_HERE, "csrc", f)
-           for f in ("pp_runtime.hip", "pp_voxelize.hip", "pp_iou.hip", "pp_ingest.hip", "pp_decode.hip", "pp_epilogue.hip", "pp_pfn.hip", "pp_pfn_train.hip", "pp_bn_train.hip", "pp_eval.hip", "pp_wino.hip", "pp_conv_f16.hip", "pp_convt_f16.hip", "pp_conv_s2_f16.hip", "pp_stem.hip", "pp_head.hip", "pp_augment.hip", "pp_paste.hip", "pp_loss.hip")]
+           for f in ("pp_runtime.hip", "pp_voxelize.hip", "pp_iou.hip", "pp_ingest.hip", "pp_decode.hip", "pp_epilogue.hip", "pp_pfn.hip", "pp_pfn_train.hip", "pp_bn_train.hip", "pp_eval.hip", "pp_wino.hip", "pp_conv_f16.hip", "pp_convt_f16.hip", "pp_conv_s2_f16.hip", "pp_stem.hip", "pp_head.hip", "pp_augment.hip", "pp_paste.hip", "pp_loss.hip", "pp_optim.hip")]
 HEADERS = [os.path.join(_HERE, "csrc", "pp_common.h"), os.path.join(_HERE, "csrc", "pp_conv_f16_tile.h"),
            os.path.join(_HERE, "csrc", "pp_box_geom.h"),
-           os.path.join(_ROOT, "include", "pp_hip.h")]
+           os.path.join(_ROOT, "include", "pp_hip.h"), os.path.join(_ROOT, "include", "pp_optim.h")]
 
 PP_OK, PP_ERR_INDEX, PP_ERR_VALUE, PP_ERR_WINDING = 0, -2, -3, -4
 PP_ERR_NOMEM, PP_ERR_HIP, PP_ERR_INTERNAL = -5, -6, -7
@@ -34,6 +34,8 @@ EXPORTS = [
     "pp_box3d_iou_dev", "pp_eval_match_batch_dev", "pp_augment_batch_dev", "pp_paste_batch_dev",
     "pp_loss_workspace_bytes", "pp_loss_fwd_dev", "pp_loss_bwd_dev",
 ]
+# the optimizer's entry points: declared in include/pp_optim.h, a header of their own
+OPTIM_EXPORTS = ["pp_adam_workspace_bytes", "pp_adam_pack_dev", "pp_adam_step_dev"]
 
 
 class VoxelParams(ctypes.Structure):
@@ -106,6 +108,17 @@ class LossParams(ctypes.Structure):
                 ("height", ctypes.c_int32), ("width", ctypes.c_int32), ("layout", ctypes.c_int32),
                 ("gamma", ctypes.c_double), ("alpha", ctypes.c_double),
                 ("b_cls", ctypes.c_double), ("b_reg", ctypes.c_double), ("b_ort", ctypes.c_double)]
+
+
+ADAM_MAX_TENSORS = 4096     # PP_ADAM_MAX_TENSORS
+ADAM_STATE_BYTES = 64       # PP_ADAM_STATE_BYTES
+
+
+class AdamParams(ctypes.Structure):
+    """pp_adam_params_t: torch.optim.Adam's hyper-parameters, the gradient scale, clipping and the non-finite skip."""
+    _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
+                ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double), ("grad_scale", ctypes.c_double),
+                ("max_grad_norm", ctypes.c_double), ("skip_nonfinite", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 def _compile(out, defines=(), force=False, verbose=False):
@@ -305,6 +318,13 @@ def _load(path):
     L.pp_loss_workspace_bytes.restype = i64
     L.pp_loss_fwd_dev.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.POINTER(LossParams), vp, vp, vp, vp]
     L.pp_loss_bwd_dev.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.POINTER(LossParams), vp, vp, vp, vp]
+    L.pp_adam_workspace_bytes.argtypes = [ctypes.c_int32, pi64]
+    L.pp_adam_workspace_bytes.restype = i64
+    L.pp_adam_pack_dev.argtypes = [vp, vp, ctypes.c_int32, ctypes.POINTER(vp), pi64, vp]
+    L.pp_adam_pack_dev.restype = c_int
+    L.pp_adam_step_dev.argtypes = [vp, vp, ctypes.c_int32, ctypes.POINTER(vp), ctypes.POINTER(vp), pi64, vp, vp,
+                                   ctypes.POINTER(AdamParams), vp, vp]
+    L.pp_adam_step_dev.restype = c_int
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("pp_last_error", "pp_version", "pp_ctx_destroy", "pp_loss_workspace_bytes"):

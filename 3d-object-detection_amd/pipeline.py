@@ -6,6 +6,8 @@ the loss: ``PPDataset.__getitem__``'s voxel stage and target stage
 (train.py:144-145, evaluate.py:228) on PyTorch-ROCm.  Nothing crosses PCIe
 except the raw points (0.96 MB per 60k-point sweep) and the boxes.
 """
+import functools
+
 import numpy as np
 import torch
 
@@ -282,3 +284,22 @@ class PillarPipeline:
         else:
             total.backward()
         return cls_loss.detach(), reg_loss.detach(), ort_loss.detach(), total.detach()
+
+    def train_step(self, points, gts, optimizer, n_points=None, shard_ctx=None, augment_rng=None):
+        """train.py:139-148 whole: ``optimizer.zero_grad(set_to_none=True)``, ``train_forward_backward`` and the
+        optimizer step; returns the four losses.  With an ``optim.FusedAdam`` and a distributed ``shard_ctx`` the
+        step packs the gradients into the optimizer's flat buffer, all-reduces that once (``shard.allreduce_flat``)
+        and updates from it; with any other optimizer it is ``shard.allreduce_gradients`` and ``optimizer.step()``."""
+        from . import shard
+        from .optim import FusedAdam
+        optimizer.zero_grad(set_to_none=True)
+        losses = self.train_forward_backward(points, gts, n_points=n_points, shard_ctx=shard_ctx,
+                                             augment_rng=augment_rng)
+        distributed = shard_ctx is not None and shard_ctx.distributed
+        if isinstance(optimizer, FusedAdam):
+            optimizer.step(grad_reduce=functools.partial(shard.allreduce_flat, shard_ctx) if distributed else None)
+        else:
+            if distributed:
+                shard.allreduce_gradients(shard_ctx, self.model.parameters())
+            optimizer.step()
+        return losses

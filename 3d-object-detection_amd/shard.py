@@ -155,6 +155,15 @@ def allreduce_gradients(ctx, parameters, bucket_bytes=32 << 20):
     return n_calls
 
 
+def allreduce_flat(ctx, flat):
+    """The ``grad_reduce`` of ``optim.FusedAdam.step`` for a ShardContext: ONE all-reduce(SUM) of the optimizer's flat
+    gradient buffer, in place, and the divisor that makes it the average (the world size) as the return value -- the
+    update kernel applies it, so there is no ``div_`` pass and no copy back into ``p.grad``."""
+    if ctx.distributed:
+        dist.all_reduce(flat, op=dist.ReduceOp.SUM)
+    return float(ctx.world_size)
+
+
 def max_over_ranks(ctx, seconds, device=None):
     t = torch.tensor([float(seconds)], dtype=torch.float64, device=device)
     if ctx.distributed:
