@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -220,6 +221,18 @@ struct pp_ctx {
 
 namespace pp {
 HostPool *host_pool(pp_ctx *ctx);  // the context's pool, created on first use
+
+// the device's compute units, asked once per device (the grid of the persistent kernels)
+inline int compute_units(int device) {
+  static std::atomic<int> cached[64];
+  const bool slot = device >= 0 && device < 64;
+  int n = slot ? cached[device].load(std::memory_order_relaxed) : 0;
+  if (n <= 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n <= 0) n = 256;
+    if (slot) cached[device].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
 
 // launch() on the context's device; kernel names it in the message of a failed launch.
 template <class Launch>

@@ -37,7 +37,6 @@
 #include "pp_common.h"
 
 #include <algorithm>
-#include <atomic>
 
 namespace pp {
 namespace {
@@ -355,18 +354,6 @@ __global__ __launch_bounds__(256, 2) void k_stem_conv(const int *__restrict__ ma
     if (more) map_store(next);
     __syncthreads();
   }
-}
-
-// the device's compute units, asked once per device
-int compute_units(int device) {
-  static std::atomic<int> cached[64];
-  const bool slot = device >= 0 && device < 64;
-  int n = slot ? cached[device].load(std::memory_order_relaxed) : 0;
-  if (n <= 0) {
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n <= 0) n = 256;
-    if (slot) cached[device].store(n, std::memory_order_relaxed);
-  }
-  return n;
 }
 
 }  // namespace

@@ -33,7 +33,35 @@
 //     of V; scalar adds, two to four per gap (packed f32 adds stall beside MFMAs);
 //   - which of this is present (a chunk behind, two chunks behind) is a compile-time property of
 //     the step, so a step's MFMAs, operand reads and transform are one basic block.
+//
+// The walk.  An item is one (16x16-pixel tile, 64-channel output group) pair, numbered
+//   item = ((b * tiles_y + ty) * tiles_x + tx) * groups + group
+// (a tile's output groups next to each other: they read the same halo).  The kernel holds all of a
+// compute unit's LDS and registers, so nothing of a second workgroup can start beside it, and every
+// workgroup pays its start, two cold global round trips, a transform and two barriers with the MFMA
+// pipe idle.  With more items than compute units the host therefore launches G = compute units
+// workgroups of k_conv3x3_wino<true>, and workgroup k computes items k, k + G, k + 2G, ... : a pure
+// function of blockIdx.x, gridDim.x and the item count, nothing shared between workgroups or calls,
+// every trip count known at entry.  The chunks a workgroup runs along its walk form one stream
+// g = 0, 1, 2, ... across its items, and the buffer parities above are parities of g (with an odd chunk
+// count the buffers swap roles from item to item).  In an item's last two steps the staging slots
+// have nothing of that item left to stage; while an item follows on the walk they work for it:
+//   - at the top of the second-to-last step the halo loader moves to the next item (a scalar base
+//     and the 3-bit inside-the-image mask; the per-thread offsets do not depend on the tile), so
+//     that step loads the next item's chunk 0 and the last step its chunk 1;
+//   - the last step copies U of the next item's chunk 0 (its output group) and transforms its
+//     chunk 0 in the gaps.
+// Behind the last step's barrier come the item's output transform and epilogue, then the next
+// item's first step straight away: its operands are in LDS, it sets the accumulators (C = 0), and
+// the epilogue's stores are in flight under it.  Only the output transform and the stores stay
+// exposed between two items.  Per item the arithmetic and its order are those of a one-item launch:
+// the result does not depend on the walk.
+// Which launch takes which form: Cin >= 24 (three chunks or more) and more items than compute units
+// walk; Cin = 8 and Cin = 16 (one or two chunks: no step, or not steps enough, to stage an item in),
+// and every launch of at most as many items as compute units, run k_conv3x3_wino<false>, one item
+// per workgroup.
 
+#include <algorithm>
 #include <utility>
 #include <type_traits>
 
@@ -124,6 +152,15 @@ __device__ __forceinline__ f32x2 sub2(f32x2 a, f32x2 b) {
   return r;
 }
 
+// One element of an accumulator.  The operand is asked for in an accumulator register, which is where
+// the MFMAs leave it: left the choice, the compiler moves whole accumulators to VGPRs ahead of the
+// output transform, and between two items of a walk there are not 256 to spare
+__device__ __forceinline__ float acc_read(float m) {
+  float r;
+  asm("v_accvgpr_read_b32 %0, %1" : "=v"(r) : "a"(m));
+  return r;
+}
+
 // The order of a step's LDS accesses, by position q = 0..15 (step() follows it to the letter):
 //   ahead of position 0:  operands of positions 0 and 1                       (2 + 2 reads)
 //   position q:           wait(q), operands of position q+2 while q+2 < 16    (2 reads)
@@ -146,51 +183,71 @@ constexpr int lds_left(int p, bool tr) {
 // u   [16 pos][Cin/8 chunk][2 half][Cout][4]: U[pos][cin = 8*chunk + 4*half + j][cout] at j.
 // prm [Cout][3] (bias, scale, shift).
 // y   pixel p, channel c at y[p*y_stride + c] (y already offset to the channel slice).
-// grid: x = B * ceil(H/16) * ceil(W/16), y = Cout/64.
+// items = B * ceil(H/16) * ceil(W/16) * groups, groups = Cout/64.
+// grid: x = G <= items workgroups; workgroup k computes items k, k + G, k + 2G, ...
+template <bool kWalk>
 __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict__ x,
                                                          const float *__restrict__ u,
                                                          const float *__restrict__ prm,
                                                          float *__restrict__ y, int H, int W, int Cin,
                                                          int Cout, int64_t y_stride, int tiles_x,
-                                                         int tiles_y) {
+                                                         int tiles_y, int groups, int items) {
   // one array: two V/U buffers, then the two halo buffers
   __shared__ __attribute__((aligned(16))) float lds[2 * kBufFloats + 2 * kHaloFloats];
   float *const halo = lds + 2 * kBufFloats;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int bx = blockIdx.x % tiles_x;
-  const int rest = blockIdx.x / tiles_x;
-  const int by = rest % tiles_y;
-  const int b = rest / tiles_y;
-  const int oy0 = by * 16, ox0 = bx * 16;
-  const int co0 = blockIdx.y * kCo;
   const int nchunks = Cin / kKc;
 
+  // ---- the walk: item = (tile, output group), a tile's groups numbered next to each other.  All of
+  // it is wave-uniform
+  struct Item {
+    int b, oy0, ox0, co0;
+  };
+  auto decode = [&](int item) {
+    const int t = item / groups, bx = t % tiles_x, rest = t / tiles_x;
+    return Item{rest / tiles_y, (rest % tiles_y) * 16, bx * 16, (item % groups) * kCo};
+  };
+
   // ---- halo loader: piece q = tid + 256*i is half (q&1) of halo pixel q>>1, image pixel
-  // (oy0 - 1 + pix/18, ox0 - 1 + pix%18).  hin: the pixel is inside the image
-  const float *xb = x + (int64_t)b * H * W * Cin;
-  int64_t hoff[kHaloPer];
+  // (oy0 - 1 + pix/18, ox0 - 1 + pix%18), at hx + hoff[i]: hx is the tile's halo pixel 0, chunk 0
+  // (a scalar; outside the image for an edge tile, never dereferenced there), hoff[i] a constant of
+  // the thread in bytes.  hin: the pixel is inside the image.  set_halo() points both at an item
+  unsigned hoff[kHaloPer];
   int hdst[kHaloPer];
-  unsigned hin = 0, hown = 0;
+  unsigned hown = 0;
 #pragma unroll
   for (int i = 0; i < kHaloPer; ++i) {
     const int q = tid + 256 * i;
     const int pix = q >> 1, hf = q & 1;
-    const int iy = oy0 - 1 + pix / kHaloW, ix = ox0 - 1 + pix % kHaloW;
-    hoff[i] = ((int64_t)iy * W + ix) * Cin + 4 * hf;
+    hoff[i] = (unsigned)(((pix / kHaloW) * W + pix % kHaloW) * Cin + 4 * hf) * 4u;
     hdst[i] = hf * kHaloHalf + pix * 4;
-    if (q < kHaloPieces) {
-      hown |= 1u << i;
-      if (iy >= 0 && iy < H && ix >= 0 && ix < W) hin |= 1u << i;
-    }
+    if (q < kHaloPieces) hown |= 1u << i;
   }
-  auto hload = [&](int chunk, float4 (&hr)[kHaloPer]) {
-    const float *xc = xb + chunk * kKc;
+  const float *hx = x;
+  unsigned hin = 0;
+  auto set_halo = [&](const Item &it) {
+    hx = x + (((int64_t)it.b * H + (it.oy0 - 1)) * W + (it.ox0 - 1)) * Cin;
+    hin = 0;
+    // computed afresh per item: hoisted out of the walk, the thread's pixel coordinates would live in
+    // registers through every step
+    int tq = tid;
+    asm volatile("" : "+v"(tq));
+#pragma unroll
+    for (int i = 0; i < kHaloPer; ++i) {
+      const int pix = (tq + 256 * i) >> 1;
+      const int iy = it.oy0 - 1 + pix / kHaloW, ix = it.ox0 - 1 + pix % kHaloW;
+      if (((hown >> i) & 1) && iy >= 0 && iy < H && ix >= 0 && ix < W) hin |= 1u << i;
+    }
+  };
+  // xc: hx of the chunk's item + 8 * its chunk index
+  auto hload = [&](const float *xc, float4 (&hr)[kHaloPer]) {
 #pragma unroll
     for (int i = 0; i < kHaloPer; ++i) {
       hr[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      if ((hin >> i) & 1) hr[i] = *reinterpret_cast<const float4 *>(xc + hoff[i]);
+      if ((hin >> i) & 1)
+        hr[i] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(xc) + hoff[i]);
     }
   };
   auto hstore = [&](float *hb, const float4 (&hr)[kHaloPer]) {
@@ -203,20 +260,29 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
   // pieces w, w + 4, ... (lane l the l-th 16 bytes), global memory to LDS directly, one piece behind
   // the last MFMA of each of a step's positions 0..7
   const int64_t useg = (int64_t)2 * Cout * 4;   // floats per (pos, chunk)
-  const float *ub = u + (int64_t)co0 * 4 + lane * 4;
+  const unsigned ulane = lane * 16;    // bytes
   // issued as an asm statement: the compiler takes an LDS-DMA builtin for a store to any LDS address and
   // drains vmcnt ahead of the chunk's first operand read.  Nothing counts these copies but the vmcnt(0)
-  // that step() issues itself before its barrier
-  auto upiece = [&](int chunk, float *buf, int i) {   // the wave's i-th piece, i = 0..7
+  // that step() issues itself before its barrier.  The piece's address is a scalar, the lane's 16 bytes
+  // a 32-bit offset: eight 64-bit addresses per lane would live in registers through the whole walk.
+  // Piece i is (pos, half) = ((wave >> 1) + 2i, wave & 1): ufirst() is the wave's piece 0 of a chunk
+  // (co0: the output group of the chunk's item), and from piece to piece the address grows by ustride.
+  // upiece() takes that step itself, behind an empty asm statement, or all eight addresses are formed
+  // at the top of the step and held in scalar registers there are not enough of
+  const int64_t ustride = 2 * nchunks * useg;
+  auto ufirst = [&](int co0, int chunk) {
+    return u + (((int64_t)(wave >> 1) * nchunks + chunk) * useg + (int64_t)(wave & 1) * Cout * 4 + co0 * 4);
+  };
+  auto upiece = [&](const float *&src, float *buf, int i) {   // the wave's i-th piece, i = 0..7 in turn
     const unsigned dst0 = (unsigned)(uintptr_t)(lptr_t)(buf + kVFloats) + wave * (kCo * 4 * 4);
-    const int seg = wave + 4 * i;     // pos*2 + half
-    const float *src = ub + ((int64_t)(seg >> 1) * nchunks + chunk) * useg + (int64_t)(seg & 1) * Cout * 4;
     const unsigned dst = __builtin_amdgcn_readfirstlane(dst0 + i * (4 * kCo * 4 * 4));
     unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep)
-                 : "v"(src), "s"(dst)
+                 : "v"(ulane), "s"(dst), "s"(src)
                  : "memory");
+    src += ustride;
+    asm volatile("" : "+s"(src));
   };
 
   // ---- transform: thread = (tile, channel pair) of the input patch, read from the halo buffer.
@@ -262,20 +328,23 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
   // in VGPRs until it starts, and they spill
   f32x16 acc[16];
 
-  // one chunk: the halo loads of chunk+2 and the U copy of chunk+1 are issued, the MFMAs run on
-  // `cur` with chunk+1's halo transformed into `nxt` in their gaps, then chunk+2's halo is written
-  // to LDS.  first: the accumulators are set, not added to; more, more2: chunk+1, chunk+2 exist
+  // one chunk, g of the workgroup's stream (par = g & 1): the halo loads of chunk g+2 and the U copy
+  // of chunk g+1 are issued, the MFMAs run on `cur` with the halo of g+1 transformed into `nxt` in
+  // their gaps, then the halo of g+2 is written to LDS.  first: the accumulators are set, not added
+  // to (an item's chunk 0); more, more2: chunks g+1, g+2 exist.  hsrc: where chunk g+2's halo is
+  // read (hload's xc); uco, uchunk: the output group and the chunk index, in its item, of chunk g+1
   const unsigned lds_addr = (unsigned)(uintptr_t)(lptr_t)lds;
-  auto step = [&](int chunk, auto first_, auto more_, auto more2_) {
+  auto step = [&](unsigned par, const float *hsrc, int uco, int uchunk, auto first_, auto more_,
+                  auto more2_) __attribute__((always_inline)) {
     constexpr bool first = decltype(first_)::value, more = decltype(more_)::value,
                    more2 = decltype(more2_)::value;
-    constexpr bool tr = more;   // the transform of chunk+1 rides in this step's gaps
-    const unsigned cur = lds_addr + (chunk & 1) * (kBufFloats * 4);
-    float *const nxt = lds + ((chunk + 1) & 1) * kBufFloats;
+    constexpr bool tr = more;   // the transform of chunk g+1 rides in this step's gaps
+    const unsigned cur = lds_addr + par * (kBufFloats * 4);
+    float *const nxt = lds + (par ^ 1) * kBufFloats;
     const unsigned a_addr = cur + a_off * 4, b_addr = cur + b_off * 4;
-    // the transform's patch (halo buffer of chunk+1) and its V (in `nxt`)
-    const unsigned p_addr = lds_addr + (2 * kBufFloats + ((chunk + 1) & 1) * kHaloFloats + p_off) * 4;
-    const unsigned v_addr = lds_addr + (((chunk + 1) & 1) * kBufFloats + v_off) * 4;
+    // the transform's patch (halo buffer of chunk g+1) and its V (in `nxt`)
+    const unsigned p_addr = lds_addr + (2 * kBufFloats + (par ^ 1) * kHaloFloats + p_off) * 4;
+    const unsigned v_addr = lds_addr + ((par ^ 1) * kBufFloats + v_off) * 4;
     constexpr int kPos = 2 * kTiles * 4 * 4;   // bytes from position to position, V and U alike
     static_assert(kTiles == kCo, "one position stride for V and U");
     f32x4 av[3], bv[3];
@@ -285,7 +354,8 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
     lds_read16<kPos>(av[1], a_addr);
     lds_read16<kPos>(bv[1], b_addr);
     float4 hr[kHaloPer];
-    if constexpr (more2) hload(chunk + 2, hr);
+    if constexpr (more2) hload(hsrc, hr);
+    const float *usrc = ufirst(uco, uchunk);
     static_for<16>([&](auto pc) {
       constexpr int p = decltype(pc)::value, s = p % 3;
       constexpr int left = lds_left(p, tr);
@@ -345,23 +415,28 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
       __builtin_amdgcn_sched_barrier(0);
       // ---- gap 3
       acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s].w, bv[s].w, acc[p], 0, 0, 0);
-      // `nxt` was last read in chunk-1, before the barrier that ended it
-      if constexpr (more && p < 8) upiece(chunk + 1, nxt, p);
+      // `nxt` was last read in chunk g-1, before the barrier that ended it
+      if constexpr (more && p < 8) upiece(usrc, nxt, p);
       __builtin_amdgcn_sched_barrier(0);
     });
-    // this halo buffer held chunk's own halo, last read by the transform of chunk-1's step
-    if constexpr (more2) hstore(halo + (chunk & 1) * kHaloFloats, hr);
+    // this halo buffer held chunk g's own halo, last read by the transform of chunk g-1's step
+    if constexpr (more2) hstore(halo + par * kHaloFloats, hr);
     // the U copy and the V writes: the compiler knows of neither
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();
   };
 
+  // ---- the workgroup's first item: nothing to hide behind
+  int item = blockIdx.x;
+  Item it = decode(item);
+  set_halo(it);
   {
     float4 h0[kHaloPer], h1[kHaloPer];
-    hload(0, h0);
-    if (nchunks > 1) hload(1, h1);
+    hload(hx, h0);
+    if (nchunks > 1) hload(hx + kKc, h1);
+    const float *usrc = ufirst(it.co0, 0);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) upiece(0, lds, i);
+    for (int i = 0; i < 8; ++i) upiece(usrc, lds, i);
     hstore(halo, h0);
     if (nchunks > 1) hstore(halo + kHaloFloats, h1);
     __builtin_amdgcn_s_waitcnt(kWaitVm0);
@@ -369,52 +444,97 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
     transform(halo, lds);
     __syncthreads();
   }
-  // the chunk loop, peeled: first, steady, second-to-last and last
-  constexpr std::true_type yes{};
-  constexpr std::false_type no{};
-  if (nchunks == 1) {
-    step(0, yes, no, no);
-  } else if (nchunks == 2) {
-    step(0, yes, yes, no);
-    step(1, no, no, no);
-  } else {
-    step(0, yes, yes, yes);
-#pragma unroll 1
-    for (int chunk = 1; chunk < nchunks - 2; ++chunk) step(chunk, no, yes, yes);
-    step(nchunks - 2, no, yes, no);
-    step(nchunks - 1, no, no, no);
-  }
 
   // ---- output transform Y = A^T M A (A^T = [1 1 1 0; 0 1 -1 -1]) and the epilogue, per lane:
   // channel co0 + 32wc + l32, tiles 32wt + (r&3) + 8(r>>2) + 4h for accumulator register r
-  const int co = co0 + 32 * wc + l32;
-  const float eb = prm[co * 3 + 0], es = prm[co * 3 + 1], et = prm[co * 3 + 2];
-  // wait for the three constants here, once.  Every store below sits behind a bounds check of its
-  // own; left to the first use, the wait is repeated inside each of those branches, and as stores
-  // count in vmcnt too, each store then waits for the one before it to complete
-  __builtin_amdgcn_s_waitcnt(kWaitVm0);
-  float *yb = y + (int64_t)b * H * W * y_stride + co;
+  auto finish = [&](const Item &it) __attribute__((always_inline)) {
+    // the lane's part of the 64 store addresses is formed here, per item, for the same reason as
+    // set_halo()'s pixels
+    int hq = h, lq = l32;
+    asm volatile("" : "+v"(hq), "+v"(lq));
+    const int co = it.co0 + 32 * wc + lq;
+    const float eb = prm[co * 3 + 0], es = prm[co * 3 + 1], et = prm[co * 3 + 2];
+    // wait for the three constants here, once.  Every store below sits behind a bounds check of its
+    // own; left to the first use, the wait is repeated inside each of those branches, and as stores
+    // count in vmcnt too, each store then waits for the one before it to complete
+    __builtin_amdgcn_s_waitcnt(kWaitVm0);
+    float *yb = y + (int64_t)it.b * H * W * y_stride + co;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int t = 32 * wt + (r & 3) + 8 * (r >> 2) + 4 * h;
-    const int oy = oy0 + 2 * (t >> 3), ox = ox0 + 2 * (t & 7);
-    float tm[2][4];
+    for (int r = 0; r < 16; ++r) {
+      const int t = 32 * wt + (r & 3) + 8 * (r >> 2) + 4 * hq;
+      const int oy = it.oy0 + 2 * (t >> 3), ox = it.ox0 + 2 * (t & 7);
+      float tm[2][4];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      tm[0][c] = acc[c][r] + acc[4 + c][r] + acc[8 + c][r];
-      tm[1][c] = acc[4 + c][r] - acc[8 + c][r] - acc[12 + c][r];
+      for (int c = 0; c < 4; ++c) {
+        const float m0 = acc_read(acc[c][r]), m1 = acc_read(acc[4 + c][r]), m2 = acc_read(acc[8 + c][r]),
+                    m3 = acc_read(acc[12 + c][r]);
+        tm[0][c] = m0 + m1 + m2;
+        tm[1][c] = m1 - m2 - m3;
+      }
+#pragma unroll
+      for (int a = 0; a < 2; ++a) {
+        const float y0 = tm[a][0] + tm[a][1] + tm[a][2];
+        const float y1 = tm[a][1] - tm[a][2] - tm[a][3];
+        float *yp = yb + ((int64_t)(oy + a) * W + ox) * y_stride;
+        // partial edge tiles: nothing past H or W is stored
+        if (oy + a < H && ox < W) yp[0] = fmaxf(y0 + eb, 0.0f) * es + et;
+        if (oy + a < H && ox + 1 < W) yp[y_stride] = fmaxf(y1 + eb, 0.0f) * es + et;
+      }
+      // one register's 16 positions at a time: hoisting every accumulator read ahead spills
+      __builtin_amdgcn_sched_barrier(0);
     }
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      const float y0 = tm[a][0] + tm[a][1] + tm[a][2];
-      const float y1 = tm[a][1] - tm[a][2] - tm[a][3];
-      float *yp = yb + ((int64_t)(oy + a) * W + ox) * y_stride;
-      // partial edge tiles: nothing past H or W is stored
-      if (oy + a < H && ox < W) yp[0] = fmaxf(y0 + eb, 0.0f) * es + et;
-      if (oy + a < H && ox + 1 < W) yp[y_stride] = fmaxf(y1 + eb, 0.0f) * es + et;
+  };
+
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  unsigned par = 0;     // g & 1
+  // an item's chunks up to its last two: first, then steady
+  auto head = [&](const Item &it) __attribute__((always_inline)) {
+    step(par, hx + 2 * kKc, it.co0, 1, yes, yes, yes);
+    par ^= 1;
+#pragma unroll 1
+    for (int chunk = 1; chunk < nchunks - 2; ++chunk) {
+      step(par, hx + (chunk + 2) * kKc, it.co0, chunk + 1, no, yes, yes);
+      par ^= 1;
     }
-    // one register's 16 positions at a time: hoisting every accumulator read ahead spills
-    __builtin_amdgcn_sched_barrier(0);
+  };
+  if constexpr (!kWalk) {
+    // the chunk loop, peeled: first, steady, second-to-last and last
+    if (nchunks == 1) {
+      step(0, hx, 0, 0, yes, no, no);
+    } else if (nchunks == 2) {
+      step(0, hx, it.co0, 1, yes, yes, no);
+      step(1, hx, 0, 0, no, no, no);
+    } else {
+      head(it);
+      step(par, hx, it.co0, nchunks - 1, no, yes, no);
+      step(par ^ 1, hx, 0, 0, no, no, no);
+    }
+    finish(it);
+  } else {
+    // three chunks or more, and the same peeled loop per item; but while an item follows, the staging
+    // slots of its last two steps, empty above, work for that item
+    const int wg = gridDim.x;
+    head(it);
+    // the items behind this one on the walk: a trip count known here
+#pragma unroll 1
+    for (int left = (items - 1 - item) / wg; left > 0; --left) {
+      // chunks g+2 and, one step on, g+1 lie in the next item.  This item's halo loads are all issued
+      // and written to LDS: the loader moves on
+      item += wg;
+      const Item nx = decode(item);
+      set_halo(nx);
+      step(par, hx, it.co0, nchunks - 1, no, yes, yes);
+      step(par ^ 1, hx + kKc, nx.co0, 0, no, yes, yes);
+      // the next item's V and U of chunk 0 and its halo of chunk 1 are in LDS behind that step's barrier;
+      // the stores of this one are in flight during the next one's first step
+      finish(it);
+      it = nx;
+      head(it);
+    }
+    step(par, hx, it.co0, nchunks - 1, no, yes, no);
+    step(par ^ 1, hx, 0, 0, no, no, no);
+    finish(it);
   }
 }
 
@@ -441,15 +561,22 @@ extern "C" int pp_conv3x3_wino_nhwc_dev(pp_ctx_t *ctx, void *stream_, const floa
     return PP_ERR_VALUE;
   }
   const int64_t tiles_x = (width + 15) / 16, tiles_y = (height + 15) / 16;
-  const int64_t blocks = (int64_t)batch * tiles_x * tiles_y;
-  if (blocks > 0x7fffffff || (int64_t)batch * height * width * std::max<int64_t>(in_channels, y_channels) >
-                                 ((int64_t)1 << 40)) {
+  const int64_t groups = out_channels / 64;
+  const int64_t items = (int64_t)batch * tiles_x * tiles_y * groups;
+  // the last limit: a thread's halo offsets inside a tile, in bytes, are 32-bit
+  if (items > 0x7fffffff || (int64_t)batch * height * width * std::max<int64_t>(in_channels, y_channels) >
+                                ((int64_t)1 << 40) || ((int64_t)17 * width + 18) * in_channels >= ((int64_t)1 << 29)) {
     set_error("pp_conv3x3_wino_nhwc_dev: tensor too large");
     return PP_ERR_VALUE;
   }
+  // one workgroup owns a compute unit.  With more items than units the workgroups stay and walk; a
+  // reduction of one or two chunks keeps one item per workgroup
+  const int64_t units = compute_units(ctx->device);
+  const bool walk = in_channels >= 3 * kKc && items > units;
   return launch_on_device(ctx, "k_conv3x3_wino", [&] {
-    hipLaunchKernelGGL(k_conv3x3_wino, dim3((unsigned)blocks, (unsigned)(out_channels / 64)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream_), x_dev, u_dev, params_dev, y_dev + y_channel_offset,
-                       height, width, in_channels, out_channels, y_channels, (int)tiles_x, (int)tiles_y);
+    hipLaunchKernelGGL(walk ? k_conv3x3_wino<true> : k_conv3x3_wino<false>, dim3((unsigned)(walk ? units : items)),
+                       dim3(256), 0, static_cast<hipStream_t>(stream_), x_dev, u_dev, params_dev,
+                       y_dev + y_channel_offset, height, width, in_channels, out_channels, y_channels, (int)tiles_x,
+                       (int)tiles_y, (int)groups, (int)items);
   });
 }
