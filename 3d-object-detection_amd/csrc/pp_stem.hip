@@ -17,16 +17,30 @@
 //                    the whole launch.  Per tile: the 17x33 map cells -> nine per-tap lists of (pillar,
 //                    local output) pairs (an output has at most one pair per tap, so a list holds at most
 //                    128 pairs: the lists are sized for a fully occupied tile) -> per tap, blocks of 16
-//                    pairs: the pairs' feature rows (gathered one block ahead, L2 resident) times W[tap]
-//                    on v_mfma_f32_16x16x4_f32, the 16 result rows added to the f32 accumulator tile in
-//                    LDS -> epilogue, one 16-byte store per thread and 4 channels, which also leaves the
-//                    accumulator zero for the next tile.  The next tile's map cells and their index checks
-//                    are loaded while the current tile is in its taps and its epilogue.
+//                    pairs: the pairs' feature rows times W[tap] on v_mfma_f32_16x16x4_f32, the 16 result
+//                    rows added to the f32 accumulator tile in LDS -> epilogue, one 16-byte store per thread
+//                    and 4 channels, which also leaves the accumulator zero for the next tile.  The next
+//                    tile's map cells and their index checks are loaded while the current tile is in its
+//                    taps and its epilogue.
+//                    With Cin = 64 the feature rows come from an LDS stage that the workgroup fills once for
+//                    its four waves (each of which needs every row, for its own 16 output channels): the
+//                    tile's blocks, tap after tap, form chunks of four, a chunk's 64 rows are fetched
+//                    together by LDS-DMA, 16 bytes per lane, into one half of the stage while the blocks of
+//                    the chunk before are multiplied out of the other half, and the MFMA's A operand is
+//                    read from there (rows swizzled on the source address, so that the 16 rows of a block
+//                    do not share banks).  A block's sums are added to the accumulator between the MFMAs of
+//                    the block after it.  The generic instance gathers per wave, one block at a time.
 //                    Tiles are numbered position-major with the sweeps interleaved (tile = position * B +
 //                    sweep).  Real sweeps are dense around the sensor, so the same few positions carry most
 //                    of the pairs in every sweep, and the kernel takes as long as the workgroup with the most
 //                    pairs: numbered this way the tiles one grid apart that a workgroup walks lie at
-//                    positions far apart instead of at one position of every sweep.
+//                    positions far apart instead of at one position of every sweep.  Each row of positions is
+//                    also rotated against the row above (one whole turn over the canvas's height), so that
+//                    those tiles lie in different columns as well: without it the workgroups of the middle
+//                    columns walk nothing but crowded tiles.  The rotation is a heuristic for the headline's
+//                    ratio of grid to tiling (512 workgroups, 32 x 16 positions, B = 4: a workgroup's tiles
+//                    lie 8 rows apart in one column); for other shapes it is harmless and may balance nothing,
+//                    and a crowded tile stays one chain of blocks whatever the numbering.
 //
 // Summation order.  Wave w owns output channels [16w, 16w+16) of the accumulator tile for ALL
 // outputs and walks the taps 0..8 in order, so an accumulator element is only ever touched by one
@@ -47,6 +61,10 @@ constexpr int kTH = 8, kTW = 16;                      // output pixels per workg
 constexpr int kOut = kTH * kTW;                       // 128: also the longest per-tap list
 constexpr int kMH = 2 * kTH + 1, kMW = 2 * kTW + 1;   // 17 x 33 map cells feed them
 constexpr int kAcc = 68;                              // floats per accumulator row (64 + 16-byte pad)
+constexpr int kStageBlocks = 8;                       // the row stage: two chunks of four 16-pair blocks
+constexpr int kWaitVm0 = 0x0F70;                      // s_waitcnt immediate: vmcnt(0), the other counters at their maxima
+
+typedef __attribute__((address_space(3))) void *lptr_t;
 
 // one wave per 64 pillars x 64 channels (k_scatter_canvas's transpose); the waves of channel block 0
 // also enter the pillars into the cell map
@@ -96,6 +114,8 @@ __global__ __launch_bounds__(256) void k_stem_prepare(const float *__restrict__ 
 //           for pixels past the image's edge)
 //   s_map   all 17 x 33 entries are written (pillar or -1) for every tile, before the barrier its lists wait on
 //   s_cnt   all nine counts are written for every tile; of the lists only entries below the count are read
+//   s_stage a block's rows are read only after this tile's own loads of them have been waited for, by every
+//           wave, before a workgroup barrier; no load is in flight when a tile's taps end
 template <int CIN>
 __global__ __launch_bounds__(256, 2) void k_stem_conv(const int *__restrict__ map,
                                                    const long long *__restrict__ idx,
@@ -110,8 +130,11 @@ __global__ __launch_bounds__(256, 2) void k_stem_conv(const int *__restrict__ ma
   __shared__ int s_lp[9][kOut];            // per tap: the pairs' pillars ...
   __shared__ __attribute__((aligned(4))) unsigned char s_lo[9][kOut];  // ... and local outputs
   __shared__ int s_cnt[9];
+  // CIN = 64: the pairs' feature rows, 256 bytes each, of two chunks of 64 pairs (see the taps below)
+  static_assert(CIN == 0 || CIN == 64, "the row stage is laid out for 256-byte rows");
+  __shared__ __attribute__((aligned(16))) float s_stage[CIN ? kStageBlocks * 16 * CIN : 4];
   const int Cin = CIN ? CIN : cin_rt;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int i16 = lane & 15, kq = lane >> 4;
   const int batch = (int)(tiles / (tiles_x * tiles_y));
 
@@ -146,16 +169,24 @@ __global__ __launch_bounds__(256, 2) void k_stem_conv(const int *__restrict__ ma
   auto place = [&](int64_t tile, int &b, int &oy0, int &ox0) {
     const int pos = (int)(tile / batch);
     b = (int)(tile - (int64_t)pos * batch);
-    oy0 = pos / tiles_x * kTH;
-    ox0 = pos % tiles_x * kTW;
+    // ... and every row of positions rotated against the one above it, by a whole turn over the canvas's
+    // height: the tiles a grid apart that a workgroup walks then also lie in different columns, not all of
+    // them in the crowded middle ones
+    const int ty = pos / tiles_x;
+    oy0 = ty * kTH;
+    ox0 = (pos % tiles_x + (int)((int64_t)ty * tiles_x / tiles_y)) % tiles_x * kTW;
   };
   auto map_fetch = [&](int64_t tile) {
     int b, oy0, ox0;
     place(tile, b, oy0, ox0);
     const int *mb = map + (int64_t)b * H * W;
+    // the cells' rows and columns are worked out anew for every tile: kept across the taps they would cost six
+    // registers that the taps do not have
+    int tc = tid;
+    asm volatile("" : "+v"(tc));
 #pragma unroll
     for (int k = 0; k < kCells; ++k) {
-      const int i = tid + 256 * k, r = i / kMW, c = i - r * kMW;
+      const int i = tc + 256 * k, r = i / kMW, c = i - r * kMW;
       const int iy = 2 * oy0 - 1 + r, ix = 2 * ox0 - 1 + c;
       mp[k] = -1;
       if (i < kMH * kMW && iy >= 0 && iy < H && ix >= 0 && ix < W) mp[k] = mb[(int64_t)iy * W + ix];
@@ -183,9 +214,13 @@ __global__ __launch_bounds__(256, 2) void k_stem_conv(const int *__restrict__ ma
   auto map_store = [&](int64_t tile) {
     int b, oy0, ox0;
     place(tile, b, oy0, ox0);
+    // the cells' rows and columns are worked out anew for every tile: kept across the taps they would cost six
+    // registers that the taps do not have
+    int tc = tid;
+    asm volatile("" : "+v"(tc));
 #pragma unroll
     for (int k = 0; k < kCells; ++k) {
-      const int i = tid + 256 * k, r = i / kMW, c = i - r * kMW;
+      const int i = tc + 256 * k, r = i / kMW, c = i - r * kMW;
       const int iy = 2 * oy0 - 1 + r, ix = 2 * ox0 - 1 + c;
       int p = mp[k];
       if (p >= 0 && (mf[k] == 0 || mc[k] != ix || mr[k] != iy)) p = -1;
@@ -238,67 +273,139 @@ __global__ __launch_bounds__(256, 2) void k_stem_conv(const int *__restrict__ ma
     // every tap in order, blocks of 16 pairs; rows past a list's end repeat the block's first pair and
     // their results are dropped
     {
-      const float *rb = rows + (int64_t)b * P * Cin + 2 * kq;
       float *acc = s_acc + wave * 16 + i16;
       const int myc = lane < 9 ? s_cnt[lane] : 0;  // lane t: the length of tap t's list
       if constexpr (CIN != 0) {
-        // The only global reads left are the row gathers.  `an` holds, or waits for, the rows of block
-        // (nt, nr): at a block's start that is the block itself.  The cursor then moves on to the block after
-        // it -- the same tap's next block or the first block of the next tap that has pairs -- and each 8-byte
-        // piece of that block's rows is requested into the registers of `an` as soon as the two MFMAs that
-        // read them have been issued, so a gather has one block's work to arrive in.  After the tile's last
-        // block the cursor stays where it is and the same rows are simply read again.
-        const unsigned ne = (unsigned)__ballot(myc > 0);
-        int nt = ne ? __builtin_ctz(ne) : 9, nr = 0;
-        float2 an[CIN / 8];
-        auto block_rows = [&]() -> const float * {
-          const int cn = __builtin_amdgcn_readlane(myc, nt);
-          const int p = s_lp[nt][nr + i16 < cn ? nr + i16 : nr];
-          return rb + (int64_t)p * CIN;
-        };
-        if (nt < 9) {
-          const float *ar = block_rows();
-#pragma unroll
-          for (int j = 0; j < CIN / 8; ++j) an[j] = *reinterpret_cast<const float2 *>(ar + 8 * j);
-        }
+        // The only global reads left are the row gathers, and the workgroup makes them once for its four waves.
+        // The tile's blocks, tap after tap, are numbered 0 .. nblk-1 (tap t's first one is bo[t]); four
+        // blocks are a chunk, and the stage holds two chunks: block g's 16 rows sit at stage row 16 * (g % 8).
+        // Wave w fetches block 4c + w of chunk c with four LDS-DMA loads of 1 KiB (4 rows x 16 lanes x 16
+        // bytes), so all 64 rows of a chunk are in flight together.  The loads of chunk c + 1 are issued when
+        // chunk c has landed (each wave waits for its own, then the workgroup barrier) and so have the four
+        // blocks of chunk c to arrive in; the barrier also says that everyone is done reading chunk c - 1,
+        // whose half of the stage they overwrite.
+        // Layout: LDS-DMA writes lane-linear, and 256-byte rows would put the 16 rows of a block on the same
+        // banks, so the 16-byte piece that lands in slot q of stage row r is piece q ^ (r & 15) of the feature
+        // row, and the reader of piece s looks in slot s ^ (r & 15): a half-wave's ds_read_b64 then covers all
+        // 64 banks once.
+        // Every address comes from a list entry, i.e. from a pillar that has passed map_store's verdict.  Rows
+        // past a list's end fetch the block's first row again; they only reach result rows that are dropped.
+        int cn[9], bo[10];
+        bo[0] = 0;
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
-          const int n = __builtin_amdgcn_readlane(myc, t);
-#pragma unroll 1
-          for (int r0 = 0; r0 < n; r0 += 16) {
-            if (nr + 16 < n) {
-              nr += 16;
-            } else if (ne >> (t + 1)) {
-              nt = t + 1 + __builtin_ctz(ne >> (t + 1));
-              nr = 0;
-            }
-            const float *ar = block_rows();
-            // the block's four result rows of this lane: outputs and their sums so far
-            const unsigned lo4 = *reinterpret_cast<const unsigned *>(&s_lo[t][r0 + 4 * kq]);
-            float *ap[4], old[4];
+          cn[t] = __builtin_amdgcn_readlane(myc, t);
+          bo[t + 1] = bo[t] + ((cn[t] + 15) >> 4);
+        }
+        const int nblk = bo[9];
+        const unsigned stage0 = (unsigned)(uintptr_t)(lptr_t)s_stage;
+        auto stage_chunk = [&](int c) {
+          const int blk = 4 * c + wave;
+          if (blk >= nblk) return;  // whole wave
+          int tt = 0, tb = 0;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              ap[r] = acc + (int)((lo4 >> (8 * r)) & (kOut - 1)) * kAcc;  // masked: bytes past the list's end
-              old[r] = *ap[r];
+          for (int u = 1; u < 9; ++u)
+            if (blk >= bo[u]) {  // the last tap that starts at or before blk: never an empty one, as blk < nblk
+              tt = u;
+              tb = bo[u];
             }
+          const int tn = __builtin_amdgcn_readlane(myc, tt);
+          const int r0 = (blk - tb) * 16;
+          const int *lp = s_lp[tt];
+          int p4[4];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) p4[k] = lp[r0 + 4 * k + kq < tn ? r0 + 4 * k + kq : r0];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const int i = 4 * k + kq;  // the lane's row of the block
+            const float *src = rows + ((int64_t)b * P + p4[k]) * CIN + 4 * (i16 ^ i);
+            const unsigned dst =
+                __builtin_amdgcn_readfirstlane(stage0 + (unsigned)(((blk & 7) * 16 + 4 * k) * CIN * 4));
+            unsigned keep;
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
+                         "s_mov_b32 m0, %0"
+                         : "=&s"(keep)
+                         : "v"(src), "s"(dst)
+                         : "memory");
+          }
+        };
+        // lane (i16, kq) reads channels 8j + 2kq + {0, 1} of row i16: piece 2j + (kq >> 1), its half kq & 1
+        const float *sa = s_stage + i16 * CIN + 2 * (kq & 1);
+        const int sx = 4 * ((kq >> 1) ^ i16);
+        auto block_rows = [&](int g) -> const float * { return sa + (g & 7) * 16 * CIN; };
+        float2 an[CIN / 8];
+        int gb = 0;
+        // A block's 16-MFMA chain starts from zero and does not read the accumulator, so the chain of block g
+        // is issued first and the sums of block g - 1 (`cp`; their outputs at `pl`, `pn` of the lane's four
+        // rows count) are added to the accumulator between its MFMAs: list read, accumulator reads, adds and
+        // stores then wait in the chain's shadow instead of in front of it.  The adds stay in block order, so
+        // an output still receives tap 0's sum first and tap 8's last.  Before the tile's first block there
+        // is nothing to add: pn = 0.
+        f32x4 cp = {0.0f, 0.0f, 0.0f, 0.0f};
+        const unsigned char *pl = &s_lo[0][4 * kq];
+        int pn = 0;
+        unsigned lo4 = 0;
+        float old[4];
+        auto add_list = [&]() { lo4 = *reinterpret_cast<const unsigned *>(pl); };
+        auto add_at = [&](int r) -> float * {  // masked: bytes past the list's end
+          return acc + (int)((lo4 >> (8 * r)) & (kOut - 1)) * kAcc;
+        };
+        auto add_read = [&]() {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) old[r] = *add_at(r);
+        };
+        auto add_write = [&]() {
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (r < pn) *add_at(r) = old[r] + cp[r];
+          // another lane of this wave may own the same accumulator element in the next tap
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+        };
+        // No ordinary load is left pending when the blocks start: the compiler would otherwise wait for it with
+        // vmcnt(0) inside the block loop, and that wait drains the next chunk's LDS-DMA loads as well.
+        __builtin_amdgcn_s_waitcnt(kWaitVm0);
+        stage_chunk(0);
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+          const int n = cn[t];
+#pragma unroll 1
+          for (int r0 = 0; r0 < n; r0 += 16, ++gb) {
+            if ((gb & 3) == 0) {  // a chunk's first block, the same for all four waves
+              __builtin_amdgcn_s_waitcnt(kWaitVm0);
+              __syncthreads();
+              stage_chunk((gb >> 2) + 1);
+              const float *ac = block_rows(gb);
+#pragma unroll
+              for (int j = 0; j < CIN / 8; ++j) an[j] = *reinterpret_cast<const float2 *>(ac + ((8 * j) ^ sx));
+            }
+            // `an` holds, or waits for, this block's rows.  The next block's are read into it behind the MFMAs
+            // that consume this one's, if they are in the stage already (the same chunk); if not, this block's
+            // are read again and the next block fills `an` itself after the chunk's barrier.
+            const float *ar = block_rows(((gb & 3) != 3 && gb + 1 < nblk) ? gb + 1 : gb);
             __builtin_amdgcn_sched_barrier(0);  // the next block's address is known before the first MFMA
             f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int j = 0; j < CIN / 8; ++j) {
               c = __builtin_amdgcn_mfma_f32_16x16x4f32(an[j].x, wr[t][j][0], c, 0, 0, 0);
               c = __builtin_amdgcn_mfma_f32_16x16x4f32(an[j].y, wr[t][j][1], c, 0, 0, 0);
-              an[j] = *reinterpret_cast<const float2 *>(ar + 8 * j);
-              __builtin_amdgcn_sched_barrier(0);  // keep each request right behind its two MFMAs
+              an[j] = *reinterpret_cast<const float2 *>(ar + ((8 * j) ^ sx));
+              if (j == 0) add_list();
+              if (j == 2) add_read();
+              if (j == 5) add_write();
+              __builtin_amdgcn_sched_barrier(0);  // keep each piece right behind its two MFMAs
             }
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (r0 + 4 * kq + r < n) *ap[r] = old[r] + c[r];
-            // another lane of this wave may own the same accumulator element in the next tap
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            // this block's four result rows of the lane
+            cp = c;
+            pl = &s_lo[t][r0 + 4 * kq];
+            pn = n - r0 - 4 * kq;
           }
         }
+        add_list();  // the tile's last block
+        add_read();
+        add_write();
       } else {
+        const float *rb = rows + (int64_t)b * P * Cin + 2 * kq;
 #pragma unroll 1
         for (int t = 0; t < 9; ++t) {
           const int n = __builtin_amdgcn_readlane(myc, t);
