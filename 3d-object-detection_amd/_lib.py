@@ -211,7 +211,7 @@ def lib():
 
 def variant_lib(name):
     """A build_variant() library as a second, independent instance in this process (its own code object, its own
-    contexts): ``Context(device, lib=variant_lib("strict"))``.  Tests only."""
+    contexts): ``Context(device, lib_=variant_lib("strict"))``.  Tests only."""
     with _lock:
         if name not in _variants:
             _variants[name] = _load(variant_path(name))

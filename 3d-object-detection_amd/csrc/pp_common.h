@@ -222,6 +222,11 @@ struct pp_ctx {
 namespace pp {
 HostPool *host_pool(pp_ctx *ctx);  // the context's pool, created on first use
 
+// PP_DROPIN_DIRECT, read once per process: the bit mask of the host drop-ins' transfers that go through mapped pinned
+// memory instead of copies (default 7, all; pp_create_pillars_f64 gives each bit a transfer, pp_make_ious_f64 asks
+// for any)
+int dropin_direct();
+
 // the device's compute units, asked once per device (the grid of the persistent kernels)
 inline int compute_units(int device) {
   static std::atomic<int> cached[64];

@@ -1980,6 +1980,25 @@ __global__ void k_targets_gt_init(u64 *best, unsigned *bestj, int64_t n, unsigne
 
 using namespace pp;
 
+// every scratch word of the target kernels is armed again by the next pp_assign_targets*_dev call (TargetKey below)
+static void disarm_targets(pp_ctx_t *ctx) { std::memset(ctx->tgt_key, 0, sizeof ctx->tgt_key); }
+
+// what an error word read back from the device means
+static int iou_flag_result(pp_ctx_t *ctx, int flag) {
+  if (flag) {
+    if (flag & kErrPosOverflow) {  // (takes precedence: the scratch has to be re-armed whatever else happened)
+      // the positive list overflowed (sized from the candidate count, so only reachable through boxes whose centre is
+      // not finite): entries were dropped; re-arm every scratch word before the next call
+      disarm_targets(ctx);
+      set_error("target assignment: more pairs above the threshold than candidate anchors (a box centre that is not finite?)");
+      return PP_ERR_VALUE;
+    }
+    set_error("IOU < 0: a box has the wrong corner winding (pillars.cpp:166-169)");
+    return PP_ERR_WINDING;
+  }
+  return PP_OK;
+}
+
 // make_ious' launch: the dense matrix (ious_dev), or -- triples != NULL -- the entries that are not zero as records
 // behind *triple_count (zeroed here)
 static int launch_make_ious(pp_ctx_t *ctx, hipStream_t stream, const double *a_corners_dev, const double *a_centers_dev,
@@ -2015,9 +2034,9 @@ static int launch_make_ious(pp_ctx_t *ctx, hipStream_t stream, const double *a_c
   const unsigned nwg = (unsigned)((A + kTgtThreads - 1) / kTgtThreads);
   TargetBatch bt{};
   bt.g_off[1] = (int)G;
-  hipLaunchKernelGGL(k_targets<true>, dim3(nwg), dim3(kTgtThreads), 0, stream, t, bt);
-  PP_HIP_TRY(hipGetLastError());
-  return PP_OK;
+  return launch_on_device(ctx, "k_targets<true>", [&] {
+    hipLaunchKernelGGL(k_targets<true>, dim3(nwg), dim3(kTgtThreads), 0, stream, t, bt);
+  });
 }
 
 extern "C" int pp_make_ious_dev(pp_ctx_t *ctx, void *stream_, const double *a_corners_dev,
@@ -2054,8 +2073,6 @@ __global__ void k_iou_tail(const unsigned *count, int *flag, unsigned *host_out)
   }
 }
 
-static int iou_flag_result(pp_ctx_t *ctx, int flag);
-
 // error flag of the last IoU / target launch on this context (synchronises)
 extern "C" int pp_iou_check(pp_ctx_t *ctx, void *stream_) {
   if (!ctx || !ctx->iou_ws.ptr) return PP_OK;
@@ -2071,19 +2088,198 @@ extern "C" int pp_iou_check(pp_ctx_t *ctx, void *stream_) {
   return iou_flag_result(ctx, flag);
 }
 
-static int iou_flag_result(pp_ctx_t *ctx, int flag) {
-  if (flag) {
-    if (flag & kErrPosOverflow) {  // (takes precedence: the scratch has to be re-armed whatever else happened)
-      // the positive list overflowed (sized from the candidate count, so only reachable through boxes whose centre is
-      // not finite): entries were dropped; re-arm every scratch word before the next call
-      std::memset(ctx->tgt_key, 0, sizeof ctx->tgt_key);
-      set_error("target assignment: more pairs above the threshold than candidate anchors (a box centre that is not finite?)");
-      return PP_ERR_VALUE;
+// pp_make_ious_f64 in phases: one call's state, handed from phase to phase
+struct IousCall {
+  pp_ctx *ctx;
+  hipStream_t stream;
+  HostPool *pool;
+  int64_t A, G;
+  const void *a_corners, *a_centers, *g_corners, *g_centers;  // the caller's (arbitrarily strided) float64 arrays ...
+  const int64_t *ac, *an, *gc, *gn, *io;                      // ... their byte strides, its [A,G] matrix's ...
+  char *dst;                                                  // ... and that matrix (out_dense: one contiguous piece)
+  bool out_dense;
+  size_t cells;       // A * G
+  unsigned cap;       // records the sparse form's list holds
+  double *d_a, *d_g;  // on the device: [rows][8] corners, then [rows][2] centres
+};
+
+static double read_f64(const void *base, int64_t off) {
+  double v;
+  std::memcpy(&v, static_cast<const char *>(base) + off, 8);
+  return v;
+}
+
+// the row split of the pool's jobs: part `part` of `parts` is rows [row_begin(part), row_begin(part + 1))
+static int64_t row_begin(int64_t A, int part, int parts) { return A * part / parts; }
+
+// one part's rows of the caller's matrix: from the dense [A][G] `src`, or (src == NULL) zeros
+static void write_rows(const IousCall &c, int part, int parts, const double *src) {
+  const int64_t G = c.G, i0 = row_begin(c.A, part, parts), i1 = row_begin(c.A, part + 1, parts);
+  const double zero = 0.0;
+  if (!c.out_dense) {
+    for (int64_t i = i0; i < i1; ++i)
+      for (int64_t j = 0; j < G; ++j) std::memcpy(c.dst + i * c.io[0] + j * c.io[1], src ? &src[i * G + j] : &zero, 8);
+  } else if (i1 > i0 && src) {
+    std::memcpy(c.dst + i0 * G * 8, src + i0 * G, (size_t)(i1 - i0) * G * 8);
+  } else if (i1 > i0) {
+    std::memset(c.dst + i0 * G * 8, 0, (size_t)(i1 - i0) * G * 8);
+  }
+}
+
+// The anchors [A][8] + [A][2] into their pinned mirror and, when they differ from what the device holds, onto the
+// device (pp_ctx::anchors_pin): the rows split across the threads, compared (as bits) while copied.
+static int ious_stage_anchors(IousCall &c) {
+  pp_ctx *ctx = c.ctx;
+  const int64_t A = c.A;
+  const size_t a_bytes = (size_t)A * 10 * 8;
+  const bool fresh = ctx->anchors_A != A || !ctx->anchors_pin.ptr || !ctx->anchors_dev.ptr;
+  if (fresh) ctx->anchors_A = -1;  // (an allocation failure below leaves nothing half-valid)
+  if (int rc = ctx->anchors_pin.ensure(a_bytes)) return rc;
+  if (int rc = ctx->anchors_dev.ensure(a_bytes)) return rc;
+  double *h_ac = static_cast<double *>(ctx->anchors_pin.ptr), *h_an = h_ac + A * 8;
+  const int64_t *ac = c.ac, *an = c.an;
+  const bool ac_dense = ac[2] == 8 && ac[1] == 16 && ac[0] == 64;
+  std::atomic<int> changed{fresh ? 1 : 0};
+  c.pool->run([&](int part, int parts) {
+    int diff = 0;
+    auto put = [&](double *slot, double v) {
+      if (std::memcmp(slot, &v, 8) != 0) {
+        *slot = v;
+        diff = 1;
+      }
+    };
+    for (int64_t i = row_begin(A, part, parts), i1 = row_begin(A, part + 1, parts); i < i1; ++i) {
+      if (ac_dense) {
+        const char *src = static_cast<const char *>(c.a_corners) + i * 64;
+        if (std::memcmp(h_ac + i * 8, src, 64) != 0) {
+          std::memcpy(h_ac + i * 8, src, 64);
+          diff = 1;
+        }
+      } else {
+        for (int k = 0; k < 4; ++k)
+          for (int col = 0; col < 2; ++col)
+            put(&h_ac[i * 8 + k * 2 + col], read_f64(c.a_corners, i * ac[0] + k * ac[1] + col * ac[2]));
+      }
+      put(&h_an[i * 2], read_f64(c.a_centers, i * an[0]));
+      put(&h_an[i * 2 + 1], read_f64(c.a_centers, i * an[0] + an[1]));
     }
-    set_error("IOU < 0: a box has the wrong corner winding (pillars.cpp:166-169)");
-    return PP_ERR_WINDING;
+    if (diff) changed.store(1, std::memory_order_relaxed);
+  });
+  c.d_a = static_cast<double *>(ctx->anchors_dev.ptr);
+  if (changed.load()) {
+    ctx->anchors_A = -1;  // (the mirror is ahead of the device until the copy is enqueued: a failure here must not leave
+                          // the next call comparing against a mirror the device never received)
+    PP_HIP_TRY(hipMemcpyAsync(c.d_a, h_ac, a_bytes, hipMemcpyHostToDevice, c.stream));
+    ctx->anchors_A = A;  // (the copy is ordered before every launch below on this stream, and the call ends synchronised)
   }
   return PP_OK;
+}
+
+// the ground truths [G][8] + [G][2] through the per-call pinned staging onto the device, behind the anchors
+static int ious_stage_boxes(IousCall &c) {
+  pp_ctx *ctx = c.ctx;
+  const int64_t G = c.G;
+  const size_t g_bytes = (size_t)G * 10 * 8;
+  if (int rc = ctx->pin_in.ensure(g_bytes)) return rc;
+  if (int rc = ctx->stage_in.ensure(g_bytes)) return rc;
+  double *h_gc = static_cast<double *>(ctx->pin_in.ptr), *h_gn = h_gc + G * 8;
+  const int64_t *gc = c.gc, *gn = c.gn;
+  for (int64_t j = 0; j < G; ++j) {
+    for (int k = 0; k < 4; ++k)
+      for (int col = 0; col < 2; ++col)
+        h_gc[j * 8 + k * 2 + col] = read_f64(c.g_corners, j * gc[0] + k * gc[1] + col * gc[2]);
+    h_gn[j * 2] = read_f64(c.g_centers, j * gn[0]);
+    h_gn[j * 2 + 1] = read_f64(c.g_centers, j * gn[0] + gn[1]);
+  }
+  c.d_g = static_cast<double *>(ctx->stage_in.ptr);
+  PP_HIP_TRY(hipMemcpyAsync(c.d_g, h_gc, g_bytes, hipMemcpyHostToDevice, c.stream));
+  return PP_OK;
+}
+
+// the sparse form's `count` records over the zeros of the caller's matrix; by copies they are fetched first
+static int ious_write_records(const IousCall &c, const IouTriple *triples_dev, unsigned count, bool direct) {
+  pp_ctx *ctx = c.ctx;
+  if (!direct) {
+    if (int rc = ctx->pin_out.ensure((size_t)count * 16)) return rc;
+    PP_HIP_TRY(hipMemcpyAsync(ctx->pin_out.ptr, triples_dev, (size_t)count * 16, hipMemcpyDeviceToHost, c.stream));
+    PP_HIP_TRY(hipStreamSynchronize(c.stream));
+  }
+  const IouTriple *tr = static_cast<const IouTriple *>(ctx->pin_out.ptr);
+  for (unsigned k = 0; k < count; ++k)
+    std::memcpy(c.dst + (int64_t)tr[k].anchor * c.io[0] + (int64_t)tr[k].box * c.io[1], &tr[k].iou, 8);
+  return PP_OK;
+}
+
+// The signature demands every entry of the caller's [A,G] matrix written (pillars.cpp:421,424) -- 40 MB at BASELINE
+// config 3, of which ~8 000 entries are not zero.  Sparse form: the device returns those entries as 16-byte records
+// (128 kB over PCIe instead of 40 MB), the pool's threads zero the caller's matrix WHILE the anchors travel and the
+// kernel runs, then the records are written over the zeros.  More records than the list holds (every anchor near
+// every box) sets *overflowed: the dense form follows, the anchors are on the device already.
+static int ious_sparse(const IousCall &c, bool *overflowed) {
+  pp_ctx *ctx = c.ctx;
+  *overflowed = false;
+  if (int rc = ctx->stage_out2.ensure(256 + (size_t)c.cap * 16)) return rc;
+  if (int rc = ctx->pin_meta.ensure(256)) return rc;
+  char *so = static_cast<char *>(ctx->stage_out2.ptr);
+  unsigned *count_dev = reinterpret_cast<unsigned *>(so);
+  IouTriple *triples_dev = reinterpret_cast<IouTriple *>(so + 256);
+  unsigned *count_host = static_cast<unsigned *>(ctx->pin_meta.ptr);
+  // PP_DROPIN_DIRECT (any bit; pp_create_pillars_f64 reads the same variable; 0 = by copies, which the transport test
+  // compares): the kernel appends its records straight into
+  // device-visible pinned memory -- each is one 16-byte store of one lane, ~8 000 of them -- and a one-thread kernel
+  // behind it leaves the count and the error word there too: the call waits for the device ONCE (before: the count's
+  // copy, the records' copy and pp_iou_check's copy, a wait each).  Lists beyond 16 MB keep the copies.
+  void *tr_map = nullptr, *cnt_map = nullptr;
+  const bool direct = dropin_direct() != 0 && (size_t)c.cap * 16 <= (16u << 20) &&
+                      ctx->pin_out.ensure((size_t)c.cap * 16) == PP_OK &&
+                      hipHostGetDevicePointer(&tr_map, ctx->pin_out.ptr, 0) == hipSuccess && tr_map &&
+                      hipHostGetDevicePointer(&cnt_map, count_host, 0) == hipSuccess && cnt_map;
+  (void)hipGetLastError();  // (a refused mapping is not an error of this call: the copies are used)
+  int rc = launch_make_ious(ctx, c.stream, c.d_a, c.d_a + c.A * 8, 2, c.A, c.d_g, c.d_g + c.G * 8, 2, c.G, nullptr,
+                            direct ? static_cast<IouTriple *>(tr_map) : triples_dev, count_dev, c.cap);
+  if (rc) return rc;
+  if (direct) {
+    rc = launch_on_device(ctx, "k_iou_tail", [&] {
+      hipLaunchKernelGGL(k_iou_tail, dim3(1), dim3(64), 0, c.stream, count_dev, static_cast<int *>(ctx->iou_ws.ptr),
+                         static_cast<unsigned *>(cnt_map));
+    });
+    if (rc) return rc;
+  } else {
+    PP_HIP_TRY(hipMemcpyAsync(count_host, count_dev, 4, hipMemcpyDeviceToHost, c.stream));
+  }
+  // ... meanwhile: zeros into the caller's matrix (rows split across the workers)
+  const std::function<void(int, int)> zero_rows = [&](int part, int parts) { write_rows(c, part, parts, nullptr); };
+  c.pool->start(zero_rows);
+  const hipError_t e_sync = hipStreamSynchronize(c.stream);
+  c.pool->wait();
+  PP_HIP_TRY(e_sync);
+  const unsigned count = count_host[0];
+  if (direct && count_host[1]) return iou_flag_result(ctx, (int)count_host[1]);  // (a wrong winding: the matrix is zeros)
+  if (count > c.cap) {
+    *overflowed = true;
+    return PP_OK;
+  }
+  if (count) {
+    rc = ious_write_records(c, triples_dev, count, direct);
+    if (rc) return rc;
+  }
+  return direct ? PP_OK : pp_iou_check(ctx, c.stream);
+}
+
+// the dense form: the whole matrix through the device's and the pinned staging
+static int ious_dense(const IousCall &c) {
+  pp_ctx *ctx = c.ctx;
+  if (int rc = ctx->stage_out2.ensure(c.cells * 8)) return rc;
+  if (int rc = ctx->pin_out.ensure(c.cells * 8)) return rc;
+  if (int rc = pp_make_ious_dev(ctx, c.stream, c.d_a, c.d_a + c.A * 8, 2, c.A, c.d_g, c.d_g + c.G * 8, 2, c.G,
+                                static_cast<double *>(ctx->stage_out2.ptr)))
+    return rc;
+  PP_HIP_TRY(hipMemcpyAsync(ctx->pin_out.ptr, ctx->stage_out2.ptr, c.cells * 8, hipMemcpyDeviceToHost, c.stream));
+  PP_HIP_TRY(hipStreamSynchronize(c.stream));
+  // every entry is written (pillars.cpp:421,424)
+  const double *src = static_cast<const double *>(ctx->pin_out.ptr);
+  c.pool->run([&](int part, int parts) { write_rows(c, part, parts, src); });
+  return pp_iou_check(ctx, c.stream);
 }
 
 extern "C" int pp_make_ious_f64(pp_ctx_t *ctx, const void *a_corners, int64_t A,
@@ -2105,176 +2301,75 @@ extern "C" int pp_make_ious_f64(pp_ctx_t *ctx, const void *a_corners, int64_t A,
     return PP_ERR_VALUE;
   }
   DeviceGuard guard(ctx->device);
-  hipStream_t stream = nullptr;
-  // pinned staging: the ground truths [G][8] + [G][2] (per call); the anchors [A][8] + [A][2] in a mirror of their own
-  const size_t a_bytes = (size_t)A * 10 * 8, g_bytes = (size_t)G * 10 * 8;
-  int rc = ctx->pin_in.ensure(g_bytes);
-  if (rc) return rc;
-  rc = ctx->stage_in.ensure(g_bytes);
-  if (rc) return rc;
-  bool fresh = ctx->anchors_A != A || !ctx->anchors_pin.ptr || !ctx->anchors_dev.ptr;
-  if (fresh) ctx->anchors_A = -1;  // (an allocation failure below leaves nothing half-valid)
-  rc = ctx->anchors_pin.ensure(a_bytes);
-  if (rc) return rc;
-  rc = ctx->anchors_dev.ensure(a_bytes);
-  if (rc) return rc;
-  // The signature demands every entry of the caller's [A,G] matrix written (pillars.cpp:421,424) -- 40 MB at BASELINE
-  // config 3, of which ~8 000 entries are not zero.  Sparse form: the device returns those entries as 16-byte records
-  // (128 kB over PCIe instead of 40 MB), the pool's threads zero the caller's matrix WHILE the anchors travel and the
-  // kernel runs, then the records are written over the zeros.  More records than the list holds (every anchor near
-  // every box): the dense form below, as before.
-  const size_t cells = (size_t)A * (size_t)G;
-  const unsigned cap = (unsigned)std::min<size_t>(std::max<size_t>(cells / 16, 1u << 16), 8u << 20);  // <= 128 MB
-  const bool sparse = A < (1ll << 32) && cells >= 4096;
-  HostPool *pool = host_pool(ctx);
-  double *h_ac = static_cast<double *>(ctx->anchors_pin.ptr), *h_an = h_ac + A * 8;
-  double *h_gc = static_cast<double *>(ctx->pin_in.ptr), *h_gn = h_gc + G * 8;
-  auto rd = [](const void *base, int64_t off) {
-    double v;
-    std::memcpy(&v, static_cast<const char *>(base) + off, 8);
-    return v;
-  };
-  const bool ac_dense = ac[2] == 8 && ac[1] == 16 && ac[0] == 64;
-  std::atomic<int> changed{fresh ? 1 : 0};
-  pool->run([&](int part, int parts) {  // the anchors' rows, split across the threads; compared (as bits) while copied
-    const int64_t i0 = A * part / parts, i1 = A * (part + 1) / parts;
-    int diff = 0;
-    auto put = [&](double *slot, double v) {
-      if (std::memcmp(slot, &v, 8) != 0) {
-        *slot = v;
-        diff = 1;
-      }
-    };
-    for (int64_t i = i0; i < i1; ++i) {
-      if (ac_dense) {
-        const char *src = static_cast<const char *>(a_corners) + i * 64;
-        if (std::memcmp(h_ac + i * 8, src, 64) != 0) {
-          std::memcpy(h_ac + i * 8, src, 64);
-          diff = 1;
-        }
-      } else {
-        for (int k = 0; k < 4; ++k)
-          for (int c = 0; c < 2; ++c) put(&h_ac[i * 8 + k * 2 + c], rd(a_corners, i * ac[0] + k * ac[1] + c * ac[2]));
-      }
-      put(&h_an[i * 2], rd(a_centers, i * an[0]));
-      put(&h_an[i * 2 + 1], rd(a_centers, i * an[0] + an[1]));
-    }
-    if (diff) changed.store(1, std::memory_order_relaxed);
-  });
-  for (int64_t j = 0; j < G; ++j) {
-    for (int k = 0; k < 4; ++k)
-      for (int c = 0; c < 2; ++c) h_gc[j * 8 + k * 2 + c] = rd(g_corners, j * gc[0] + k * gc[1] + c * gc[2]);
-    h_gn[j * 2] = rd(g_centers, j * gn[0]);
-    h_gn[j * 2 + 1] = rd(g_centers, j * gn[0] + gn[1]);
+  IousCall c{ctx, nullptr, host_pool(ctx), A, G, a_corners, a_centers, g_corners, g_centers, ac, an, gc, gn, io};
+  c.dst = static_cast<char *>(ious);
+  c.out_dense = io[1] == 8 && io[0] == G * 8;
+  c.cells = (size_t)A * (size_t)G;
+  c.cap = (unsigned)std::min<size_t>(std::max<size_t>(c.cells / 16, 1u << 16), 8u << 20);  // <= 128 MB
+  if (int rc = ious_stage_anchors(c)) return rc;
+  if (int rc = ious_stage_boxes(c)) return rc;
+  if (A < (1ll << 32) && c.cells >= 4096) {
+    bool overflowed = false;
+    const int rc = ious_sparse(c, &overflowed);
+    if (rc || !overflowed) return rc;
   }
-  double *d_a = static_cast<double *>(ctx->anchors_dev.ptr), *d_g = static_cast<double *>(ctx->stage_in.ptr);
-  if (changed.load()) {
-    ctx->anchors_A = -1;  // (the mirror is ahead of the device until the copy is enqueued: a failure here must not leave
-                          // the next call comparing against a mirror the device never received)
-    PP_HIP_TRY(hipMemcpyAsync(d_a, h_ac, a_bytes, hipMemcpyHostToDevice, stream));
-    ctx->anchors_A = A;  // (the copy is ordered before every launch below on this stream, and the call ends synchronised)
-  }
-  PP_HIP_TRY(hipMemcpyAsync(d_g, h_gc, g_bytes, hipMemcpyHostToDevice, stream));
-  char *dst = static_cast<char *>(ious);
-  const bool out_dense = io[1] == 8 && io[0] == G * 8;
-  if (sparse) {
-    rc = ctx->stage_out2.ensure(256 + (size_t)cap * 16);
-    if (rc) return rc;
-    rc = ctx->pin_meta.ensure(256);
-    if (rc) return rc;
-    char *so = static_cast<char *>(ctx->stage_out2.ptr);
-    unsigned *count_dev = reinterpret_cast<unsigned *>(so);
-    IouTriple *triples_dev = reinterpret_cast<IouTriple *>(so + 256);
-    unsigned *count_host = static_cast<unsigned *>(ctx->pin_meta.ptr);
-    // PP_DROPIN_DIRECT (any bit; pp_create_pillars_f64 reads the same variable; 0 = by copies, which the transport test
-    // compares): the kernel appends its records straight into
-    // device-visible pinned memory -- each is one 16-byte store of one lane, ~8 000 of them -- and a one-thread kernel
-    // behind it leaves the count and the error word there too: the call waits for the device ONCE (before: the count's
-    // copy, the records' copy and pp_iou_check's copy, a wait each).  Lists beyond 16 MB keep the copies.
-    static const bool k_direct = [] { const char *e = getenv("PP_DROPIN_DIRECT"); return e ? atoi(e) != 0 : true; }();
-    void *tr_map = nullptr, *cnt_map = nullptr;
-    bool direct = k_direct && (size_t)cap * 16 <= (16u << 20) && ctx->pin_out.ensure((size_t)cap * 16) == PP_OK &&
-                  hipHostGetDevicePointer(&tr_map, ctx->pin_out.ptr, 0) == hipSuccess && tr_map &&
-                  hipHostGetDevicePointer(&cnt_map, count_host, 0) == hipSuccess && cnt_map;
-    (void)hipGetLastError();  // (a refused mapping is not an error of this call: the copies are used)
-    rc = launch_make_ious(ctx, stream, d_a, d_a + A * 8, 2, A, d_g, d_g + G * 8, 2, G, nullptr,
-                          direct ? static_cast<IouTriple *>(tr_map) : triples_dev, count_dev, cap);
-    if (rc) return rc;
-    if (direct) {
-      hipLaunchKernelGGL(k_iou_tail, dim3(1), dim3(64), 0, stream, count_dev, static_cast<int *>(ctx->iou_ws.ptr),
-                         static_cast<unsigned *>(cnt_map));
-      PP_HIP_TRY(hipGetLastError());
-    } else {
-      PP_HIP_TRY(hipMemcpyAsync(count_host, count_dev, 4, hipMemcpyDeviceToHost, stream));
-    }
-    // ... meanwhile: zeros into the caller's matrix (rows split across the workers)
-    const std::function<void(int, int)> zero_rows = [&](int part, int parts) {
-      const int64_t i0 = A * part / parts, i1 = A * (part + 1) / parts;
-      if (out_dense) {
-        if (i1 > i0) std::memset(dst + i0 * G * 8, 0, (size_t)(i1 - i0) * G * 8);
-      } else {
-        const double zero = 0.0;
-        for (int64_t i = i0; i < i1; ++i)
-          for (int64_t j = 0; j < G; ++j) std::memcpy(dst + i * io[0] + j * io[1], &zero, 8);
-      }
-    };
-    pool->start(zero_rows);
-    const hipError_t e_sync = hipStreamSynchronize(stream);
-    pool->wait();
-    PP_HIP_TRY(e_sync);
-    const unsigned count = count_host[0];
-    if (direct && count_host[1]) return iou_flag_result(ctx, (int)count_host[1]);  // (a wrong winding: the matrix is zeros)
-    if (count <= cap) {
-      if (count) {
-        if (!direct) {
-          rc = ctx->pin_out.ensure((size_t)count * 16);
-          if (rc) return rc;
-          PP_HIP_TRY(hipMemcpyAsync(ctx->pin_out.ptr, triples_dev, (size_t)count * 16, hipMemcpyDeviceToHost, stream));
-          PP_HIP_TRY(hipStreamSynchronize(stream));
-        }
-        const IouTriple *tr = static_cast<const IouTriple *>(ctx->pin_out.ptr);
-        for (unsigned k = 0; k < count; ++k)
-          std::memcpy(dst + (int64_t)tr[k].anchor * io[0] + (int64_t)tr[k].box * io[1], &tr[k].iou, 8);
-      }
-      return direct ? PP_OK : pp_iou_check(ctx, stream);
-    }
-    // the list overflowed: the anchors are on the device already, take the dense form
-  }
-  rc = ctx->stage_out2.ensure(cells * 8);
-  if (rc) return rc;
-  rc = ctx->pin_out.ensure(cells * 8);
-  if (rc) return rc;
-  rc = pp_make_ious_dev(ctx, stream, d_a, d_a + A * 8, 2, A, d_g, d_g + G * 8, 2, G,
-                        static_cast<double *>(ctx->stage_out2.ptr));
-  if (rc) return rc;
-  PP_HIP_TRY(hipMemcpyAsync(ctx->pin_out.ptr, ctx->stage_out2.ptr, cells * 8, hipMemcpyDeviceToHost, stream));
-  PP_HIP_TRY(hipStreamSynchronize(stream));
-  // every entry is written (pillars.cpp:421,424)
-  const double *src = static_cast<const double *>(ctx->pin_out.ptr);
-  pool->run([&](int part, int parts) {
-    const int64_t i0 = A * part / parts, i1 = A * (part + 1) / parts;
-    if (out_dense) {
-      if (i1 > i0) std::memcpy(dst + i0 * G * 8, src + i0 * G, (size_t)(i1 - i0) * G * 8);
-    } else {
-      for (int64_t i = i0; i < i1; ++i)
-        for (int64_t j = 0; j < G; ++j) std::memcpy(dst + i * io[0] + j * io[1], &src[i * G + j], 8);
-    }
-  });
-  return pp_iou_check(ctx, stream);
+  return ious_dense(c);
 }
 
+// pp_assign_targets*_dev: validate, plan, lay out, bind, launch.  The anchors: arrays of A rows, or a grid ...
 struct AnchorSource {
+  int64_t A = 0;
   const double *corners = nullptr, *centers = nullptr, *wlh = nullptr, *yaw = nullptr;
   int grid = 0, fm_w = 0, fm_h = 0, per_cell = 0;
   double fm_scale = 1.0;
   const double *types = nullptr;
 };
+// ... whose A is fm_h * fm_w * per_cell, known once check_targets has passed
+static AnchorSource anchor_grid(int fm_height, int fm_width, double fm_scale, int per_cell, const double *types_dev) {
+  return {0, nullptr, nullptr, nullptr, nullptr, 1, fm_width, fm_height, per_cell, fm_scale, types_dev};
+}
 
-static int assign_targets_impl(pp_ctx_t *ctx, void *stream_, int batch, const int32_t *g_counts,
-                               int64_t A, const AnchorSource &an, const double *g_corners,
-                               const double *g_centers_img, const double *g_centers, const double *g_wlh,
-                               const double *g_yaw, const int32_t *g_class, const pp_target_params_t *prm,
-                               float *cls_targets, float *reg_targets) {
+// all samples' ground truths, concatenated in sample order
+struct GroundTruths {
+  const double *corners, *centers_img, *centers, *wlh, *yaw;
+  const int32_t *cls;
+};
+
+// what the checked arguments say about the call's size: anchors, samples, all samples' boxes and the most one has
+struct TargetShape {
+  int64_t A;
+  int batch;
+  int64_t g_total;
+  int g_max;
+  TargetBatch bt;
+};
+
+// Every argument check of the four entry points, in the order and with the texts their callers have always met.
+// `single`: the name of a single-sample entry point, whose count G is refused under that name ("bad sizes (G=-1)",
+// where the batch forms name the sample); NULL: the batch forms' g_counts[batch].
+static int check_targets(const pp_ctx_t *ctx, const char *single, int64_t G, int batch, const int32_t *g_counts,
+                         const AnchorSource &an, const GroundTruths &g, const pp_target_params_t *prm,
+                         const float *cls_targets, const float *reg_targets, TargetShape *s) {
+  if (an.grid) {
+    if (an.fm_h < 1 || an.fm_w < 1 || an.per_cell < 1 || an.per_cell > 1024 || !(an.fm_scale > 0.0) || !an.types ||
+        (int64_t)an.fm_h * an.fm_w * an.per_cell > 65535ll * kTgtThreads) {
+      set_error("pp_assign_targets_grid*_dev: bad anchor grid (%dx%d, %d per cell, scale %g)", an.fm_h, an.fm_w,
+                an.per_cell, an.fm_scale);
+      return PP_ERR_VALUE;
+    }
+  } else if (!an.corners || !an.centers || !an.wlh || !an.yaw) {
+    set_error("pp_assign_targets*_dev: NULL anchor array");
+    return PP_ERR_VALUE;
+  }
+  int32_t g1 = 0;
+  if (single) {
+    if (G < 0 || G > 65535) {
+      set_error("%s: bad sizes (G=%lld)", single, (long long)G);
+      return PP_ERR_VALUE;
+    }
+    g1 = (int32_t)G;
+    g_counts = &g1;
+  }
   if (!ctx || !prm || !g_counts) {
     set_error("pp_assign_targets*_dev: NULL argument");
     return PP_ERR_VALUE;
@@ -2283,208 +2378,269 @@ static int assign_targets_impl(pp_ctx_t *ctx, void *stream_, int batch, const in
     set_error("pp_assign_targets*_dev: batch %d outside 1..%d", batch, PP_MAX_BATCH);
     return PP_ERR_VALUE;
   }
-  TargetBatch bt{};
-  int64_t g_total = 0;
+  s->batch = batch;
+  s->g_total = 0;
+  s->g_max = 0;
   for (int b = 0; b < batch; ++b) {
     if (g_counts[b] < 0 || g_counts[b] > 65535) {
       set_error("pp_assign_targets*_dev: sample %d has %d ground truths (0..65535)", b, (int)g_counts[b]);
       return PP_ERR_VALUE;
     }
-    g_total += g_counts[b];
-    bt.g_off[b + 1] = (int)g_total;
+    s->g_total += g_counts[b];
+    s->g_max = std::max<int>(s->g_max, g_counts[b]);
+    s->bt.g_off[b + 1] = (int)s->g_total;
   }
+  const int64_t A = s->A = an.grid ? (int64_t)an.fm_h * an.fm_w * an.per_cell : an.A;
   if (A < 1 || A > 65535ll * kTgtThreads || prm->num_classes < 1 || prm->num_classes > 1024 ||
       A * std::max(prm->num_classes, 9) * 4 > INT_MAX) {  // grid.y = tiles of 256; 32-bit offsets into one sample's rows
     set_error("pp_assign_targets*_dev: bad sizes (A=%lld classes=%d)", (long long)A, prm->num_classes);
     return PP_ERR_VALUE;
   }
   if (!cls_targets || !reg_targets ||
-      (g_total > 0 && (!g_corners || !g_centers_img || !g_centers || !g_wlh || !g_yaw || !g_class))) {
+      (s->g_total > 0 && (!g.corners || !g.centers_img || !g.centers || !g.wlh || !g.yaw || !g.cls))) {
     set_error("pp_assign_targets*_dev: NULL array");
     return PP_ERR_VALUE;
   }
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  DeviceGuard guard(ctx->device);
-  // Which form: anchors on the fly -> the box-centric kernel (k_targets_gt); anchor arrays -> k_targets.
-  bool boxes_form = an.grid && an.per_cell <= kLdsTypes;  // (the box-centric kernel keeps the type table in LDS)
-  // scratch: [0,8192) error flag + every sample's {list counter, ticket, pair counter} | col_max[Gcap] |
-  // col_win[Gcap] | first-level tickets | cand[cand_per_gt * Gcap] | pos[pos_per_gt * Gcap] | best, bestj
-  // [batch * A]; sample b owns the rows [g_off[b], g_off[b+1]) of each (Gcap = all samples' G)
-  const size_t gcap = (size_t)std::max<int64_t>(g_total, 1);
+  return PP_OK;
+}
+
+// How a call is cut into workgroups and what each may append: everything the scratch layout and the launch depend on.
+struct TargetPlan {
+  bool boxes_form;     // k_targets_gt (anchors on the fly, box-centric); else k_targets<false> (anchor-centric)
+  size_t splits;       // PAIR workgroups per ground truth
+  size_t cand_per_wg;  // candidate anchors per PAIR workgroup
+  size_t pos_per_gt;   // pairs above the threshold the list holds per ground truth
+  size_t cand_per_gt;  // column-list entries reserved per ground truth
+  size_t units;        // workgroups per sample
+  int ticket_shift;    // first-level ticket groups of 1 << ticket_shift workgroups ...
+  size_t ngrp;         // ... this many per sample
+};
+
+// Pure arithmetic: no HIP call, no context.
+static TargetPlan plan_targets(int64_t A, int batch, int64_t g_total, int g_max, const AnchorSource &an) {
   const size_t nwg = (size_t)((A + kTgtThreads - 1) / kTgtThreads);
-  int g_max = 0;
-  for (int b = 0; b < batch; ++b) g_max = std::max<int>(g_max, g_counts[b]);
-  // box-centric: candidate cells per axis <= floor(20 * fm_scale) + 3 (the +-10 gate, one cell generous either side)
-  // ... kCandPerWg of them per PAIR workgroup, fewer when the launch is small: 32 candidates leave ~22 pairs, ONE
-  // clip round, where 64 leave ~45 and take two -- worth it as long as the workgroups still fit the chip at once
-  // (one sample: 15.1 -> 14.2 us; four samples: 22.6 us with 64 against 25.3 with 32)
-  size_t splits = 1, cand_per_wg = kCandPerWg;
-  if (boxes_form) {
+  // Which form: anchors on the fly -> the box-centric kernel (k_targets_gt); anchor arrays -> k_targets.
+  TargetPlan p{};  // the anchor-centric form, also the fall-back of a grid the box-centric one cannot take
+  p.boxes_form = false;
+  p.splits = 1;
+  p.cand_per_wg = kCandPerWg;
+  p.pos_per_gt = 0;
+  if (an.grid && an.per_cell <= kLdsTypes) {  // (the box-centric kernel keeps the type table in LDS)
+    // box-centric: candidate cells per axis <= floor(20 * fm_scale) + 3 (the +-10 gate, one cell generous either side)
+    // ... kCandPerWg of them per PAIR workgroup, fewer when the launch is small: 32 candidates leave ~22 pairs, ONE
+    // clip round, where 64 leave ~45 and take two -- worth it as long as the workgroups still fit the chip at once
+    // (one sample: 15.1 -> 14.2 us; four samples: 22.6 us with 64 against 25.3 with 32)
     const double per_axis = std::min(std::floor(20.0 * an.fm_scale) + 3.0, 32768.0);
     const double cand = per_axis * per_axis * an.per_cell;
+    size_t cand_per_wg = kCandPerWg;
     for (size_t c : {(size_t)32, (size_t)40, (size_t)48, (size_t)64}) {
       cand_per_wg = c;
       if ((double)g_total * std::ceil(cand / (double)c) + (double)batch * kZeroWgs <= 900.0) break;
     }
-    splits = (size_t)std::min(std::max(std::ceil(cand / (double)cand_per_wg), 1.0), 64.0);
+    const size_t splits = (size_t)std::min(std::max(std::ceil(cand / (double)cand_per_wg), 1.0), 64.0);
+    // positives per box: at most one entry per candidate.  The PAIR loop strides over ALL of a box's candidates, also
+    // when `splits` was clamped to 64 workgroups (fm_scale ~1 with six anchors per cell: 3174 candidates against
+    // 64 x 32), so the list is sized from the candidate count itself, not from splits x cand_per_wg
+    const double cand_on_map = std::min(cand, (double)A);
+    const size_t pos_per_gt = std::max(splits * cand_per_wg, (size_t)std::ceil(cand_on_map));
     // grid.y holds the zero-fill workgroups and every box's PAIR workgroups: a sample with more boxes than that
     // (eleven thousand at C3's six workgroups per box) goes through the anchor-centric kernel, which walks any
     // number of boxes in chunks
-    if ((size_t)kZeroWgs + (size_t)g_max * splits > 65535) {
-      boxes_form = false;
-      splits = 1;
-      cand_per_wg = kCandPerWg;
-    }
-  }
-  // positives per box: at most one entry per candidate.  The PAIR loop strides over ALL of a box's candidates, also
-  // when `splits` was clamped to 64 workgroups (fm_scale ~1 with six anchors per cell: 3174 candidates against
-  // 64 x 32), so the list is sized from the candidate count itself, not from splits x cand_per_wg
-  size_t pos_per_gt = 0;
-  if (boxes_form) {
-    const double per_axis = std::min(std::floor(20.0 * an.fm_scale) + 3.0, 32768.0);
-    const double cand = std::min(per_axis * per_axis * an.per_cell, (double)A);
-    pos_per_gt = std::max(splits * cand_per_wg, (size_t)std::ceil(cand));
+    const bool grid_fits = (size_t)kZeroWgs + (size_t)g_max * splits <= 65535;
     // the PAIR role addresses a sample's pair entries through one buffer resource with 32-bit byte offsets
-    if ((double)g_max * (double)pos_per_gt * sizeof(PosRow) >= 2147483648.0) {
-      boxes_form = false;
-      splits = 1;
-      cand_per_wg = kCandPerWg;
-      pos_per_gt = 0;
+    const bool rows_fit = (double)g_max * (double)pos_per_gt * sizeof(PosRow) < 2147483648.0;
+    if (grid_fits && rows_fit) {
+      p.boxes_form = true;
+      p.splits = splits;
+      p.cand_per_wg = cand_per_wg;
+      p.pos_per_gt = pos_per_gt;
     }
   }
-  const size_t units = boxes_form ? (size_t)kZeroWgs + (size_t)g_max * splits : nwg;  // workgroups per sample
-  if (units > 65535) {
-    set_error("pp_assign_targets*_dev: %zu workgroups per sample (limit 65535)", units);
+  p.units = p.boxes_form ? (size_t)kZeroWgs + (size_t)g_max * p.splits : nwg;
+  p.cand_per_gt = p.boxes_form ? p.splits : nwg;
+  // first-level tickets: groups of ~sqrt(workgroups) (a power of two), one 64-byte line per group and sample
+  p.ticket_shift = 0;
+  while (((size_t)1 << (2 * p.ticket_shift)) < p.units) ++p.ticket_shift;
+  p.ngrp = ((p.units - 1) >> p.ticket_shift) + 1;
+  return p;
+}
+
+// scratch: [0,8192) error flag + every sample's {list counter, ticket, pair counter} | col_max[Gcap] |
+// col_win[Gcap] | first-level tickets | cand[cand_per_gt * Gcap] | pos[pos_per_gt * Gcap] | best, bestj
+// [batch * A]; sample b owns the rows [g_off[b], g_off[b+1]) of each (Gcap = all samples' G)
+constexpr size_t kCounterBlock = 8192;                // the fixed block in front of the regions
+constexpr size_t kOffCandCount = 256;                 // sample b's words: + b * kCounterStride * 4
+constexpr size_t kOffTicket = kOffCandCount + 64;     // (two words: k_targets_gt counts in 64 bits)
+constexpr size_t kOffPosCount = kOffCandCount + 96;
+static_assert(kOffCandCount + PP_MAX_BATCH * kCounterStride * 4 <= kCounterBlock, "counter block");
+
+struct ScratchRegion {
+  size_t off, bytes;
+};
+struct TargetLayout {
+  int64_t A;  // what it was laid out for
+  size_t gcap;
+  int batch;
+  size_t n_ticket1, n_best;  // first-level ticket words; entries of best / bestj
+  ScratchRegion cmax, cwin, tk1, cand, pos, prow, crow, best, bestj;
+  size_t need;
+};
+
+// Offsets of every region and the bytes the workspace needs.  The only place that knows which regions the
+// anchor-centric form leaves empty: cand_rows, best and bestj by `box_only`, pos and pos_rows by pos_per_gt == 0.
+static TargetLayout layout_targets(const TargetPlan &p, size_t gcap, int batch, int64_t A) {
+  TargetLayout l{A, gcap, batch};
+  const size_t box_only = p.boxes_form ? 1 : 0;
+  l.n_ticket1 = (size_t)PP_MAX_BATCH * p.ngrp * kTicketPad;
+  l.n_best = box_only * (size_t)batch * (size_t)A;
+  size_t end = kCounterBlock;
+  auto place = [&end](size_t bytes, size_t align) {
+    const ScratchRegion r{(end + align - 1) / align * align, bytes};
+    end = r.off + bytes;
+    return r;
+  };
+  l.cmax = place(gcap * 8, 256);
+  l.cwin = place(gcap * 8, 1);
+  l.tk1 = place(l.n_ticket1 * 4, 256);
+  l.cand = place(p.cand_per_gt * gcap * sizeof(ColEntry), 256);
+  l.pos = place(p.pos_per_gt * gcap * sizeof(PosKey), 256);
+  l.prow = place(p.pos_per_gt * gcap * sizeof(PosRow), 256);
+  l.crow = place(box_only * p.cand_per_gt * gcap * kRowPitch * 4, 256);
+  l.best = place(l.n_best * 8, 256);
+  l.bestj = place(l.n_best * 4, 1);
+  l.need = end;
+  return l;
+}
+
+template <class T>
+static T *scratch_at(char *ws, size_t off) {
+  return reinterpret_cast<T *>(ws + off);
+}
+template <class T>  // a region of the box-centric form alone: NULL where the layout left it empty
+static T *box_region(char *ws, ScratchRegion r) {
+  return r.bytes ? scratch_at<T>(ws, r.off) : nullptr;
+}
+
+// the scratch and plan fields of the kernels' arguments
+static void bind_scratch(char *ws, const TargetLayout &l, const TargetPlan &p, TargetArgs *t) {
+  t->errflag = scratch_at<int>(ws, 0);
+  t->cand_count = scratch_at<unsigned>(ws, kOffCandCount);
+  t->ticket = scratch_at<unsigned>(ws, kOffTicket);
+  t->pos_count = scratch_at<unsigned>(ws, kOffPosCount);
+  t->col_max = scratch_at<u64>(ws, l.cmax.off);
+  t->col_win = scratch_at<u64>(ws, l.cwin.off);
+  t->cand = scratch_at<ColEntry>(ws, l.cand.off);
+  t->cand_per_gt = (unsigned)p.cand_per_gt;
+  t->ticket1 = scratch_at<unsigned>(ws, l.tk1.off);
+  t->ticket_shift = p.ticket_shift;
+  t->ticket_groups = (int)p.ngrp;
+  t->gt_splits = (int)p.splits;
+  t->cand_per_wg = (int)p.cand_per_wg;
+  t->pos = scratch_at<PosKey>(ws, l.pos.off);
+  t->pos_rows = box_region<PosRow>(ws, l.prow);
+  t->pos_per_gt = (unsigned)p.pos_per_gt;
+  t->cand_rows = box_region<float>(ws, l.crow);
+  t->best = box_region<u64>(ws, l.best);
+  t->bestj = box_region<unsigned>(ws, l.bestj);
+}
+
+// The scratch words are re-armed by every sample's tail at the end of every call; only a
+// fresh / regrown / re-shaped workspace needs the init.
+// ... identified by every value that moves a scratch word (no packed bit fields: two assigners with different grids
+// on one context must never look alike).  The image of pp_ctx::tgt_key: nine words of one type, so no padding byte
+// takes part in the comparison.
+struct TargetKey {
+  unsigned long long v[9];
+};
+static_assert(sizeof(TargetKey) == sizeof(pp_ctx::tgt_key), "re-arm key");
+static TargetKey target_key(const TargetPlan &p, const TargetLayout &l) {
+  return {{(unsigned long long)l.A, (unsigned long long)l.gcap, (unsigned long long)l.batch,
+           (unsigned long long)p.units, p.boxes_form ? 2ull : 1ull, (unsigned long long)p.splits,
+           (unsigned long long)p.cand_per_wg, (unsigned long long)l.best.off, (unsigned long long)p.ngrp}};
+}
+
+// the inputs, parameters and outputs of the kernels' arguments
+static void bind_call(const TargetShape &s, const AnchorSource &an, const GroundTruths &g,
+                      const pp_target_params_t *prm, float *cls_targets, float *reg_targets, TargetArgs *t) {
+  t->A = s.A;
+  t->G = 0;  // per sample: sample_view
+  t->a_corners = an.corners;
+  t->a_centers = an.centers;
+  t->a_wlh = an.wlh;
+  t->a_yaw = an.yaw;
+  t->a_center_cols = 3;
+  t->g_center_cols = 3;
+  t->ious = nullptr;
+  t->grid = an.grid;
+  t->fm_w = an.fm_w;
+  t->fm_h = an.fm_h;
+  t->per_cell = an.per_cell;
+  t->fm_scale = an.fm_scale;
+  int e2 = 0;
+  t->inv_scale = (an.grid && std::frexp(an.fm_scale, &e2) == 0.5) ? 1.0 / an.fm_scale : 0.0;
+  t->types = an.types;
+  t->g_corners = g.corners;
+  t->g_centers_img = g.centers_img;
+  t->g_centers = g.centers;
+  t->g_wlh = g.wlh;
+  t->g_yaw = g.yaw;
+  t->g_class = g.cls;
+  t->pos_thresh = prm->pos_thresh;
+  t->canvas_height = prm->canvas_height;
+  t->num_classes = prm->num_classes;
+  t->cls_targets = cls_targets;
+  t->reg_targets = reg_targets;
+}
+
+// One launch step: `arm` -- the init kernels first -- then the plan's target kernel.
+static int launch_targets(const pp_ctx_t *ctx, hipStream_t stream, const TargetPlan &p, const TargetLayout &l, bool arm,
+                          const TargetArgs &t, const TargetBatch &bt) {
+  return launch_on_device(ctx, p.boxes_form ? "k_targets_gt" : "k_targets", [&] {
+    if (arm) {
+      const unsigned gb =
+          (unsigned)((std::max<size_t>(std::max<size_t>(l.gcap, PP_MAX_BATCH), l.n_ticket1) + 255) / 256);
+      hipLaunchKernelGGL(k_targets_init, dim3(gb), dim3(256), 0, stream, t.col_max, t.col_win, (int)l.gcap, t.errflag,
+                         t.cand_count, t.ticket, t.ticket1, (int)l.n_ticket1);
+      if (p.boxes_form)
+        hipLaunchKernelGGL(k_targets_gt_init, dim3((unsigned)((std::max<size_t>(l.n_best, PP_MAX_BATCH) + 255) / 256)),
+                           dim3(256), 0, stream, t.best, t.bestj, (int64_t)l.n_best, t.pos_count);
+    }
+    const dim3 grid((unsigned)l.batch, (unsigned)p.units);
+    if (p.boxes_form)
+      hipLaunchKernelGGL(k_targets_gt, grid, dim3(kTgtThreads), 0, stream, t, bt);
+    else
+      hipLaunchKernelGGL(k_targets<false>, grid, dim3(kTgtThreads), 0, stream, t, bt);
+  });
+}
+
+// the four entry points' one path (single / G and g_counts: see check_targets)
+static int assign_targets(pp_ctx_t *ctx, void *stream_, const char *single, int64_t G, int batch,
+                          const int32_t *g_counts, const AnchorSource &an, const GroundTruths &g,
+                          const pp_target_params_t *prm, float *cls_targets, float *reg_targets) {
+  TargetShape s{};
+  if (int rc = check_targets(ctx, single, G, batch, g_counts, an, g, prm, cls_targets, reg_targets, &s)) return rc;
+  const TargetPlan p = plan_targets(s.A, s.batch, s.g_total, s.g_max, an);
+  if (p.units > 65535) {
+    set_error("pp_assign_targets*_dev: %zu workgroups per sample (limit 65535)", p.units);
     return PP_ERR_VALUE;
   }
-  const size_t cand_per_gt = boxes_form ? splits : nwg;
-  const size_t off_cmax = 8192, off_cwin = off_cmax + gcap * 8;
-  // first-level tickets: groups of ~sqrt(workgroups) (a power of two), one 64-byte line per group and sample
-  int ticket_shift = 0;
-  while (((size_t)1 << (2 * ticket_shift)) < units) ++ticket_shift;
-  const size_t ngrp = ((units - 1) >> ticket_shift) + 1;
-  const size_t n_ticket1 = (size_t)PP_MAX_BATCH * ngrp * kTicketPad;
-  const size_t off_tk1 = (off_cwin + gcap * 8 + 255) / 256 * 256;
-  const size_t off_cand = (off_tk1 + n_ticket1 * 4 + 255) / 256 * 256;
-  const size_t off_pos = (off_cand + cand_per_gt * gcap * sizeof(ColEntry) + 255) / 256 * 256;
-  const size_t off_prow = (off_pos + pos_per_gt * gcap * sizeof(PosKey) + 255) / 256 * 256;
-  const size_t off_crow = (off_prow + pos_per_gt * gcap * sizeof(PosRow) + 255) / 256 * 256;
-  const size_t off_best = (off_crow + (boxes_form ? cand_per_gt * gcap * kRowPitch * 4 : 0) + 255) / 256 * 256;
-  const size_t n_best = boxes_form ? (size_t)batch * (size_t)A : 0;
-  const size_t off_bestj = off_best + n_best * 8;
-  const size_t need = off_bestj + n_best * 4;
-  static_assert(256 + PP_MAX_BATCH * kCounterStride * 4 <= 8192, "counter block");
+  const TargetLayout l = layout_targets(p, (size_t)std::max<int64_t>(s.g_total, 1), s.batch, s.A);
   bool grew = false;
-  int rc = ctx->iou_ws.ensure(need, &grew);
-  if (rc) return rc;
-  char *ws = static_cast<char *>(ctx->iou_ws.ptr);
+  {
+    DeviceGuard guard(ctx->device);  // (the allocation's)
+    if (int rc = ctx->iou_ws.ensure(l.need, &grew)) return rc;
+  }
   TargetArgs t;
   std::memset(&t, 0, sizeof t);
-  t.A = A;
-  t.G = 0;  // per sample: sample_view
-  t.a_corners = an.corners;
-  t.a_centers = an.centers;
-  t.a_wlh = an.wlh;
-  t.a_yaw = an.yaw;
-  t.a_center_cols = 3;
-  t.g_center_cols = 3;
-  t.ious = nullptr;
-  t.grid = an.grid;
-  t.fm_w = an.fm_w;
-  t.fm_h = an.fm_h;
-  t.per_cell = an.per_cell;
-  t.fm_scale = an.fm_scale;
-  {
-    int e2 = 0;
-    t.inv_scale = (an.grid && std::frexp(an.fm_scale, &e2) == 0.5) ? 1.0 / an.fm_scale : 0.0;
+  bind_call(s, an, g, prm, cls_targets, reg_targets, &t);
+  bind_scratch(static_cast<char *>(ctx->iou_ws.ptr), l, p, &t);
+  const TargetKey key = target_key(p, l);
+  const bool arm = grew || std::memcmp(ctx->tgt_key, key.v, sizeof key.v) != 0;
+  if (int rc = launch_targets(ctx, static_cast<hipStream_t>(stream_), p, l, arm, t, s.bt)) {
+    disarm_targets(ctx);  // counters in an unknown state: re-arm on the next call
+    return rc;
   }
-  t.types = an.types;
-  t.g_corners = g_corners;
-  t.g_centers_img = g_centers_img;
-  t.g_centers = g_centers;
-  t.g_wlh = g_wlh;
-  t.g_yaw = g_yaw;
-  t.g_class = g_class;
-  t.pos_thresh = prm->pos_thresh;
-  t.canvas_height = prm->canvas_height;
-  t.num_classes = prm->num_classes;
-  t.errflag = reinterpret_cast<int *>(ws);
-  t.cand_count = reinterpret_cast<unsigned *>(ws + 256);
-  t.ticket = reinterpret_cast<unsigned *>(ws + 256 + 64);
-  t.pos_count = reinterpret_cast<unsigned *>(ws + 256 + 96);
-  t.col_max = reinterpret_cast<u64 *>(ws + off_cmax);
-  t.col_win = reinterpret_cast<u64 *>(ws + off_cwin);
-  t.cand = reinterpret_cast<ColEntry *>(ws + off_cand);
-  t.cand_per_gt = (unsigned)cand_per_gt;
-  t.ticket1 = reinterpret_cast<unsigned *>(ws + off_tk1);
-  t.ticket_shift = ticket_shift;
-  t.ticket_groups = (int)ngrp;
-  t.gt_splits = (int)splits;
-  t.cand_per_wg = (int)cand_per_wg;
-  t.pos = reinterpret_cast<PosKey *>(ws + off_pos);
-  t.pos_rows = boxes_form ? reinterpret_cast<PosRow *>(ws + off_prow) : nullptr;
-  t.pos_per_gt = (unsigned)pos_per_gt;
-  t.cand_rows = boxes_form ? reinterpret_cast<float *>(ws + off_crow) : nullptr;
-  t.best = boxes_form ? reinterpret_cast<u64 *>(ws + off_best) : nullptr;
-  t.bestj = boxes_form ? reinterpret_cast<unsigned *>(ws + off_bestj) : nullptr;
-  t.cls_targets = cls_targets;
-  t.reg_targets = reg_targets;
-  // The scratch words are re-armed by every sample's tail at the end of every call; only a
-  // fresh / regrown / re-shaped workspace needs the init.
-  // ... identified by every value that moves a scratch word (no packed bit fields: two assigners with different grids
-  // on one context must never look alike)
-  const unsigned long long key[9] = {(unsigned long long)A, (unsigned long long)gcap, (unsigned long long)batch,
-                                     (unsigned long long)units, boxes_form ? 2ull : 1ull, (unsigned long long)splits,
-                                     (unsigned long long)cand_per_wg, (unsigned long long)off_best,
-                                     (unsigned long long)ngrp};
-  if (grew || std::memcmp(ctx->tgt_key, key, sizeof key) != 0) {
-    const unsigned gb = (unsigned)((std::max<size_t>(std::max<size_t>(gcap, PP_MAX_BATCH), n_ticket1) + 255) / 256);
-    hipLaunchKernelGGL(k_targets_init, dim3(gb), dim3(256), 0, stream, t.col_max, t.col_win,
-                       (int)gcap, t.errflag, t.cand_count, t.ticket, t.ticket1, (int)n_ticket1);
-    if (boxes_form)
-      hipLaunchKernelGGL(k_targets_gt_init, dim3((unsigned)((std::max<size_t>(n_best, PP_MAX_BATCH) + 255) / 256)),
-                         dim3(256), 0, stream, t.best, t.bestj, (int64_t)n_best, t.pos_count);
-    std::memcpy(ctx->tgt_key, key, sizeof key);
-  }
-  if (boxes_form)
-    hipLaunchKernelGGL(k_targets_gt, dim3((unsigned)batch, (unsigned)units), dim3(kTgtThreads), 0, stream, t, bt);
-  else
-    hipLaunchKernelGGL(k_targets<false>, dim3((unsigned)batch, (unsigned)nwg), dim3(kTgtThreads), 0, stream, t, bt);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) {
-    std::memset(ctx->tgt_key, 0, sizeof ctx->tgt_key);  // counters in an unknown state: re-arm on the next call
-    set_error("k_targets launch failed: %s", hipGetErrorString(e));
-    return PP_ERR_HIP;
-  }
-  return PP_OK;
-}
-
-static int check_anchor_arrays(const double *a_corners, const double *a_centers, const double *a_wlh,
-                               const double *a_yaw, AnchorSource *an) {
-  if (!a_corners || !a_centers || !a_wlh || !a_yaw) {
-    set_error("pp_assign_targets*_dev: NULL anchor array");
-    return PP_ERR_VALUE;
-  }
-  an->corners = a_corners;
-  an->centers = a_centers;
-  an->wlh = a_wlh;
-  an->yaw = a_yaw;
-  return PP_OK;
-}
-
-static int check_anchor_grid(int fm_height, int fm_width, double fm_scale, int per_cell,
-                             const double *anchor_types_dev, AnchorSource *an) {
-  if (fm_height < 1 || fm_width < 1 || per_cell < 1 || per_cell > 1024 || !(fm_scale > 0.0) ||
-      !anchor_types_dev || (int64_t)fm_height * fm_width * per_cell > 65535ll * kTgtThreads) {
-    set_error("pp_assign_targets_grid*_dev: bad anchor grid (%dx%d, %d per cell, scale %g)",
-              fm_height, fm_width, per_cell, fm_scale);
-    return PP_ERR_VALUE;
-  }
-  an->grid = 1;
-  an->fm_w = fm_width;
-  an->fm_h = fm_height;
-  an->per_cell = per_cell;
-  an->fm_scale = fm_scale;
-  an->types = anchor_types_dev;
+  if (arm) std::memcpy(ctx->tgt_key, key.v, sizeof key.v);
   return PP_OK;
 }
 
@@ -2496,15 +2652,9 @@ extern "C" int pp_assign_targets_dev(pp_ctx_t *ctx, void *stream_, int64_t A,
                                      const double *g_yaw, const int32_t *g_class,
                                      const pp_target_params_t *prm, float *cls_targets,
                                      float *reg_targets) {
-  AnchorSource an;
-  if (int rc = check_anchor_arrays(a_corners, a_centers, a_wlh, a_yaw, &an)) return rc;
-  if (G < 0 || G > 65535) {
-    set_error("pp_assign_targets_dev: bad sizes (G=%lld)", (long long)G);
-    return PP_ERR_VALUE;
-  }
-  const int32_t g1 = (int32_t)G;
-  return assign_targets_impl(ctx, stream_, 1, &g1, A, an, g_corners, g_centers_img, g_centers, g_wlh,
-                             g_yaw, g_class, prm, cls_targets, reg_targets);
+  const AnchorSource an{A, a_corners, a_centers, a_wlh, a_yaw};
+  return assign_targets(ctx, stream_, "pp_assign_targets_dev", G, 1, nullptr, an,
+                        {g_corners, g_centers_img, g_centers, g_wlh, g_yaw, g_class}, prm, cls_targets, reg_targets);
 }
 
 extern "C" int pp_assign_targets_batch_dev(pp_ctx_t *ctx, void *stream_, int32_t batch,
@@ -2515,10 +2665,9 @@ extern "C" int pp_assign_targets_batch_dev(pp_ctx_t *ctx, void *stream_, int32_t
                                            const double *g_wlh, const double *g_yaw,
                                            const int32_t *g_class, const pp_target_params_t *prm,
                                            float *cls_targets, float *reg_targets) {
-  AnchorSource an;
-  if (int rc = check_anchor_arrays(a_corners, a_centers, a_wlh, a_yaw, &an)) return rc;
-  return assign_targets_impl(ctx, stream_, batch, g_counts, A, an, g_corners, g_centers_img, g_centers,
-                             g_wlh, g_yaw, g_class, prm, cls_targets, reg_targets);
+  const AnchorSource an{A, a_corners, a_centers, a_wlh, a_yaw};
+  return assign_targets(ctx, stream_, nullptr, 0, batch, g_counts, an,
+                        {g_corners, g_centers_img, g_centers, g_wlh, g_yaw, g_class}, prm, cls_targets, reg_targets);
 }
 
 extern "C" int pp_assign_targets_grid_dev(pp_ctx_t *ctx, void *stream_, int fm_height, int fm_width,
@@ -2529,16 +2678,9 @@ extern "C" int pp_assign_targets_grid_dev(pp_ctx_t *ctx, void *stream_, int fm_h
                                           const double *g_yaw, const int32_t *g_class,
                                           const pp_target_params_t *prm, float *cls_targets,
                                           float *reg_targets) {
-  AnchorSource an;
-  if (int rc = check_anchor_grid(fm_height, fm_width, fm_scale, per_cell, anchor_types_dev, &an)) return rc;
-  if (G < 0 || G > 65535) {
-    set_error("pp_assign_targets_grid_dev: bad sizes (G=%lld)", (long long)G);
-    return PP_ERR_VALUE;
-  }
-  const int32_t g1 = (int32_t)G;
-  return assign_targets_impl(ctx, stream_, 1, &g1, (int64_t)fm_height * fm_width * per_cell, an, g_corners,
-                             g_centers_img, g_centers, g_wlh, g_yaw, g_class, prm, cls_targets,
-                             reg_targets);
+  const AnchorSource an = anchor_grid(fm_height, fm_width, fm_scale, per_cell, anchor_types_dev);
+  return assign_targets(ctx, stream_, "pp_assign_targets_grid_dev", G, 1, nullptr, an,
+                        {g_corners, g_centers_img, g_centers, g_wlh, g_yaw, g_class}, prm, cls_targets, reg_targets);
 }
 
 extern "C" int pp_assign_targets_grid_batch_dev(pp_ctx_t *ctx, void *stream_, int32_t batch,
@@ -2549,9 +2691,7 @@ extern "C" int pp_assign_targets_grid_batch_dev(pp_ctx_t *ctx, void *stream_, in
                                                 const double *g_wlh, const double *g_yaw,
                                                 const int32_t *g_class, const pp_target_params_t *prm,
                                                 float *cls_targets, float *reg_targets) {
-  AnchorSource an;
-  if (int rc = check_anchor_grid(fm_height, fm_width, fm_scale, per_cell, anchor_types_dev, &an)) return rc;
-  return assign_targets_impl(ctx, stream_, batch, g_counts, (int64_t)fm_height * fm_width * per_cell, an,
-                             g_corners, g_centers_img, g_centers, g_wlh, g_yaw, g_class, prm,
-                             cls_targets, reg_targets);
+  const AnchorSource an = anchor_grid(fm_height, fm_width, fm_scale, per_cell, anchor_types_dev);
+  return assign_targets(ctx, stream_, nullptr, 0, batch, g_counts, an,
+                        {g_corners, g_centers_img, g_centers, g_wlh, g_yaw, g_class}, prm, cls_targets, reg_targets);
 }

@@ -175,6 +175,14 @@ HostPool *host_pool(pp_ctx *ctx) {
   return ctx->pool;
 }
 
+int dropin_direct() {
+  static const int k_direct = [] {
+    const char *e = getenv("PP_DROPIN_DIRECT");
+    return e ? atoi(e) : 7;
+  }();
+  return k_direct;
+}
+
 }  // namespace pp
 
 using namespace pp;

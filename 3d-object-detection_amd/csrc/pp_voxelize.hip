@@ -2877,7 +2877,7 @@ bool dropin_pack() { static const bool k_pack = env_int("PP_DROPIN_PACK", 1) != 
 // link's rate and the copy's start-up and completion hand-over fall away); 2 -- k_emit writes the descriptors and the
 // totals, which nothing on the device reads back, straight into pinned memory: they are there when the kernel is.
 // 4 -- the features' way back is k_records_to_host, enqueued behind the kernels and sized on the device.
-int dropin_direct() { static const int k_direct = env_int("PP_DROPIN_DIRECT", 7); return k_direct; }
+// (dropin_direct(), pp_common.h: pp_make_ious_f64 reads the same variable)
 
 // one call's state, handed from phase to phase
 struct PillarsCall {

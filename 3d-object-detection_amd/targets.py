@@ -55,9 +55,15 @@ class TargetAssigner:
         self._ctx = _lib.Context(self.device.index, lib_=self._L)
         self._prm = _lib.TargetParams(self.pos_thresh, self.canvas_height, self.num_classes, 0)
 
-    def _check(self, rc, what):
+    def _call(self, name, *args, check=False):
+        """``name(context, current stream, *args)`` on this assigner's build of the library; ``check``: followed by
+        pp_iou_check (synchronises).  A failure raises with that library's own message."""
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = getattr(self._L, name)(self._ctx.handle, stream, *args)
+        if rc == _lib.PP_OK and check:
+            rc = self._L.pp_iou_check(self._ctx.handle, stream)
         if rc != _lib.PP_OK:
-            _lib.check(rc, what, self._L.pp_last_error())
+            _lib.check(rc, name, self._L.pp_last_error())
 
     def _gt_to_device(self, gt_centers, gt_wlh, gt_yaw, gt_classes):
         gt_centers = np.asarray(gt_centers, np.float64).reshape(-1, 3)
@@ -93,23 +99,15 @@ class TargetAssigner:
                     cls_t.dtype != torch.float32 or reg_t.dtype != torch.float32 or \
                     not (cls_t.is_contiguous() and reg_t.is_contiguous()) or cls_t.device != self.device:
                 raise ValueError("out: contiguous f32 (cls[A,C], reg[A,9]) on " + str(self.device))
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        tail = (G, _vp(g_corners), _vp(g_centers_img), _vp(g_centers), _vp(g_wlh), _vp(g_yaw), _vp(g_class),
+                ctypes.byref(self._prm), _vp(cls_t), _vp(reg_t))
         if self.grid is not None:
             c = self.grid
-            rc = self._L.pp_assign_targets_grid_dev(
-                self._ctx.handle, stream, c.fm_height, c.fm_width, float(c.fm_scale), c.per_cell,
-                _vp(self.types), G, _vp(g_corners), _vp(g_centers_img), _vp(g_centers), _vp(g_wlh),
-                _vp(g_yaw), _vp(g_class), ctypes.byref(self._prm), _vp(cls_t), _vp(reg_t))
-            self._check(rc, "pp_assign_targets_grid_dev")
+            self._call("pp_assign_targets_grid_dev", c.fm_height, c.fm_width, float(c.fm_scale), c.per_cell,
+                       _vp(self.types), *tail, check=check)
         else:
-            rc = self._L.pp_assign_targets_dev(
-                self._ctx.handle, stream, self.A, _vp(self.a_corners), _vp(self.a_centers),
-                _vp(self.a_wlh), _vp(self.a_yaw), G, _vp(g_corners), _vp(g_centers_img),
-                _vp(g_centers), _vp(g_wlh), _vp(g_yaw), _vp(g_class), ctypes.byref(self._prm),
-                _vp(cls_t), _vp(reg_t))
-            self._check(rc, "pp_assign_targets_dev")
-        if check:
-            self._check(self._L.pp_iou_check(self._ctx.handle, stream), "pp_assign_targets_dev")
+            self._call("pp_assign_targets_dev", self.A, _vp(self.a_corners), _vp(self.a_centers), _vp(self.a_wlh),
+                       _vp(self.a_yaw), *tail, check=check)
         return cls_t, reg_t
 
     # ------------------------------------------------------------------ a batch of samples per launch
@@ -159,19 +157,14 @@ class TargetAssigner:
         base = packed.data_ptr()
         gp = [ctypes.c_void_p(base + 8 * T * k) if T else None for k in (0, 8, 11, 14, 17, 18)]
         counts = (ctypes.c_int32 * B)(*g_counts)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        tail = (*gp, ctypes.byref(self._prm), _vp(cls_t), _vp(reg_t))
         if self.grid is not None:
             c = self.grid
-            rc = self._L.pp_assign_targets_grid_batch_dev(
-                self._ctx.handle, stream, B, counts, c.fm_height, c.fm_width, float(c.fm_scale), c.per_cell,
-                _vp(self.types), *gp, ctypes.byref(self._prm), _vp(cls_t), _vp(reg_t))
+            self._call("pp_assign_targets_grid_batch_dev", B, counts, c.fm_height, c.fm_width, float(c.fm_scale),
+                       c.per_cell, _vp(self.types), *tail, check=check)
         else:
-            rc = self._L.pp_assign_targets_batch_dev(
-                self._ctx.handle, stream, B, counts, self.A, _vp(self.a_corners), _vp(self.a_centers),
-                _vp(self.a_wlh), _vp(self.a_yaw), *gp, ctypes.byref(self._prm), _vp(cls_t), _vp(reg_t))
-        self._check(rc, "pp_assign_targets_batch_dev")
-        if check:
-            self._check(self._L.pp_iou_check(self._ctx.handle, stream), "pp_assign_targets_batch_dev")
+            self._call("pp_assign_targets_batch_dev", B, counts, self.A, _vp(self.a_corners), _vp(self.a_centers),
+                       _vp(self.a_wlh), _vp(self.a_yaw), *tail, check=check)
         return cls_t, reg_t
 
     def ious(self, g_corners_img, g_centers_img, check=True):
@@ -184,11 +177,6 @@ class TargetAssigner:
         gn = torch.as_tensor(np.ascontiguousarray(g_centers_img), **f64).contiguous()
         G = int(gc.shape[0])
         out = torch.empty((self.A, G), **f64)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = self._L.pp_make_ious_dev(self._ctx.handle, stream, _vp(self.a_corners),
-                                         _vp(self.a_centers), 3, self.A, _vp(gc), _vp(gn),
-                                         int(gn.shape[1]) if G else 3, G, _vp(out))
-        self._check(rc, "pp_make_ious_dev")
-        if check:
-            self._check(self._L.pp_iou_check(self._ctx.handle, stream), "pp_make_ious_dev")
+        self._call("pp_make_ious_dev", _vp(self.a_corners), _vp(self.a_centers), 3, self.A, _vp(gc), _vp(gn),
+                   int(gn.shape[1]) if G else 3, G, _vp(out), check=check)
         return out
