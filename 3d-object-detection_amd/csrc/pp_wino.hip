@@ -17,7 +17,7 @@
 // While the MFMAs of chunk c run on one V/U buffer:
 //   - the raw 18x18-pixel input halo of chunk c+2 is in flight in registers (each pixel's 32 bytes
 //     loaded once, as two 16-byte pieces; pixels outside the image are not loaded, zeros take their
-//     place), and is written to one of two small halo buffers at the end of the chunk;
+//     place), and is written to one of two small halo buffers late in the chunk;
 //   - U of chunk c+1 goes from global memory straight into the other V/U buffer (LDS-DMA: the
 //     packed layout is the LDS image), a piece per position;
 //   - the halo of chunk c+1, in LDS since the previous chunk, is transformed into V of that buffer.
@@ -25,14 +25,43 @@
 // The schedule inside a chunk is written out, not left to the compiler: a chunk is 16 positions of
 // 4 MFMAs, and every LDS access of the chunk is an asm statement in one of the gaps behind an MFMA,
 // waited for with the kernel's own counted s_waitcnt lgkmcnt (LDS accesses complete in order):
-//   - operands: a ring of three register sets; the two ds_read_b128 of position p+2 are issued
-//     behind the first MFMA of position p, so a read has two positions (512 MFMA cycles) to land
-//     and no wait inside a chunk drains the counter;
-//   - transform of chunk c+1: positions 0..3 read one patch column each, positions 4..7 form
-//     that column's four row-transformed values, positions 8..15 each form and write half a row
-//     of V; scalar adds, two to four per gap (packed f32 adds stall beside MFMAs);
+//   - operands: a ring of four register sets, position p in set p % 4; the two ds_read_b128 of
+//     position p+2 are issued behind the first MFMA of position p, so a read has two positions
+//     (512 MFMA cycles) to land and no wait before position 15 drains the counter;
+//   - transform of chunk c+1: positions 0..3 read one patch column each, positions 3..6 form
+//     that column's four row-transformed values, positions 6..13 each form and write half a row
+//     of V; scalar adds, two to six per gap (packed f32 adds stall beside MFMAs);
+//   - the halo of chunk c+2: its loads are issued a piece per position at positions 1..3, with no
+//     branch (the lanes whose pixel lies outside the image are masked in EXEC and keep zeros), so
+//     a step starts on an MFMA; the pieces go to LDS at positions 12..14, each behind a counted
+//     s_waitcnt vmcnt that leaves the later U pieces in flight (a wave's loads complete in order;
+//     the epilogue's stores of the item before are older than all of them);
 //   - which of this is present (a chunk behind, two chunks behind) is a compile-time property of
 //     the step, so a step's MFMAs, operand reads and transform are one basic block.
+//
+// The chunk boundary lies inside position 15.  While a chunk follows, the order there is
+//     wait(15): s_waitcnt vmcnt(0) lgkmcnt(0)  |  first MFMA of position 15  |  s_barrier  |
+//     the ds_read_b128 of the NEXT chunk's positions 0 and 1, from the other V/U buffer, into sets
+//     0 and 1 (left by positions 12 and 13)  |  the other three MFMAs of position 15,
+// so the barrier and the LDS round trip of the next chunk's first operands run under 192 cycles of
+// MFMAs, and the next step starts at its wait(0) with no reads of its own ahead of it.  (The wave
+// waits for those four reads at the end of position 15: what the compiler does with the registers
+// between two bodies must find the values present.  A workgroup's first step finds them read by
+// the prologue.)  Why each buffer's last read precedes its next write, step g reading V/U buffer
+// `cur` and writing `nxt`, barrier g being the one inside step g's position 15:
+//   - `cur` is written again by step g+1, from its position 0 (U) and position 6 (V), behind barrier g.
+//     A wave's operand reads of `cur`, those of positions 14 and 15 last (issued at 12 and 13), have
+//     returned at its wait(15), lgkmcnt(0), ahead of barrier g;
+//   - `nxt` is read first behind barrier g (the reads above).  Every wave's V writes (the last at
+//     position 13) are covered by its lgkmcnt(0), its U pieces (LDS-DMA, which no barrier drains and
+//     no ds_read is ordered behind) by its vmcnt(0), both at wait(15), ahead of barrier g.  The reads
+//     behind barrier g have returned at the end of step g; `nxt` is written again in step g+2, behind
+//     barrier g+1;
+//   - halo buffer g&1 receives the halo of chunk g+2 at positions 12..14 of step g, covered by the
+//     same lgkmcnt(0); it is read by the transform in step g+1, behind barrier g.  Its last reads, of
+//     chunk g's own halo, were the transform's in step g-1 (positions 0..3, returned by wait(6) at the
+//     latest), ahead of barrier g-1;
+//   - a wave is never more than one barrier ahead of another, so nothing else can overlap.
 //
 // The walk.  An item is one (16x16-pixel tile, 64-channel output group) pair, numbered
 //   item = ((b * tiles_y + ty) * tiles_x + tx) * groups + group
@@ -51,9 +80,10 @@
 //     that step loads the next item's chunk 0 and the last step its chunk 1;
 //   - the last step copies U of the next item's chunk 0 (its output group) and transforms its
 //     chunk 0 in the gaps.
-// Behind the last step's barrier come the item's output transform and epilogue, then the next
-// item's first step straight away: its operands are in LDS, it sets the accumulators (C = 0), and
-// the epilogue's stores are in flight under it.  Only the output transform and the stores stay
+// Behind the last step come the item's output transform and epilogue, then the next item's first
+// step straight away: the operands of its positions 0 and 1 are in registers (read behind the last
+// step's barrier), the rest in LDS, it sets the accumulators (C = 0), and the epilogue's stores are
+// in flight under it.  Only the output transform and the stores stay
 // exposed between two items.  Per item the arithmetic and its order are those of a one-item launch:
 // the result does not depend on the walk.
 // Which launch takes which form: Cin >= 24 (three chunks or more) and more items than compute units
@@ -125,6 +155,17 @@ template <int kOff>
 __device__ __forceinline__ void lds_write8(unsigned addr, f32x2 v) {
   asm volatile("ds_write_b64 %0, %1 offset:%2" : : "v"(addr), "v"(v), "i"(kOff) : "memory");
 }
+__device__ __forceinline__ void lds_write16(unsigned addr, f32x4 v) {
+  asm volatile("ds_write_b128 %0, %1" : : "v"(addr), "v"(v) : "memory");
+}
+// the same for the lanes of `lanes` only (wave-uniform), with no branch: a step's body stays one basic block
+__device__ __forceinline__ void lds_write16(unsigned addr, f32x4 v, uint64_t lanes) {
+  uint64_t keep;
+  asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %1\n\tds_write_b128 %2, %3\n\ts_mov_b64 exec, %0"
+               : "=&s"(keep)
+               : "s"(lanes), "v"(addr), "v"(v)
+               : "memory");
+}
 // waits until at most kLeft LDS accesses are outstanding; the values named are read-write operands,
 // so that no use of them is scheduled ahead of the wait
 template <int kLeft>
@@ -136,6 +177,26 @@ __device__ __forceinline__ void lds_wait(f32x4 &a, f32x4 &b, f32x2 (&d)[4]) {
   asm volatile("s_waitcnt lgkmcnt(%6)"
                : "+v"(a), "+v"(b), "+v"(d[0]), "+v"(d[1]), "+v"(d[2]), "+v"(d[3])
                : "i"(kLeft));
+}
+// a halo piece, global memory to registers, for the lanes of `lanes` (wave-uniform; the others keep the zeros
+// that d holds), with no branch.  base + off: a scalar address and the lane's 32-bit byte offset.  The compiler
+// does not count this load either: d passes through vm_wait before its use
+__device__ __forceinline__ void halo_read16(f32x4 &d, const float *base, unsigned off, uint64_t lanes) {
+  uint64_t keep;
+  asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %2\n\tglobal_load_dwordx4 %1, %3, %4\n\ts_mov_b64 exec, %0"
+               : "=&s"(keep), "+v"(d)
+               : "s"(lanes), "v"(off), "s"(base)
+               : "memory");
+}
+// waits until at most kLeft of the wave's global accesses are outstanding (loads complete in order)
+template <int kLeft>
+__device__ __forceinline__ void vm_wait(f32x4 &d) {
+  asm volatile("s_waitcnt vmcnt(%1)" : "+v"(d) : "i"(kLeft));
+}
+// position 15 of a step that another follows: every LDS access and every global access of the wave
+// (the U copy among them) complete, ahead of the barrier behind that position's first MFMA
+__device__ __forceinline__ void wait_all(f32x4 &a, f32x4 &b) {
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(a), "+v"(b) : : "memory");
 }
 // one v_add_f32 / v_sub_f32 per component: left to the compiler, adjacent f32 adds are packed
 // (v_pk_add_f32), which costs MFMA cycles when issued beside them.  Same IEEE results
@@ -163,16 +224,20 @@ __device__ __forceinline__ float acc_read(float m) {
 
 // The order of a step's LDS accesses, by position q = 0..15 (step() follows it to the letter):
 //   ahead of position 0:  operands of positions 0 and 1                       (2 + 2 reads)
+//                         (issued behind the barrier in position 15 of the step before, or by the prologue)
 //   position q:           wait(q), operands of position q+2 while q+2 < 16    (2 reads)
-//                         with a transform: patch column q for q < 4 (4 reads), half a row of V for q >= 8 (2 writes)
-// lds_left(p, tr): the accesses issued after the operand reads of position p and ahead of wait(p),
-// which is what wait(p) leaves outstanding
-constexpr int lds_left(int p, bool tr) {
+//                         with a halo to write: its piece q-12 for 12 <= q < 15 (1 write)
+//                         with a transform: patch column q for q < 4 (4 reads), half a row of V for 6 <= q < 14 (2 writes)
+// lds_left(p, tr, hs): the accesses issued after the operand reads of position p and ahead of wait(p),
+// which is what wait(p) leaves outstanding.  (In a step that another follows, wait(15) leaves nothing:
+// the barrier comes behind it.)
+constexpr int lds_left(int p, bool tr, bool hs) {
   int n = p < 2 ? 2 * (1 - p) : 0;
   for (int q = 0; q < p; ++q) {
     if (q + 2 < 16 && q + 2 > p) n += 2;
+    if (hs && q >= 12 && q < 15 && q + 2 >= p) n += 1;
     if (tr && q < 4 && q + 2 >= p) n += 4;
-    if (tr && q >= 8 && q + 2 >= p) n += 2;
+    if (tr && q >= 6 && q < 14 && q + 2 >= p) n += 2;
   }
   return n;
 }
@@ -213,7 +278,8 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
   // ---- halo loader: piece q = tid + 256*i is half (q&1) of halo pixel q>>1, image pixel
   // (oy0 - 1 + pix/18, ox0 - 1 + pix%18), at hx + hoff[i]: hx is the tile's halo pixel 0, chunk 0
   // (a scalar; outside the image for an edge tile, never dereferenced there), hoff[i] a constant of
-  // the thread in bytes.  hin: the pixel is inside the image.  set_halo() points both at an item
+  // the thread in bytes.  hin: the pixel is inside the image (hlanes: the same per wave, as EXEC masks).
+  // set_halo() points them at an item
   unsigned hoff[kHaloPer];
   int hdst[kHaloPer];
   unsigned hown = 0;
@@ -225,8 +291,12 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
     hdst[i] = hf * kHaloHalf + pix * 4;
     if (q < kHaloPieces) hown |= 1u << i;
   }
+  // the lanes of this wave that own a last piece (the other pieces have an owner in every lane)
+  static_assert(256 * (kHaloPer - 1) <= kHaloPieces && kHaloPer == 3, "pieces 0 and 1 whole, piece 2 partial");
+  const uint64_t hlast = __ballot((hown >> (kHaloPer - 1)) & 1);
   const float *hx = x;
   unsigned hin = 0;
+  uint64_t hlanes[kHaloPer] = {};   // per piece, the lanes of this wave whose pixel is inside the image
   auto set_halo = [&](const Item &it) {
     hx = x + (((int64_t)it.b * H + (it.oy0 - 1)) * W + (it.ox0 - 1)) * Cin;
     hin = 0;
@@ -240,20 +310,23 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
       const int iy = it.oy0 - 1 + pix / kHaloW, ix = it.ox0 - 1 + pix % kHaloW;
       if (((hown >> i) & 1) && iy >= 0 && iy < H && ix >= 0 && ix < W) hin |= 1u << i;
     }
+#pragma unroll
+    for (int i = 0; i < kHaloPer; ++i) hlanes[i] = __ballot((hin >> i) & 1);
   };
-  // xc: hx of the chunk's item + 8 * its chunk index
-  auto hload = [&](const float *xc, float4 (&hr)[kHaloPer]) {
+  // xc: hx of the chunk's item + 8 * its chunk index.  The prologue's form, as hstore() below; step() issues
+  // a piece per position with halo_read16 and writes it with lds_write16
+  auto hload = [&](const float *xc, f32x4 (&hr)[kHaloPer]) {
 #pragma unroll
     for (int i = 0; i < kHaloPer; ++i) {
-      hr[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      hr[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
       if ((hin >> i) & 1)
-        hr[i] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(xc) + hoff[i]);
+        hr[i] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const char *>(xc) + hoff[i]);
     }
   };
-  auto hstore = [&](float *hb, const float4 (&hr)[kHaloPer]) {
+  auto hstore = [&](float *hb, const f32x4 (&hr)[kHaloPer]) {
 #pragma unroll
     for (int i = 0; i < kHaloPer; ++i)
-      if ((hown >> i) & 1) *reinterpret_cast<float4 *>(hb + hdst[i]) = hr[i];
+      if ((hown >> i) & 1) *reinterpret_cast<f32x4 *>(hb + hdst[i]) = hr[i];
   };
 
   // ---- U: a chunk's 32 KiB are 32 pieces of 1 KiB in the order of the LDS image; wave w copies
@@ -327,10 +400,16 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
   // set by the first chunk's first MFMAs (C = 0): accumulators zeroed ahead of the loop are held
   // in VGPRs until it starts, and they spill
   f32x16 acc[16];
+  // the MFMA operands: a ring of four register sets, position p in set p % 4.  They belong to the kernel,
+  // not to a step: a step enters with the operands of its positions 0 and 1 on their way into sets 0 and 1
+  // (read by the step before, or by the prologue), across the output transform too
+  f32x4 av[4], bv[4];
 
   // one chunk, g of the workgroup's stream (par = g & 1): the halo loads of chunk g+2 and the U copy
   // of chunk g+1 are issued, the MFMAs run on `cur` with the halo of g+1 transformed into `nxt` in
-  // their gaps, then the halo of g+2 is written to LDS.  first: the accumulators are set, not added
+  // their gaps, and the halo of g+2 is written to LDS in the gaps of positions 12..14.  The chunk barrier
+  // stands behind the first MFMA of position 15, and behind it the operands of chunk g+1's positions 0
+  // and 1 are read from `nxt`.  first: the accumulators are set, not added
   // to (an item's chunk 0); more, more2: chunks g+1, g+2 exist.  hsrc: where chunk g+2's halo is
   // read (hload's xc); uco, uchunk: the output group and the chunk index, in its item, of chunk g+1
   const unsigned lds_addr = (unsigned)(uintptr_t)(lptr_t)lds;
@@ -347,41 +426,69 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
     const unsigned v_addr = lds_addr + ((par ^ 1) * kBufFloats + v_off) * 4;
     constexpr int kPos = 2 * kTiles * 4 * 4;   // bytes from position to position, V and U alike
     static_assert(kTiles == kCo, "one position stride for V and U");
-    f32x4 av[3], bv[3];
+    // the buffers' other halves: the operands of chunk g+1, and where the halo of chunk g+2 goes.  That
+    // halo buffer held chunk g's own halo, last read by the transform in step g-1, ahead of its barrier
+    const unsigned an_addr = lds_addr + ((par ^ 1) * kBufFloats + a_off) * 4;
+    const unsigned bn_addr = lds_addr + ((par ^ 1) * kBufFloats + b_off) * 4;
+    const unsigned h_addr = lds_addr + (2 * kBufFloats + par * kHaloFloats) * 4;
     f32x2 d[4][4], e[16], v[2];
-    lds_read16<0>(av[0], a_addr);
-    lds_read16<0>(bv[0], b_addr);
-    lds_read16<kPos>(av[1], a_addr);
-    lds_read16<kPos>(bv[1], b_addr);
-    float4 hr[kHaloPer];
-    if constexpr (more2) hload(hsrc, hr);
+    f32x4 hr[kHaloPer];
     const float *usrc = ufirst(uco, uchunk);
+    // the wave's global accesses of a step with a halo to load, in their order: U piece 0 (position 0), then
+    // halo piece i and U piece i+1 at position i+1, then U pieces 4..7.  vm_left(i): those behind halo piece i
+    constexpr auto vm_left = [](int i) { return (7 - i) + (kHaloPer - 1 - i); };
+    static_assert(more || !more2, "a halo is loaded only beside a U copy");
     static_for<16>([&](auto pc) {
-      constexpr int p = decltype(pc)::value, s = p % 3;
-      constexpr int left = lds_left(p, tr);
+      constexpr int p = decltype(pc)::value, s = p % 4;
+      constexpr int left = lds_left(p, tr, more2);
       static_assert(left < 16, "lgkmcnt has four bits");
-      if constexpr (tr && p >= 4 && p < 8)
-        lds_wait<left>(av[s], bv[s], d[p - 4]);
+      if constexpr (more && p == 15)
+        wait_all(av[s], bv[s]);
+      else if constexpr (tr && p >= 3 && p < 7)
+        lds_wait<left>(av[s], bv[s], d[p - 3]);
       else
         lds_wait<left>(av[s], bv[s]);
-      // ---- gap 0: the operands of position p+2, into the set that position p-1 has left
+      // ---- gap 0: the operands of position p+2, into the set that position p-2 has left
       if constexpr (first)
         acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s].x, bv[s].x, f32x16{}, 0, 0, 0);
       else
         acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s].x, bv[s].x, acc[p], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (p + 2 < 16) {
-        lds_read16<(p + 2) * kPos>(av[(p + 2) % 3], a_addr);
-        lds_read16<(p + 2) * kPos>(bv[(p + 2) % 3], b_addr);
+        lds_read16<(p + 2) * kPos>(av[(p + 2) % 4], a_addr);
+        lds_read16<(p + 2) * kPos>(bv[(p + 2) % 4], b_addr);
+      }
+      if constexpr (more && p == 15) {
+        // the chunk barrier.  Ahead of it (wait_all) this wave's V and halo writes and its U pieces have
+        // landed, and every operand it reads from `cur` has returned: behind it `nxt` is complete and `cur`
+        // is free.  The operands of the next step's positions 0 and 1 go into sets 0 and 1, which
+        // positions 12 and 13 have left; the three MFMAs that follow cover their round trip
+        asm volatile("s_barrier" ::: "memory");
+        lds_read16<0>(av[0], an_addr);
+        lds_read16<0>(bv[0], bn_addr);
+        lds_read16<kPos>(av[1], an_addr);
+        lds_read16<kPos>(bv[1], bn_addr);
+      }
+      if constexpr (more2 && p >= 1 && p < 1 + kHaloPer) {   // the halo of chunk g+2: a piece per position leaves
+        hr[p - 1] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        halo_read16(hr[p - 1], hsrc, hoff[p - 1], hlanes[p - 1]);
+      }
+      if constexpr (more2 && p >= 12 && p < 12 + kHaloPer) {   // ... and goes to LDS, eleven positions later
+        constexpr int i = p - 12;
+        vm_wait<vm_left(i)>(hr[i]);
+        if constexpr (i < kHaloPer - 1)
+          lds_write16(h_addr + hdst[i] * 4, hr[i]);
+        else
+          lds_write16(h_addr + hdst[i] * 4, hr[i], hlast);
       }
       // V = B^T d B, rows first.  B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]
-      if constexpr (tr && p >= 4 && p < 8) {
-        constexpr int c = p - 4;
+      if constexpr (tr && p >= 3 && p < 7) {
+        constexpr int c = p - 3;
         e[c] = sub2(d[c][0], d[c][2]);
         e[4 + c] = add2(d[c][1], d[c][2]);
       }
-      if constexpr (tr && p >= 8) {
-        constexpr int r = (p - 8) >> 1;
+      if constexpr (tr && p >= 6 && p < 14) {
+        constexpr int r = (p - 6) >> 1;
         v[0] = (p & 1) ? sub2(e[4 * r + 2], e[4 * r + 1]) : sub2(e[4 * r], e[4 * r + 2]);
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -391,13 +498,13 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
         lds_read8<(0 * kHaloW + p) * 16>(d[p][0], p_addr);
         lds_read8<(1 * kHaloW + p) * 16>(d[p][1], p_addr);
       }
-      if constexpr (tr && p >= 4 && p < 8) {
-        constexpr int c = p - 4;
+      if constexpr (tr && p >= 3 && p < 7) {
+        constexpr int c = p - 3;
         e[8 + c] = sub2(d[c][2], d[c][1]);
         e[12 + c] = sub2(d[c][1], d[c][3]);
       }
-      if constexpr (tr && p >= 8) {
-        constexpr int r = (p - 8) >> 1;
+      if constexpr (tr && p >= 6 && p < 14) {
+        constexpr int r = (p - 6) >> 1;
         v[1] = (p & 1) ? sub2(e[4 * r + 1], e[4 * r + 3]) : add2(e[4 * r + 1], e[4 * r + 2]);
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -407,23 +514,23 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
         lds_read8<(2 * kHaloW + p) * 16>(d[p][2], p_addr);
         lds_read8<(3 * kHaloW + p) * 16>(d[p][3], p_addr);
       }
-      if constexpr (tr && p >= 8) {  // V[row r][columns 2(p&1), 2(p&1)+1]
-        constexpr int r = (p - 8) >> 1, c0 = 2 * (p & 1);
+      if constexpr (tr && p >= 6 && p < 14) {  // V[row r][columns 2(p&1), 2(p&1)+1]
+        constexpr int r = (p - 6) >> 1, c0 = 2 * (p & 1);
         lds_write8<(4 * r + c0) * kPos>(v_addr, v[0]);
         lds_write8<(4 * r + c0 + 1) * kPos>(v_addr, v[1]);
       }
       __builtin_amdgcn_sched_barrier(0);
       // ---- gap 3
       acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s].w, bv[s].w, acc[p], 0, 0, 0);
-      // `nxt` was last read in chunk g-1, before the barrier that ended it
+      // `nxt` was last read in step g-1 (its operands, all returned ahead of that step's barrier)
       if constexpr (more && p < 8) upiece(usrc, nxt, p);
       __builtin_amdgcn_sched_barrier(0);
     });
-    // this halo buffer held chunk g's own halo, last read by the transform of chunk g-1's step
-    if constexpr (more2) hstore(halo + par * kHaloFloats, hr);
-    // the U copy and the V writes: the compiler knows of neither
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __syncthreads();
+    // The body ends here, and the compiler takes the four values read behind the barrier for present: where
+    // it moves one at a block boundary (it does, in the one-item kernel), the move must find it landed.  The
+    // wave waits under position 15's last three MFMAs, 192 cycles of a busy pipe
+    if constexpr (more)
+      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(av[0]), "+v"(bv[0]), "+v"(av[1]), "+v"(bv[1]));
   };
 
   // ---- the workgroup's first item: nothing to hide behind
@@ -431,7 +538,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
   Item it = decode(item);
   set_halo(it);
   {
-    float4 h0[kHaloPer], h1[kHaloPer];
+    f32x4 h0[kHaloPer], h1[kHaloPer];
     hload(hx, h0);
     if (nchunks > 1) hload(hx + kKc, h1);
     const float *usrc = ufirst(it.co0, 0);
@@ -443,6 +550,13 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float *__restrict
     __syncthreads();
     transform(halo, lds);
     __syncthreads();
+    // the first step's operands of positions 0 and 1, which every later step finds read by the one before
+    constexpr int kPos = 2 * kTiles * 4 * 4;
+    lds_read16<0>(av[0], lds_addr + a_off * 4);
+    lds_read16<0>(bv[0], lds_addr + b_off * 4);
+    lds_read16<kPos>(av[1], lds_addr + a_off * 4);
+    lds_read16<kPos>(bv[1], lds_addr + b_off * 4);
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(av[0]), "+v"(bv[0]), "+v"(av[1]), "+v"(bv[1]));
   }
 
   // ---- output transform Y = A^T M A (A^T = [1 1 1 0; 0 1 -1 -1]) and the epilogue, per lane:
