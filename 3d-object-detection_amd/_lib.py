@@ -12,10 +12,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("PP_HIP_LIB") or os.path.join(_HERE, "libpp_hip.so")
 SOURCES = [os.path.join(_HERE, "csrc", f)
-           for f in ("pp_runtime.hip", "pp_voxelize.hip", "pp_iou.hip", "pp_ingest.hip", "pp_decode.hip", "pp_epilogue.hip", "pp_pfn.hip", "pp_pfn_train.hip", "pp_bn_train.hip", "pp_eval.hip", "pp_wino.hip", "pp_conv_f16.hip", "pp_convt_f16.hip", "pp_conv_s2_f16.hip", "pp_stem.hip", "pp_head.hip", "pp_augment.hip", "pp_paste.hip", "pp_loss.hip", "pp_optim.hip")]
+           for f in ("pp_runtime.hip", "pp_voxelize.hip", "pp_iou.hip", "pp_ingest.hip", "pp_decode.hip", "pp_epilogue.hip", "pp_pfn.hip", "pp_pfn_train.hip", "pp_bn_train.hip", "pp_eval.hip", "pp_wino.hip", "pp_conv_f16.hip", "pp_convt_f16.hip", "pp_conv_s2_f16.hip", "pp_conv_split.hip", "pp_stem.hip", "pp_head.hip", "pp_augment.hip", "pp_paste.hip", "pp_loss.hip", "pp_optim.hip")]
 HEADERS = [os.path.join(_HERE, "csrc", "pp_common.h"), os.path.join(_HERE, "csrc", "pp_conv_f16_tile.h"),
            os.path.join(_HERE, "csrc", "pp_box_geom.h"),
-           os.path.join(_ROOT, "include", "pp_hip.h"), os.path.join(_ROOT, "include", "pp_optim.h")]
+           os.path.join(_ROOT, "include", "pp_hip.h"), os.path.join(_ROOT, "include", "pp_optim.h"),
+           os.path.join(_ROOT, "include", "pp_conv_split.h")]
 
 PP_OK, PP_ERR_INDEX, PP_ERR_VALUE, PP_ERR_WINDING = 0, -2, -3, -4
 PP_ERR_NOMEM, PP_ERR_HIP, PP_ERR_INTERNAL = -5, -6, -7
@@ -36,6 +37,8 @@ EXPORTS = [
 ]
 # the optimizer's entry points: declared in include/pp_optim.h, a header of their own
 OPTIM_EXPORTS = ["pp_adam_workspace_bytes", "pp_adam_pack_dev", "pp_adam_step_dev"]
+# the split-fp16 conv: declared in include/pp_conv_split.h, a header of its own
+SPLIT_EXPORTS = ["pp_conv3x3_split_nhwc_dev"]
 
 
 class VoxelParams(ctypes.Structure):
@@ -291,6 +294,8 @@ def _load(path):
     L.pp_conv3x3_wino_nhwc_dev.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, vp, c_int, vp, vp, i64, i64]
     L.pp_conv3x3_f16_nhwc_dev.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, vp, c_int, vp, vp, i64, i64]
     L.pp_conv3x3_s2_f16_nhwc_dev.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, vp, c_int, vp, vp, i64, i64]
+    L.pp_conv3x3_split_nhwc_dev.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, vp, c_int, vp, vp, i64, i64]
+    L.pp_conv3x3_split_nhwc_dev.restype = c_int
     L.pp_convt3x3_f16_nhwc_dev.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, vp, c_int, c_int, c_int, vp, vp, i64,
                                            i64]
     L.pp_conv3x3_s2_pillars_nhwc_dev.argtypes = [vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, vp, c_int, vp, vp,

@@ -1,15 +1,20 @@
 // pp_conv_f16_tile.h -- what the fp16-operand MFMA convolutions (pp_conv_f16.hip, pp_convt_f16.hip,
-// pp_conv_s2_f16.hip) share:
+// pp_conv_s2_f16.hip, pp_conv_split.hip) share:
 // the LDS image of one chunk of 16 input channels, the loader that stages it through registers, the
 // double-buffered chunk pipeline, the epilogue constants, and the host-side argument checks.
 // A kernel brings its tile geometry, its MFMA role (which fragments feed which accumulators) and the
-// accumulator-to-pixel mapping of its stores.  Included by those three files only.
+// accumulator-to-pixel mapping of its stores.  Included by those four files only.
 //
 // One LDS buffer (bytes): A[2 half][halo pixel][8 fp16] then B[9 tap][2 half][64 cout][8 fp16]; half h
 // holds channels 8h .. 8h+7 of the chunk.  A lane's A fragment is 8 consecutive channels of one pixel,
 // one 16-byte read, and the nine taps are constant address offsets into the halo tile (no im2col).
 // The weights arrive in that order, [Cout/64][Cin/16][9 tap][2 half][64][8] fp16: a workgroup's chunk is
 // 18 KB in one piece.
+//
+// Operand planes (the template parameter NP of the geometry, which Stager and chunk_pipeline take with it):
+// NP = 1 is the image above.  NP = 2 is the split-fp16 image of pp_conv_split.hip: every f32 x is staged as
+// x_hi = f16(x) and x_lo = f16((x - x_hi) * 2^11), and the buffer is A_hi, A_lo, B_hi, B_lo, each part laid
+// out as above; the weights arrive as [Cout/64][Cin/16][2 plane][9 tap][2 half][64][8], 36 KB per chunk.
 #pragma once
 
 #include "pp_common.h"
@@ -21,7 +26,8 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 // register-staged weights (a vector, not an array: a private array is promoted to LDS before unrolling)
-typedef unsigned u32x20 __attribute__((ext_vector_type(20)));
+template <int N>
+using u32xN = unsigned __attribute__((ext_vector_type(N)));
 
 constexpr int kKc = 16;                      // input channels per chunk
 constexpr int kTw = 32;                      // tile width: the pixels of one MFMA row block
@@ -33,21 +39,26 @@ constexpr int kWaitVm0 = 0x0F70;
 // The halo tile a workgroup of 256 threads stages per chunk: HH rows of HW input pixels.  slot() places
 // halo pixel pix = hy * HW + hx in an A plane, in units of 16 bytes: pixel-linear here; a kernel whose
 // taps step two pixels along a row hides it with a row order of its own (pp_conv_s2_f16.hip).
-template <int HW, int HH>
+template <int HW, int HH, int NP = 1>
 struct HaloGeo {
+  static constexpr int kPlanes = NP;                           // operand planes: 1, or 2 = (hi, lo)
   static constexpr int kHw = HW;                               // halo tile width
   static constexpr int kHalo = HW * HH;                        // halo pixels
   static constexpr int kAPlane = kHalo * 16;
-  static constexpr int kABytes = 2 * kAPlane;
-  static constexpr int kBufBytes = kABytes + kBVecs * 16;
+  static constexpr int kAPart = 2 * kAPlane;                   // the two halves of one operand plane of A
+  static constexpr int kABytes = NP * kAPart;
+  static constexpr int kBPart = kBVecs * 16;                   // one operand plane of B
+  static constexpr int kWVecs = NP * kBVecs;                   // 16-byte vectors of weights per chunk
+  static constexpr int kNW = (kWVecs + 255) / 256;             // ... per thread, the last round partial
+  static constexpr int kBufBytes = kABytes + kWVecs * 16;
   static constexpr int kItems = 2 * kHalo;                     // (pixel, half) pairs of the halo tile
   static constexpr int kNItem = (kItems + 255) / 256;          // ... per thread, the last round partial
   __device__ static __forceinline__ int slot(int pix, int /*hy*/, int /*hx*/) { return pix; }
 };
 
 // The input tile of ROWS rows of kTw pixels plus LO / HI halo pixels on the low / high side of both axes.
-template <int ROWS, int LO, int HI>
-struct TileGeo : HaloGeo<kTw + LO + HI, ROWS + LO + HI> {
+template <int ROWS, int LO, int HI, int NP = 1>
+struct TileGeo : HaloGeo<kTw + LO + HI, ROWS + LO + HI, NP> {
   static constexpr int kRows = ROWS;
   static constexpr int kHl = LO;                               // halo pixels on the low side
 };
@@ -72,16 +83,16 @@ struct Stager {
   const uint4 *wb;
   int xoff[G::kNItem], adst[G::kNItem];
   bool xin[G::kNItem];
-  // only the last round of items and the fifth weight vector (128 threads) depend on the thread
+  // only the last round of items and the last weight vector (NP = 1: the fifth, 128 threads) depend on the thread
   const bool last_item = tid + 256 * (G::kNItem - 1) < G::kItems;
-  const bool wvec4 = tid + 1024 < kBVecs;
+  const bool wvec4 = tid + 256 * (G::kNW - 1) < G::kWVecs;
   float4 xr[G::kNItem][2];
-  u32x20 wr;
+  u32xN<4 * G::kNW> wr;
 
   // (iy0, ix0): the image coordinates of the halo tile's first pixel
   __device__ __forceinline__ Stager(const float *x, const uint4 *w, int b, int H, int W, int Cin, int iy0,
                                     int ix0, int nchunks)
-      : xb(x + (int64_t)b * H * W * Cin), wb(w + (int64_t)blockIdx.y * nchunks * kBVecs) {
+      : xb(x + (int64_t)b * H * W * Cin), wb(w + (int64_t)blockIdx.y * nchunks * G::kWVecs) {
 #pragma unroll
     for (int k = 0; k < G::kNItem; ++k) {
       const int i = tid + 256 * k;
@@ -95,6 +106,7 @@ struct Stager {
   }
 
   __device__ __forceinline__ bool has(int k) const { return k + 1 < G::kNItem || last_item; }
+  __device__ __forceinline__ bool has_w(int i) const { return i + 1 < G::kNW || G::kWVecs % 256 == 0 || wvec4; }
 
   __device__ __forceinline__ void load(int chunk) {
     const float *xc = xb + chunk * kKc;
@@ -104,10 +116,10 @@ struct Stager {
         xr[k][0] = *reinterpret_cast<const float4 *>(xc + xoff[k]);
         xr[k][1] = *reinterpret_cast<const float4 *>(xc + xoff[k] + 4);
       }
-    const uint4 *wc = wb + (int64_t)chunk * kBVecs;
+    const uint4 *wc = wb + (int64_t)chunk * G::kWVecs;
 #pragma unroll
-    for (int i = 0; i < 5; ++i)
-      if (i < 4 || wvec4) {
+    for (int i = 0; i < G::kNW; ++i)
+      if (has_w(i)) {
         const uint4 v = wc[tid + 256 * i];
         wr[4 * i] = v.x;
         wr[4 * i + 1] = v.y;
@@ -124,12 +136,22 @@ struct Stager {
         // f32 -> f16 casts: v_cvt_f16_f32, round to nearest even, +-inf beyond the range
         f16x8 v = {(_Float16)lo.x, (_Float16)lo.y, (_Float16)lo.z, (_Float16)lo.w,
                    (_Float16)hi.x, (_Float16)hi.y, (_Float16)hi.z, (_Float16)hi.w};
+        if constexpr (G::kPlanes == 2) {
+          // the low plane: x - x_hi is exact in f32, the scaling by 2^11 too; one more rounding to fp16.
+          // Beyond the fp16 range x_hi is +-inf and x_lo is -+inf: non-finite in both planes
+          const float x8[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+          f16x8 r;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) r[j] = (_Float16)((x8[j] - (float)v[j]) * 2048.0f);
+          if (!xin[k]) r = f16x8{};
+          *reinterpret_cast<f16x8 *>(buf + G::kAPart + adst[k]) = r;
+        }
         if (!xin[k]) v = f16x8{};
         *reinterpret_cast<f16x8 *>(buf + adst[k]) = v;
       }
 #pragma unroll
-    for (int i = 0; i < 5; ++i)
-      if (i < 4 || wvec4)
+    for (int i = 0; i < G::kNW; ++i)
+      if (has_w(i))
         *reinterpret_cast<uint4 *>(buf + G::kABytes + (tid + 256 * i) * 16) =
             make_uint4(wr[4 * i], wr[4 * i + 1], wr[4 * i + 2], wr[4 * i + 3]);
   }

@@ -165,6 +165,37 @@ def _conv_f16(x, w16, table, cout, out=None, channel_offset=0):
     return _conv3x3_nhwc("pp_conv3x3_f16_nhwc_dev", x, w16, table, cout, out, channel_offset)
 
 
+def _split_filter(w):
+    """Conv weight [Cout,Cin,3,3] -> pp_conv3x3_split_nhwc_dev's operand (include/pp_conv_split.h), made in f64: per
+    output channel the power-of-two scale 2^e_c with max|w_c| * 2^e_c in [1, 2) (e_c = 0 for an all-zero channel),
+    ``w_hi = f16(w * 2^e_c)``, ``w_lo = f16((w * 2^e_c - w_hi) * 2^11)``, both planes in the layout
+    [Cout/64][Cin/16][2 plane][9][2][64][8], then the Cout scales 2^-e_c as f32: one flat fp16 tensor."""
+    co, ci = w.shape[:2]
+    wd = w.detach().double()
+    amax = wd.abs().reshape(co, -1).amax(1)
+    e = -torch.frexp(amax)[1].double() + 1.0                  # amax = m * 2^k, m in [0.5, 1): e = 1 - k
+    e = torch.where(amax > 0, e, torch.zeros_like(e))
+    ws = torch.ldexp(wd, e.view(co, 1, 1, 1).to(torch.int32))
+    hi = ws.half()
+    lo = ((ws - hi.double()) * 2048.0).half()
+    planes = torch.stack([hi, lo], 0).reshape(2, co // 64, 64, ci // 16, 2, 8, 9).permute(1, 3, 0, 6, 4, 2, 5)
+    scale = torch.ldexp(torch.ones_like(e), (-e).to(torch.int32)).float()
+    return torch.cat([planes.reshape(-1), scale.contiguous().view(torch.float16)])
+
+
+def _split_ok(module, conv, x, transposed=False):
+    """The split-fp16 MFMA kernel takes this layer: the module's ``winograd`` and ``split_mma`` flags, f32,
+    Cin % 16 == 0."""
+    return (module.winograd and module.split_mma and x.dtype == torch.float32
+            and _conv3x3_s1_ok(conv, x, 16, transposed))
+
+
+def _conv_split(x, ws, table, cout, out=None, channel_offset=0):
+    """pp_conv3x3_split_nhwc_dev: ``_conv_wino``'s layer at f32 grade on the fp16 MFMA pipe (``ws`` from
+    ``_split_filter``); f32 activations in and out."""
+    return _conv3x3_nhwc("pp_conv3x3_split_nhwc_dev", x, ws, table, cout, out, channel_offset)
+
+
 def _conv_out_size(n):
     """The output extent of a 3x3, padding-1, stride-2 conv along an axis of ``n`` input pixels."""
     return (n + 1) // 2
@@ -337,7 +368,7 @@ class _FusedConv:
     def __init__(self):
         self._table_key = None
         self._table = None
-        self._packed = {}           # kind ("nhwc", "wino", "f16", "convt_f16", "stem") -> (key, packed weight)
+        self._packed = {}           # kind ("nhwc", "wino", "f16", "split", "convt_f16", "stem") -> (key, packed weight)
 
     def table(self, bias, bn):
         """[C,3] f32: conv bias, BatchNorm scale, BatchNorm shift."""
@@ -365,7 +396,8 @@ class _FusedConv:
 
     def __call__(self, module, conv, bn, x, out=None, channel_offset=0, transposed=False, defer=False):
         """``bn(relu(conv(x)))`` into a new tensor, or into channels [channel_offset, +Cout) of ``out``: the fp16
-        kernel if ``module.half_mma`` and the layer is eligible, else the Winograd kernel if ``module.winograd``
+        kernel if ``module.half_mma`` and the layer is eligible, else the split-fp16 kernel if ``module.winograd and
+        module.split_mma`` and the layer is eligible, else the Winograd kernel if ``module.winograd``
         and the layer is eligible, else (a strided ConvTranspose) the fp16 transposed-conv kernel if
         ``module.half_mma_up`` and the layer is eligible, else (a stride-2 conv) the fp16 stride-2 kernel if
         ``module.half_mma_s2`` and the layer is eligible, else MIOpen's conv (``transposed``: ConvTranspose) and
@@ -382,6 +414,9 @@ class _FusedConv:
         if _f16_ok(module, conv, x, transposed) and out_ok and (out is None or out.data_ptr() % 16 == 0):
             w16 = self.packed("f16", conv.weight, _f16_filter, transposed)
             return done(_conv_f16(x, w16, self.table(conv.bias, bn), conv.out_channels, out, channel_offset))
+        if _split_ok(module, conv, x, transposed) and out_ok and (out is None or out.data_ptr() % 16 == 0):
+            ws = self.packed("split", conv.weight, _split_filter, transposed)
+            return done(_conv_split(x, ws, self.table(conv.bias, bn), conv.out_channels, out, channel_offset))
         if _wino_ok(module, conv, x, transposed) and out_ok:
             u = self.packed("wino", conv.weight, _wino_filter, transposed)
             return done(_conv_wino(x, u, self.table(conv.bias, bn), conv.out_channels, out, channel_offset))
@@ -660,6 +695,10 @@ class PPDownBlock(nn.Module):
         #: opt-in "fp16 inference" (PPModel.set_inference_precision): those layers with fp16 operands and
         #: f32 accumulation instead (csrc/pp_conv_f16.hip); changes results at the 1e-4 level
         self.half_mma = False
+        #: opt-in (PillarPipeline sets it where it measured ahead): the Winograd layers at f32 grade on the fp16 MFMA
+        #: pipe instead, split-fp16 operands and three products per f32 product (csrc/pp_conv_split.hip); results
+        #: stay within the Winograd kernel's own error bound
+        self.split_mma = False
         #: opt-in, with either fp16 mode (``set_inference_precision(..., strided=True)``): the stride-2 layer that
         #: opens the block as one fused fp16-operand kernel too (csrc/pp_conv_s2_f16.hip: conv and epilogue in one
         #: pass, no MIOpen call); where the pillar-driven stem takes down1's first layer, it keeps it, in f32
@@ -703,6 +742,7 @@ class PPUpBlock(nn.Module):
         self.fused_train = True
         self.winograd = True
         self.half_mma = False
+        self.split_mma = False
         #: opt-in "fp16-up" inference: a stride-2 or stride-4 block as one fused fp16-operand kernel
         #: (csrc/pp_convt_f16.hip: transposed conv and epilogue in one pass, no MIOpen call, no zero fill)
         self.half_mma_up = False

@@ -19,11 +19,17 @@ from .targets import TargetAssigner
 from .voxelizer import PillarVoxelizer, VoxelConfig
 
 
+#: the backbone blocks whose stride-1 layers PillarPipeline switches to the split-fp16 kernel: those of down1, down2,
+#: down3, up1 at whose headline shape (B = 4, 500 x 500 canvas) the slowest of three legs of 500 launches of
+#: ``_conv_split`` was ahead of the fastest Winograd leg (profiles/r29/NOTES.md)
+SPLIT_MMA_BLOCKS = ("down1", "down2", "down3", "up1")
+
+
 class PillarPipeline:
     def __init__(self, vox_cfg: VoxelConfig, anchor_cfg: boxes.AnchorConfig = None,
                  feature_channels=64, num_classes=9, reg_dims=8, device=None, seed=0,
                  pos_thresh=0.6, with_targets=False, data_mean=None, precision="f32",
-                 strided=False, augment=None, paste=None, fused_loss=False):
+                 strided=False, augment=None, paste=None, fused_loss=False, split_mma=True):
         """``augment``: an ``augment.AugmentConfig`` -- ``train_forward_backward(..., augment_rng=rng)`` then augments
         the points and the boxes on the device before the voxelizer and the assigner (needs ``with_targets``).
         ``paste``: ``(augment.GtBank, augment.PasteConfig)`` -- ground-truth sampling before that augmentation, so
@@ -32,6 +38,10 @@ class PillarPipeline:
         ``precision``: ``PPModel.set_inference_precision`` ("f32", "fp16" for fp16-operand MFMA in the
         backbone's stride-1 layers at inference, or "fp16-up" for those and the two strided transposed convolutions);
         ``strided``: its keyword of the same name (the down blocks' stride-2 convolutions too; not with "f32").
+        ``split_mma``: with ``precision="f32"``, the stride-1 layers of ``SPLIT_MMA_BLOCKS`` run the split-fp16 MFMA
+        kernel (``PPDownBlock.split_mma``, csrc/pp_conv_split.hip: f32-grade results on the fp16 matrix pipe) instead
+        of the Winograd kernel; False keeps every block on Winograd, and so does ``with_targets`` (a training
+        pipeline: activations beyond the kernel's window, |x| >= 65520, come out as NaN).
         ``fused_loss``: ``train_forward_backward`` computes the loss and its gradients with ``loss.FusedPPLoss`` (three
         HIP launches, no host wait) instead of ``PPLoss``."""
         check_inference_precision(precision, strided)      # before anything is built
@@ -50,6 +60,11 @@ class PillarPipeline:
         self.model.set_inference_precision(precision, strided)
         # inference: the head reads the up blocks' outputs where they lie (PPDetectionHead.fused_parts)
         self.model.det_head.fused_parts = True
+        # ... and the stride-1 layers of the blocks that measured ahead of the Winograd kernel run split-fp16.  Not in
+        # a pipeline built for training: it evaluates weights between optimizer steps, whose activations nothing
+        # bounds, and the kernel's window ends at |x| < 65520 (a step at lr 0.05 took down3's inputs to 7.9e4)
+        for name in SPLIT_MMA_BLOCKS if split_mma and precision == "f32" and not with_targets else ():
+            getattr(self.model.backbone, name).split_mma = True
         self.loss = FusedPPLoss(return_p=False) if fused_loss else PPLoss()
         self.assigner = None
         if with_targets:
