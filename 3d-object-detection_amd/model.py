@@ -12,6 +12,7 @@ imported reference module).  Differences, none of them numerical:
     pillars are routed to a spill column that is sliced away.
 """
 import ctypes
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -111,33 +112,45 @@ def _wino_filter(w):
     return u.reshape(16, ci // 8, 2, 4, co).permute(0, 1, 2, 4, 3).float().contiguous()
 
 
-def _is_conv3x3(conv, stride, transposed=False):
-    """3x3, the given stride, padding 1, no dilation, no groups (ConvTranspose: no output padding)."""
-    return (tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (stride, stride)
-            and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.groups == 1
-            and (not transposed or tuple(conv.output_padding) == (0, 0)))
+def _conv_kind(conv, transposed=False):
+    """The geometry a fused conv kernel exists for, or None: 3x3, padding 1, no dilation, no groups, and
+    "s1": stride 1 (``transposed``: a ConvTranspose without output padding, read as the conv it stands for);
+    "s2": a conv of stride 2;  "up": a ConvTranspose of stride 2 or 4 with equal output padding below the stride."""
+    if not (tuple(conv.kernel_size) == (3, 3) and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1)
+            and conv.groups == 1):
+        return None
+    s = tuple(conv.stride)
+    if not transposed:
+        return {(1, 1): "s1", (2, 2): "s2"}.get(s)
+    op = tuple(conv.output_padding)
+    if s == (1, 1):
+        return "s1" if op == (0, 0) else None
+    return "up" if s in ((2, 2), (4, 4)) and op[0] == op[1] and 0 <= op[0] < s[0] else None
 
 
-def _conv3x3_s1_ok(conv, x, cin_multiple, transposed):
-    """What both fused stride-1 kernels ask of a layer and its input: ``_is_conv3x3`` at stride 1, a dense
-    16-byte aligned channels-last input, Cin a multiple of ``cin_multiple``, Cout % 64 == 0."""
-    return (_is_nhwc(x) and x.data_ptr() % 16 == 0 and _is_conv3x3(conv, 1, transposed)
-            and x.shape[1] == conv.in_channels and conv.in_channels % cin_multiple == 0
-            and conv.out_channels % 64 == 0)
+def _nhwc_f32(t, aligned=True):
+    """A tensor the fused conv kernels and the head kernel work on in place: dense channels-last f32, 16-byte
+    aligned (``aligned`` False: at any address)."""
+    return _is_nhwc(t) and t.dtype == torch.float32 and (not aligned or t.data_ptr() % 16 == 0)
 
 
-def _wino_ok(module, conv, x, transposed=False):
-    """The fused Winograd kernel takes this layer: the module's ``winograd`` flag, Cin % 8 == 0."""
-    return module.winograd and _conv3x3_s1_ok(conv, x, 8, transposed)
+def _out_extent(kind, h, w, stride=1, output_padding=0):
+    """``(ho, wo)`` of a ``_conv_kind`` layer on h x w pixels ("up": the ConvTranspose's stride and output padding)."""
+    if kind == "up":
+        return (h - 1) * stride + 1 + output_padding, (w - 1) * stride + 1 + output_padding
+    return (h, w) if kind == "s1" else ((h + 1) // 2, (w + 1) // 2)
 
 
-def _conv3x3_nhwc(name, x, w, table, cout, out, channel_offset):
-    """A fused stride-1 conv entry point: conv + bias/ReLU/BatchNorm of ``x`` (NHWC) into a new channels-last
-    tensor, or into channels [channel_offset, +cout) of the channels-last ``out``."""
+def _conv3x3_nhwc(name, x, w, table, cout, out, channel_offset, kind="s1", *scalars):
+    """A fused conv entry point: the ``kind`` layer + bias/ReLU/BatchNorm of ``x`` (NHWC) into a new channels-last
+    tensor, or into channels [channel_offset, +cout) of the channels-last ``out``.  ``scalars``: what the entry
+    point takes between Cout and the table ("up": stride, output padding)."""
     B, C, H, W = x.shape
     if out is None:
-        out = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    _call(name, x.device, _vp(x), B, H, W, C, _vp(w), cout, _vp(table), _vp(out), out.shape[1], int(channel_offset))
+        out = torch.empty((B, cout) + _out_extent(kind, H, W, *scalars), dtype=torch.float32, device=x.device,
+                          memory_format=torch.channels_last)
+    _call(name, x.device, _vp(x), B, H, W, C, _vp(w), cout, *scalars, _vp(table), _vp(out), out.shape[1],
+          int(channel_offset))
     return out
 
 
@@ -152,11 +165,6 @@ def _f16_filter(w):
     channels are one contiguous copy into the kernel's LDS image)."""
     co, ci = w.shape[:2]
     return w.detach().half().reshape(co // 64, 64, ci // 16, 2, 8, 9).permute(0, 2, 5, 3, 1, 4).contiguous()
-
-
-def _f16_ok(module, conv, x, transposed=False):
-    """The fp16-operand MFMA kernel takes this layer: the module's ``half_mma`` flag, Cin % 16 == 0."""
-    return module.half_mma and _conv3x3_s1_ok(conv, x, 16, transposed)
 
 
 def _conv_f16(x, w16, table, cout, out=None, channel_offset=0):
@@ -183,48 +191,17 @@ def _split_filter(w):
     return torch.cat([planes.reshape(-1), scale.contiguous().view(torch.float16)])
 
 
-def _split_ok(module, conv, x, transposed=False):
-    """The split-fp16 MFMA kernel takes this layer: the module's ``winograd`` and ``split_mma`` flags, f32,
-    Cin % 16 == 0."""
-    return (module.winograd and module.split_mma and x.dtype == torch.float32
-            and _conv3x3_s1_ok(conv, x, 16, transposed))
-
-
 def _conv_split(x, ws, table, cout, out=None, channel_offset=0):
     """pp_conv3x3_split_nhwc_dev: ``_conv_wino``'s layer at f32 grade on the fp16 MFMA pipe (``ws`` from
     ``_split_filter``); f32 activations in and out."""
     return _conv3x3_nhwc("pp_conv3x3_split_nhwc_dev", x, ws, table, cout, out, channel_offset)
 
 
-def _conv_out_size(n):
-    """The output extent of a 3x3, padding-1, stride-2 conv along an axis of ``n`` input pixels."""
-    return (n + 1) // 2
-
-
-def _f16_s2_ok(module, conv, x, out):
-    """The fp16-operand stride-2 kernel takes this layer: the module's ``half_mma_s2`` flag; ``_is_conv3x3`` at
-    stride 2; a dense 16-byte aligned channels-last f32 input, Cin % 16 == 0, Cout % 64 == 0; ``out``, if given,
-    channels-last f32, 16-byte aligned and of the strided conv's output extent."""
-    if not (module.half_mma_s2 and _is_conv3x3(conv, 2) and _is_nhwc(x) and x.dtype == torch.float32
-            and x.data_ptr() % 16 == 0 and x.shape[1] == conv.in_channels and conv.in_channels % 16 == 0
-            and conv.out_channels % 64 == 0):
-        return False
-    return out is None or (_is_nhwc(out) and out.dtype == torch.float32 and out.data_ptr() % 16 == 0
-                           and out.shape[0] == x.shape[0]
-                           and tuple(out.shape[2:]) == (_conv_out_size(x.shape[2]), _conv_out_size(x.shape[3])))
-
-
 def _conv_s2_f16(x, w16, table, cout, out=None, channel_offset=0):
     """pp_conv3x3_s2_f16_nhwc_dev: Conv2d(3x3, padding 1, stride 2) + bias/ReLU/BatchNorm of ``x`` (NHWC) with fp16
     operands (``w16`` from ``_f16_filter``) and f32 accumulation, into a new channels-last tensor or into channels
     [channel_offset, +cout) of the channels-last ``out``."""
-    B, C, H, W = x.shape
-    if out is None:
-        out = torch.empty((B, cout, _conv_out_size(H), _conv_out_size(W)), dtype=torch.float32, device=x.device,
-                          memory_format=torch.channels_last)
-    _call("pp_conv3x3_s2_f16_nhwc_dev", x.device, _vp(x), B, H, W, C, _vp(w16), cout, _vp(table), _vp(out),
-          out.shape[1], int(channel_offset))
-    return out
+    return _conv3x3_nhwc("pp_conv3x3_s2_f16_nhwc_dev", x, w16, table, cout, out, channel_offset, "s2")
 
 
 def _convt_f16_filter(w_t):
@@ -233,40 +210,12 @@ def _convt_f16_filter(w_t):
     return _f16_filter(w_t.transpose(0, 1))
 
 
-def _convt_out_size(conv, n):
-    """ConvTranspose2d's output extent along an axis of ``n`` input pixels (kernel 3, padding 1, square)."""
-    return (n - 1) * conv.stride[0] + 1 + conv.output_padding[0]
-
-
-def _convt_f16_ok(module, conv, x, out):
-    """The fp16-operand transposed-conv kernel takes this layer: the module's ``half_mma_up`` flag; 3x3, padding 1,
-    no dilation, no groups, stride (2,2) or (4,4), equal output padding below the stride; a dense 16-byte aligned
-    channels-last input, Cin % 16 == 0, Cout % 64 == 0; ``out``, if given, channels-last f32, 16-byte aligned and of
-    the transposed conv's output extent."""
-    s, op = tuple(conv.stride), tuple(conv.output_padding)
-    if not (module.half_mma_up and tuple(conv.kernel_size) == (3, 3) and s in ((2, 2), (4, 4))
-            and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.groups == 1
-            and op[0] == op[1] and 0 <= op[0] < s[0]
-            and _is_nhwc(x) and x.data_ptr() % 16 == 0 and x.shape[1] == conv.in_channels
-            and conv.in_channels % 16 == 0 and conv.out_channels % 64 == 0):
-        return False
-    return out is None or (_is_nhwc(out) and out.dtype == torch.float32 and out.data_ptr() % 16 == 0
-                           and out.shape[0] == x.shape[0]
-                           and tuple(out.shape[2:]) == (_convt_out_size(conv, x.shape[2]),
-                                                        _convt_out_size(conv, x.shape[3])))
-
-
 def _convt_f16(x, w16, table, cout, stride, output_padding, out=None, channel_offset=0):
     """pp_convt3x3_f16_nhwc_dev: ConvTranspose2d(3x3, padding 1, ``stride`` 2 or 4) + bias/ReLU/BatchNorm of ``x``
     (NHWC) with fp16 operands (``w16`` from ``_convt_f16_filter``) and f32 accumulation, into a new channels-last
     tensor or into channels [channel_offset, +cout) of the channels-last ``out``."""
-    B, C, H, W = x.shape
-    if out is None:
-        out = torch.empty((B, cout, (H - 1) * stride + 1 + output_padding, (W - 1) * stride + 1 + output_padding),
-                          dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    _call("pp_convt3x3_f16_nhwc_dev", x.device, _vp(x), B, H, W, C, _vp(w16), cout, int(stride), int(output_padding),
-          _vp(table), _vp(out), out.shape[1], int(channel_offset))
-    return out
+    return _conv3x3_nhwc("pp_convt3x3_f16_nhwc_dev", x, w16, table, cout, out, channel_offset, "up", int(stride),
+                         int(output_padding))
 
 
 def _stem_filter(w):
@@ -283,7 +232,7 @@ def _stem_ok(backbone, scatter, feats, inds):
     return (backbone.sparse_stem and _use_fused_epilogue(d1, feats) and not scatter.training
             and scatter.channels_last_inference and feats.dim() == 3 and inds.dtype == torch.int64
             and inds.is_cuda and tuple(inds.shape) == (feats.shape[0], feats.shape[2], 3) and feats.shape[2] > 0
-            and _is_conv3x3(conv, 2) and feats.shape[1] == conv.in_channels and conv.in_channels % 8 == 0
+            and _conv_kind(conv) == "s2" and feats.shape[1] == conv.in_channels and conv.in_channels % 8 == 0
             and conv.out_channels % 64 == 0)
 
 
@@ -326,11 +275,6 @@ def _head_filter(w):
     return wp.reshape(nt, 16, k // 16, 4, 4).permute(2, 0, 3, 1, 4).contiguous()
 
 
-def _part_ok(t):
-    """A source the head kernel reads in place: a dense 16-byte aligned channels-last f32 tensor."""
-    return _is_nhwc(t) and t.dtype == torch.float32 and t.data_ptr() % 16 == 0
-
-
 def _head_parts(parts, w_packed, bias, n_out):
     """pp_head1x1_nhwc_dev: the 1x1 head convolution of the channel concatenation of ``parts`` -- pairs
     ``(tensor, table)`` of equally sized channels-last tensors, ``table`` None or the bias/ReLU/BatchNorm table
@@ -359,6 +303,38 @@ def _nhwc_weight(w):
     return w.detach().contiguous(memory_format=torch.channels_last)
 
 
+#: The fused conv kernels, one row each, in their order of priority (``_fused_kernel`` takes the first eligible row):
+#: the launcher's name (looked up on this module at call time, so a test can count or replace it), the block
+#: switches that must all be on, the ``_conv_kind`` it computes, the multiple Cin must be, whether a caller's ``out``
+#: must be 16-byte aligned (the Winograd entry point does not ask for it), ``_FusedConv.packed``'s kind and packer
+#: (the stride-2 kernel reads the stride-1 fp16 kernel's layout: one entry).
+_Kernel = namedtuple("_Kernel", "launcher switches kind cin_multiple aligned_out cache pack")
+_KERNELS = (
+    _Kernel("_conv_f16", ("half_mma",), "s1", 16, True, "f16", _f16_filter),
+    _Kernel("_conv_split", ("winograd", "split_mma"), "s1", 16, True, "split", _split_filter),
+    _Kernel("_conv_wino", ("winograd",), "s1", 8, False, "wino", _wino_filter),
+    _Kernel("_convt_f16", ("half_mma_up",), "up", 16, True, "convt_f16", _convt_f16_filter),
+    _Kernel("_conv_s2_f16", ("half_mma_s2",), "s2", 16, True, "f16", _f16_filter),
+)
+
+
+def _fused_kernel(module, conv, kind, scalars, x, out):
+    """The first row of ``_KERNELS`` that takes this layer, or None.  Every kernel asks for a ``_conv_kind`` layer,
+    an ``_nhwc_f32`` input of the conv's Cin channels, Cout % 64 == 0 and, for ``out``, a channels-last f32 tensor of
+    the input's batch and the layer's output extent; a row adds its kind, its switches, its multiple of Cin and
+    whether ``out`` must be aligned.  ``scalars``: ``_out_extent``'s for ``kind``."""
+    if kind is None or not _nhwc_f32(x) or x.shape[1] != conv.in_channels or conv.out_channels % 64 != 0:
+        return None
+    if out is not None and (out.shape[0] != x.shape[0]
+                            or tuple(out.shape[2:]) != _out_extent(kind, x.shape[2], x.shape[3], *scalars)):
+        return None
+    for k in _KERNELS:
+        if (k.kind == kind and conv.in_channels % k.cin_multiple == 0 and all(getattr(module, s) for s in k.switches)
+                and (out is None or _nhwc_f32(out, k.aligned_out))):
+            return k
+    return None
+
+
 class _FusedConv:
     """One conv + BatchNorm pair on the no-grad inference path: which kernel takes it, and what that kernel needs
     beside the activation.  Not a module and no owner of parameters: it caches the epilogue table and the conv weight
@@ -366,67 +342,45 @@ class _FusedConv:
     copied or moved model starts over)."""
 
     def __init__(self):
-        self._table_key = None
-        self._table = None
-        self._packed = {}           # kind ("nhwc", "wino", "f16", "split", "convt_f16", "stem") -> (key, packed weight)
+        self._table = _LayoutCache()
+        self._packed = {}           # kind ("nhwc", "wino", "f16", "split", "convt_f16", "stem") -> _LayoutCache
 
     def table(self, bias, bn):
         """[C,3] f32: conv bias, BatchNorm scale, BatchNorm shift."""
+        def make():
+            scale, shift = _bn_affine(bn)
+            b = bias.double() if bias is not None else torch.zeros_like(scale)
+            return torch.stack([b, scale, shift], 1).float().contiguous()
+
         # num_batches_tracked: the fused training kernels update running_mean / running_var
         # through raw pointers (no version bump), but every such step bumps the counter
         ts = (bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked)
-        key = tuple((t.data_ptr(), t._version) for t in ts if t is not None)
-        if key != self._table_key:
-            with torch.no_grad():
-                scale, shift = _bn_affine(bn)
-                b = bias.double() if bias is not None else torch.zeros_like(scale)
-                self._table = torch.stack([b, scale, shift], 1).float().contiguous()
-            self._table_key = key
-        return self._table
+        return self._table.get([t for t in ts if t is not None], make)
 
     def packed(self, kind, weight, pack, transposed=False):
         """``pack(weight)``, made once per version of ``weight``.  ``transposed``: the weight of a stride-1
         ConvTranspose, packed as the conv weight it stands for: w_conv[co][ci][kh][kw] = w_t[ci][co][2-kh][2-kw]."""
-        key = (weight.data_ptr(), weight._version)
-        hit = self._packed.get(kind)
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                hit = self._packed[kind] = (key, pack(weight.transpose(0, 1).flip(2, 3) if transposed else weight))
-        return hit[1]
+        cache = self._packed.get(kind)
+        if cache is None:
+            cache = self._packed[kind] = _LayoutCache()
+        return cache.get((weight,), lambda: pack(weight.transpose(0, 1).flip(2, 3) if transposed else weight))
 
     def __call__(self, module, conv, bn, x, out=None, channel_offset=0, transposed=False, defer=False):
-        """``bn(relu(conv(x)))`` into a new tensor, or into channels [channel_offset, +Cout) of ``out``: the fp16
-        kernel if ``module.half_mma`` and the layer is eligible, else the split-fp16 kernel if ``module.winograd and
-        module.split_mma`` and the layer is eligible, else the Winograd kernel if ``module.winograd``
-        and the layer is eligible, else (a strided ConvTranspose) the fp16 transposed-conv kernel if
-        ``module.half_mma_up`` and the layer is eligible, else (a stride-2 conv) the fp16 stride-2 kernel if
-        ``module.half_mma_s2`` and the layer is eligible, else MIOpen's conv (``transposed``: ConvTranspose) and
-        the epilogue kernel.
+        """``bn(relu(conv(x)))`` into a new tensor, or into channels [channel_offset, +Cout) of ``out``: the first
+        eligible row of ``_KERNELS``, else MIOpen's conv (``transposed``: ConvTranspose) and the epilogue kernel.
 
         ``defer`` (``out`` is None): a pair ``(tensor, table)`` for a consumer that applies the epilogue as it
         reads (``PPDetectionHead.forward_parts``).  ``table`` is None where a fused kernel has applied it already;
         on the MIOpen branch ``tensor`` is the bare conv output and ``_epilogue(tensor, table)`` is still owed."""
         if defer and out is not None:
             raise ValueError("a deferred epilogue has no destination")
-        done = (lambda t: (t, None)) if defer else (lambda t: t)
-        out_ok = out is None or (_is_nhwc(out) and out.dtype == torch.float32 and out.shape[0] == x.shape[0]
-                                 and out.shape[2:] == x.shape[2:])
-        if _f16_ok(module, conv, x, transposed) and out_ok and (out is None or out.data_ptr() % 16 == 0):
-            w16 = self.packed("f16", conv.weight, _f16_filter, transposed)
-            return done(_conv_f16(x, w16, self.table(conv.bias, bn), conv.out_channels, out, channel_offset))
-        if _split_ok(module, conv, x, transposed) and out_ok and (out is None or out.data_ptr() % 16 == 0):
-            ws = self.packed("split", conv.weight, _split_filter, transposed)
-            return done(_conv_split(x, ws, self.table(conv.bias, bn), conv.out_channels, out, channel_offset))
-        if _wino_ok(module, conv, x, transposed) and out_ok:
-            u = self.packed("wino", conv.weight, _wino_filter, transposed)
-            return done(_conv_wino(x, u, self.table(conv.bias, bn), conv.out_channels, out, channel_offset))
-        if transposed and _convt_f16_ok(module, conv, x, out):
-            w16 = self.packed("convt_f16", conv.weight, _convt_f16_filter)
-            return done(_convt_f16(x, w16, self.table(conv.bias, bn), conv.out_channels, conv.stride[0],
-                                   conv.output_padding[0], out, channel_offset))
-        if not transposed and _f16_s2_ok(module, conv, x, out):
-            w16 = self.packed("f16", conv.weight, _f16_filter)
-            return done(_conv_s2_f16(x, w16, self.table(conv.bias, bn), conv.out_channels, out, channel_offset))
+        kind = _conv_kind(conv, transposed)
+        scalars = (conv.stride[0], conv.output_padding[0]) if kind == "up" else ()
+        k = _fused_kernel(module, conv, kind, scalars, x, out)
+        if k is not None:
+            w = self.packed(k.cache, conv.weight, k.pack, transposed and kind == "s1")
+            y = globals()[k.launcher](x, w, self.table(conv.bias, bn), conv.out_channels, *scalars, out, channel_offset)
+            return (y, None) if defer else y
         w = self.packed("nhwc", conv.weight, _nhwc_weight) if _is_nhwc(x) else conv.weight
         if transposed:
             y = F.conv_transpose2d(x, w, None, conv.stride, conv.padding, conv.output_padding)
@@ -798,30 +752,26 @@ class PPBackbone(nn.Module):
         """``after_stem``: ``x`` is ``down1.stem``'s output instead of the canvas.  ``parts`` (needs ``parts_ok``):
         the three up blocks' outputs as ``(tensor, table)`` pairs (``_FusedConv.__call__``'s ``defer``) in the
         order of the concatenation, each block in a tensor of its own; the concatenated tensor is not built."""
-        if parts:
-            if not self.parts_ok(x):
-                raise RuntimeError("PPBackbone: parts need the fused inference path and a channels-last input")
-            x = self.down1(x, 1 if after_stem else 0)
-            p1 = self.up1(x, defer=True)
-            x = self.down2(x)
-            p2 = self.up2(x, defer=True)
-            x = self.down3(x)
-            return [p1, p2, self.up3(x, defer=True)]
+        if parts and not self.parts_ok(x):
+            raise RuntimeError("PPBackbone: parts need the fused inference path and a channels-last input")
         # inference: the three up blocks write their channel slices of the concatenated output directly (no
         # torch.cat copy); otherwise ``out`` is None, the offsets are 0 and each returns its own tensor
-        # (all three or none: a block off the fused path returns a tensor of its own and takes no ``out``)
-        fused = all(_use_fused_epilogue(up, x) for up in (self.up1, self.up2, self.up3))
+        # (all three or none: a block off the fused path returns a tensor of its own and takes no ``out``);
+        # ``parts``: no ``out`` either, each block hands back its pair
+        fused = not parts and all(_use_fused_epilogue(up, x) for up in (self.up1, self.up2, self.up3))
         c = self.up1.conv2d_t.out_channels if fused else 0
         x = self.down1(x, 1 if after_stem else 0)
         out = None
         if fused:
             out = torch.empty((x.shape[0], 3 * c, x.shape[2], x.shape[3]), dtype=x.dtype, device=x.device,
                               memory_format=torch.channels_last if _is_nhwc(x) else torch.contiguous_format)
-        out1 = self.up1(x, out, 0)
+        out1 = self.up1(x, out, 0, defer=parts)
         x = self.down2(x)
-        out2 = self.up2(x, out, c)
+        out2 = self.up2(x, out, c, defer=parts)
         x = self.down3(x)
-        out3 = self.up3(x, out, 2 * c)
+        out3 = self.up3(x, out, 2 * c, defer=parts)
+        if parts:
+            return [out1, out2, out3]
         return out if fused else torch.cat((out1, out2, out3), dim=1)
 
 
@@ -871,7 +821,7 @@ class PPDetectionHead(nn.Module):
         """``forward`` of the channel concatenation of ``parts`` (``PPBackbone.forward(..., parts=True)``'s pairs),
         read where the parts lie.  A part the kernel cannot read in place (not dense channels-last, misaligned)
         sends the call the long way round: the owed epilogues, ``torch.cat``, ``forward``."""
-        if (self.parts_ok([t.shape[1] for t, _ in parts]) and all(_part_ok(t) for t, _ in parts)
+        if (self.parts_ok([t.shape[1] for t, _ in parts]) and all(_nhwc_f32(t) for t, _ in parts)
                 and all(t.shape[0] == parts[0][0].shape[0] and t.shape[2:] == parts[0][0].shape[2:]
                         and t.device == self.cls.weight.device for t, _ in parts)):
             w, b = self._packed.get(
@@ -937,9 +887,7 @@ class PPModel(nn.Module):
     def forward_canvas(self, canvas):
         """The network from PPScatter's output on: ``canvas[B,C,H,W]`` in either memory
         format (the fused HIP voxelizer + feature net + scatter writes it channels-last)."""
-        if self._parts_ok(canvas):
-            return self.det_head.forward_parts(self.backbone(canvas, parts=True))
-        return self.det_head(self.backbone(canvas))
+        return self._tail(canvas, False)
 
     def _parts_ok(self, x):
         """The detection head reads the up blocks' outputs directly (``PPDetectionHead.fused_parts``) for the
@@ -948,16 +896,15 @@ class PPModel(nn.Module):
         return (bb.parts_ok(x) and self.det_head.parts_ok(
             [up.conv2d_t.out_channels for up in (bb.up1, bb.up2, bb.up3)]))
 
+    def _tail(self, x, after_stem):
+        """Backbone and head of ``x``: the canvas, or (``after_stem``) ``down1.stem``'s output."""
+        if self._parts_ok(x):
+            return self.det_head.forward_parts(self.backbone(x, after_stem, parts=True))
+        return self.det_head(self.backbone(x, after_stem))
+
     def forward_features(self, feats, inds):
         """Same network from PPFeatureNet's output ``feats[B,C,P]`` on (the fused
         HIP voxelizer + feature net produces it directly)."""
         if _stem_ok(self.backbone, self.scatter, feats, inds):
-            x = self.backbone.down1.stem(feats, inds, self.scatter.h, self.scatter.w)
-            if self._parts_ok(x):
-                return self.det_head.forward_parts(self.backbone(x, after_stem=True, parts=True))
-            return self.det_head(self.backbone(x, after_stem=True))
-        x = self.scatter(feats, inds)
-        if self._parts_ok(x):
-            return self.det_head.forward_parts(self.backbone(x, parts=True))
-        x = self.backbone(x)
-        return self.det_head(x)
+            return self._tail(self.backbone.down1.stem(feats, inds, self.scatter.h, self.scatter.w), True)
+        return self._tail(self.scatter(feats, inds), False)

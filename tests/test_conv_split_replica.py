@@ -146,23 +146,27 @@ def test_replica_with_tiny_weights():
     assert float(w.half().abs().max()) < 2.0 ** -14          # unscaled, every weight is an fp16 subnormal
 
 
-def test_flags_default_off_and_pipeline_constant():
+def test_flags_default_off_and_pipeline_constant(monkeypatch):
     from pp_amd import pipeline
+    from test_model_dispatch import dispatch
     model = M.PPModel(9, 64, 18, 16, 40, 40)
     bb = model.backbone
     assert not any(b.split_mma for b in (bb.down1, bb.down2, bb.down3, bb.up1, bb.up2, bb.up3))
     assert set(pipeline.SPLIT_MMA_BLOCKS) <= {"down1", "down2", "down3", "up1"}
-    import types
     conv = torch.nn.Conv2d(64, 64, 3, 1, 1)
     x = torch.zeros(1, 64, 4, 4).contiguous(memory_format=torch.channels_last)
-    on = types.SimpleNamespace(winograd=True, split_mma=True)
-    assert M._split_ok(on, conv, x)
-    assert not M._split_ok(types.SimpleNamespace(winograd=False, split_mma=True), conv, x)
-    assert not M._split_ok(types.SimpleNamespace(winograd=True, split_mma=False), conv, x)
-    assert not M._split_ok(on, torch.nn.Conv2d(8, 64, 3, 1, 1), torch.zeros(1, 8, 4, 4).contiguous(
-        memory_format=torch.channels_last))                                          # Cin = 8: Winograd's
-    assert not M._split_ok(on, torch.nn.Conv2d(64, 32, 3, 1, 1), x)                  # Cout 32
-    assert not M._split_ok(on, torch.nn.Conv2d(64, 64, 3, 2, 1), x)                  # stride 2
-    assert not M._split_ok(on, conv, torch.zeros(1, 64, 4, 4))                       # NCHW
-    assert not M._split_ok(on, conv, x.double())
-    assert M._split_ok(on, torch.nn.ConvTranspose2d(64, 128, 3, 1, 1, 0), x, True)
+    on = ("winograd", "split_mma")
+
+    def taker(on, conv, x, transposed=False):
+        return dispatch(monkeypatch, on, conv, x, transposed=transposed).taker
+
+    assert taker(on, conv, x) == "_conv_split"
+    assert taker(("split_mma",), conv, x) == "miopen"
+    assert taker(("winograd",), conv, x) == "_conv_wino"
+    assert taker(on, torch.nn.Conv2d(8, 64, 3, 1, 1), torch.zeros(1, 8, 4, 4).contiguous(
+        memory_format=torch.channels_last)) == "_conv_wino"                             # Cin = 8: Winograd's
+    assert taker(on, torch.nn.Conv2d(64, 32, 3, 1, 1), x) == "miopen"                   # Cout 32
+    assert taker(on, torch.nn.Conv2d(64, 64, 3, 2, 1), x) == "miopen"                   # stride 2
+    assert taker(on, conv, torch.zeros(1, 64, 4, 4)) == "miopen"                        # NCHW
+    assert taker(on, conv, x.double()) != "_conv_split"
+    assert taker(on, torch.nn.ConvTranspose2d(64, 128, 3, 1, 1, 0), x, True) == "_conv_split"
