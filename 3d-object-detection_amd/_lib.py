@@ -12,8 +12,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("PP_HIP_LIB") or os.path.join(_HERE, "libpp_hip.so")
 SOURCES = [os.path.join(_HERE, "csrc", f)
-           for f in ("pp_runtime.hip", "pp_voxelize.hip", "pp_iou.hip", "pp_ingest.hip", "pp_decode.hip", "pp_epilogue.hip", "pp_pfn.hip", "pp_pfn_train.hip", "pp_bn_train.hip", "pp_eval.hip", "pp_wino.hip", "pp_conv_f16.hip", "pp_convt_f16.hip", "pp_conv_s2_f16.hip", "pp_conv_split.hip", "pp_stem.hip", "pp_head.hip", "pp_augment.hip", "pp_paste.hip", "pp_loss.hip", "pp_optim.hip")]
+           for f in ("pp_runtime.hip", "pp_voxelize.hip", "pp_iou.hip", "pp_ingest.hip", "pp_decode.hip", "pp_epilogue.hip", "pp_pfn.hip", "pp_pfn_train.hip", "pp_bn_train.hip", "pp_eval.hip", "pp_wino.hip", "pp_conv_f16.hip", "pp_convt_f16.hip", "pp_conv_s2_f16.hip", "pp_conv_split.hip", "pp_conv_s2_split.hip", "pp_convt_split.hip", "pp_stem.hip", "pp_head.hip", "pp_augment.hip", "pp_paste.hip", "pp_loss.hip", "pp_optim.hip")]
 HEADERS = [os.path.join(_HERE, "csrc", "pp_common.h"), os.path.join(_HERE, "csrc", "pp_conv_f16_tile.h"),
+           os.path.join(_HERE, "csrc", "pp_conv_split_tile.h"),
            os.path.join(_HERE, "csrc", "pp_box_geom.h"),
            os.path.join(_ROOT, "include", "pp_hip.h"), os.path.join(_ROOT, "include", "pp_optim.h"),
            os.path.join(_ROOT, "include", "pp_conv_split.h")]
@@ -39,6 +40,8 @@ EXPORTS = [
 OPTIM_EXPORTS = ["pp_adam_workspace_bytes", "pp_adam_pack_dev", "pp_adam_step_dev"]
 # the split-fp16 conv: declared in include/pp_conv_split.h, a header of its own
 SPLIT_EXPORTS = ["pp_conv3x3_split_nhwc_dev"]
+# ... and its strided forms (csrc/pp_conv_s2_split.hip, csrc/pp_convt_split.hip), declared in the same header
+SPLIT_STRIDED_EXPORTS = ["pp_conv3x3_s2_split_nhwc_dev", "pp_convt3x3_split_nhwc_dev"]
 
 
 class VoxelParams(ctypes.Structure):
@@ -296,6 +299,11 @@ def _load(path):
     L.pp_conv3x3_s2_f16_nhwc_dev.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, vp, c_int, vp, vp, i64, i64]
     L.pp_conv3x3_split_nhwc_dev.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, vp, c_int, vp, vp, i64, i64]
     L.pp_conv3x3_split_nhwc_dev.restype = c_int
+    L.pp_conv3x3_s2_split_nhwc_dev.argtypes = L.pp_conv3x3_s2_f16_nhwc_dev.argtypes
+    L.pp_conv3x3_s2_split_nhwc_dev.restype = c_int
+    L.pp_convt3x3_split_nhwc_dev.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, vp, c_int, c_int, c_int, vp, vp,
+                                             i64, i64]
+    L.pp_convt3x3_split_nhwc_dev.restype = c_int
     L.pp_convt3x3_f16_nhwc_dev.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, vp, c_int, c_int, c_int, vp, vp, i64,
                                            i64]
     L.pp_conv3x3_s2_pillars_nhwc_dev.argtypes = [vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, vp, c_int, vp, vp,

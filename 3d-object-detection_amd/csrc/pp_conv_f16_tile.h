@@ -3,7 +3,8 @@
 // the LDS image of one chunk of 16 input channels, the loader that stages it through registers, the
 // double-buffered chunk pipeline, the epilogue constants, and the host-side argument checks.
 // A kernel brings its tile geometry, its MFMA role (which fragments feed which accumulators) and the
-// accumulator-to-pixel mapping of its stores.  Included by those four files only.
+// accumulator-to-pixel mapping of its stores.  Included by those four files and, through pp_conv_split_tile.h, by the
+// split kernels of the strided layers (pp_conv_s2_split.hip, pp_convt_split.hip) only.
 //
 // One LDS buffer (bytes): A[2 half][halo pixel][8 fp16] then B[9 tap][2 half][64 cout][8 fp16]; half h
 // holds channels 8h .. 8h+7 of the chunk.  A lane's A fragment is 8 consecutive channels of one pixel,

@@ -22,18 +22,14 @@
 
 #include <algorithm>
 
-#include "pp_conv_f16_tile.h"
 #include "pp_conv_split.h"
+#include "pp_conv_split_tile.h"
 
 namespace pp {
 
 namespace {
 
 using G = TileGeo<8, 1, 1, 2>;               // pp_conv_f16.hip's tile, two operand planes
-
-// max(u, 0) as torch.relu has it: a NaN stays one (fmaxf would return the 0).  An activation beyond the fp16
-// range gives main = +-inf and corr = -+inf or NaN, so v is NaN wherever that pixel is read: it has to stay loud
-__device__ __forceinline__ float relu_keeps_nan(float u) { return u < 0.0f ? 0.0f : u; }
 
 }  // namespace
 
@@ -119,8 +115,8 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_split(const float *__restric
       const int px = (r & 3) + 8 * (r >> 2) + 4 * h;
       if (ox0 + px < W) {
         float *yp = yrow + px * y_stride;
-        yp[0] = relu_keeps_nan((v0[r] + 0x1p-11f * d0[r]) * e0 + ep.b[0]) * ep.s[0] + ep.t[0];
-        yp[32] = relu_keeps_nan((v1[r] + 0x1p-11f * d1[r]) * e1 + ep.b[1]) * ep.s[1] + ep.t[1];
+        yp[0] = split_output(v0[r], d0[r], e0, ep, 0);
+        yp[32] = split_output(v1[r], d1[r], e1, ep, 1);
       }
     }
   }
@@ -144,9 +140,8 @@ extern "C" int pp_conv3x3_split_nhwc_dev(pp_ctx_t *ctx, void *stream_, const flo
     set_error("pp_conv3x3_split_nhwc_dev: tensor too large");
     return PP_ERR_VALUE;
   }
-  // the two fp16 planes, then the channel scales 2^-e_c as f32
   const uint4 *w = static_cast<const uint4 *>(w_split_dev);
-  const float *esc = reinterpret_cast<const float *>(w + (int64_t)out_channels * in_channels * 9 * 2 * 2 / 16);
+  const float *esc = split_scales(w_split_dev, out_channels, in_channels);
   return launch_on_device(ctx, "k_conv3x3_split", [&] {
     hipLaunchKernelGGL(k_conv3x3_split, dim3((unsigned)blocks, (unsigned)(out_channels / 64)), dim3(256), 0,
                        static_cast<hipStream_t>(stream_), x_dev, w, esc, params_dev, y_dev + y_channel_offset, height,

@@ -1,0 +1,29 @@
+// pp_conv_split_tile.h -- what the split-fp16 convolutions (pp_conv_split.hip, pp_conv_s2_split.hip,
+// pp_convt_split.hip) share beyond pp_conv_f16_tile.h: how an output is made of its two accumulators, and where
+// the channel scales lie behind the packed weight.  include/pp_conv_split.h states the arithmetic.
+#pragma once
+
+#include "pp_conv_f16_tile.h"
+
+namespace pp {
+
+namespace {
+
+// max(u, 0) as torch.relu has it: a NaN stays one (fmaxf would return the 0).  An activation beyond the fp16
+// range gives main = +-inf and corr = -+inf or NaN, so v is NaN wherever that pixel is read: it has to stay loud
+__device__ __forceinline__ float relu_keeps_nan(float u) { return u < 0.0f ? 0.0f : u; }
+
+// y = relu((main + 2^-11 corr) * 2^-e_c + b_c) * s_c + t_c for column block n of ep; both scalings are by powers of two
+template <int NCB>
+__device__ __forceinline__ float split_output(float main, float corr, float esc, const Epilogue<NCB> &ep, int n) {
+  return relu_keeps_nan((main + 0x1p-11f * corr) * esc + ep.b[n]) * ep.s[n] + ep.t[n];
+}
+
+// _split_filter's operand: the two fp16 planes of the weight, then the channel scales 2^-e_c as f32
+inline const float *split_scales(const void *w_split, int out_channels, int in_channels) {
+  return reinterpret_cast<const float *>(static_cast<const uint4 *>(w_split) +
+                                         (int64_t)out_channels * in_channels * 9 * 2 * 2 / 16);
+}
+
+}  // namespace
+}  // namespace pp

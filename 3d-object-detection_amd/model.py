@@ -204,6 +204,12 @@ def _conv_s2_f16(x, w16, table, cout, out=None, channel_offset=0):
     return _conv3x3_nhwc("pp_conv3x3_s2_f16_nhwc_dev", x, w16, table, cout, out, channel_offset, "s2")
 
 
+def _conv_s2_split(x, ws, table, cout, out=None, channel_offset=0):
+    """pp_conv3x3_s2_split_nhwc_dev: ``_conv_s2_f16``'s layer at f32 grade on the fp16 MFMA pipe (``ws`` from
+    ``_split_filter``: the stride-1 split kernel's operand); f32 activations in and out."""
+    return _conv3x3_nhwc("pp_conv3x3_s2_split_nhwc_dev", x, ws, table, cout, out, channel_offset, "s2")
+
+
 def _convt_f16_filter(w_t):
     """ConvTranspose weight [Cin,Cout,3,3] -> pp_convt3x3_f16_nhwc_dev's layout: ``_f16_filter``'s of the weight
     with its first two axes exchanged, [Cout/64][Cin/16][9][2][64][8], tap 3*kh + kw of ``w_t``, not flipped."""
@@ -215,6 +221,20 @@ def _convt_f16(x, w16, table, cout, stride, output_padding, out=None, channel_of
     (NHWC) with fp16 operands (``w16`` from ``_convt_f16_filter``) and f32 accumulation, into a new channels-last
     tensor or into channels [channel_offset, +cout) of the channels-last ``out``."""
     return _conv3x3_nhwc("pp_convt3x3_f16_nhwc_dev", x, w16, table, cout, out, channel_offset, "up", int(stride),
+                         int(output_padding))
+
+
+def _convt_split_filter(w_t):
+    """ConvTranspose weight [Cin,Cout,3,3] -> pp_convt3x3_split_nhwc_dev's operand: ``_split_filter``'s of the weight
+    with its first two axes exchanged, tap 3*kh + kw of ``w_t``, not flipped, one scale per output channel of the
+    transposed conv."""
+    return _split_filter(w_t.transpose(0, 1))
+
+
+def _convt_split(x, ws, table, cout, stride, output_padding, out=None, channel_offset=0):
+    """pp_convt3x3_split_nhwc_dev: ``_convt_f16``'s layer at f32 grade on the fp16 MFMA pipe (``ws`` from
+    ``_convt_split_filter``); f32 activations in and out."""
+    return _conv3x3_nhwc("pp_convt3x3_split_nhwc_dev", x, ws, table, cout, out, channel_offset, "up", int(stride),
                          int(output_padding))
 
 
@@ -307,14 +327,16 @@ def _nhwc_weight(w):
 #: the launcher's name (looked up on this module at call time, so a test can count or replace it), the block
 #: switches that must all be on, the ``_conv_kind`` it computes, the multiple Cin must be, whether a caller's ``out``
 #: must be 16-byte aligned (the Winograd entry point does not ask for it), ``_FusedConv.packed``'s kind and packer
-#: (the stride-2 kernel reads the stride-1 fp16 kernel's layout: one entry).
+#: (the stride-2 kernels read the stride-1 kernels' layouts: one entry each).  A switch a block does not have is off.
 _Kernel = namedtuple("_Kernel", "launcher switches kind cin_multiple aligned_out cache pack")
 _KERNELS = (
     _Kernel("_conv_f16", ("half_mma",), "s1", 16, True, "f16", _f16_filter),
     _Kernel("_conv_split", ("winograd", "split_mma"), "s1", 16, True, "split", _split_filter),
     _Kernel("_conv_wino", ("winograd",), "s1", 8, False, "wino", _wino_filter),
     _Kernel("_convt_f16", ("half_mma_up",), "up", 16, True, "convt_f16", _convt_f16_filter),
+    _Kernel("_convt_split", ("split_mma_up",), "up", 16, True, "convt_split", _convt_split_filter),
     _Kernel("_conv_s2_f16", ("half_mma_s2",), "s2", 16, True, "f16", _f16_filter),
+    _Kernel("_conv_s2_split", ("split_mma_s2",), "s2", 16, True, "split", _split_filter),
 )
 
 
@@ -329,7 +351,8 @@ def _fused_kernel(module, conv, kind, scalars, x, out):
                             or tuple(out.shape[2:]) != _out_extent(kind, x.shape[2], x.shape[3], *scalars)):
         return None
     for k in _KERNELS:
-        if (k.kind == kind and conv.in_channels % k.cin_multiple == 0 and all(getattr(module, s) for s in k.switches)
+        if (k.kind == kind and conv.in_channels % k.cin_multiple == 0
+                and all(getattr(module, s, False) for s in k.switches)
                 and (out is None or _nhwc_f32(out, k.aligned_out))):
             return k
     return None
@@ -343,7 +366,7 @@ class _FusedConv:
 
     def __init__(self):
         self._table = _LayoutCache()
-        self._packed = {}           # kind ("nhwc", "wino", "f16", "split", "convt_f16", "stem") -> _LayoutCache
+        self._packed = {}           # kind ("nhwc", "stem" or a ``_Kernel.cache``) -> _LayoutCache
 
     def table(self, bias, bn):
         """[C,3] f32: conv bias, BatchNorm scale, BatchNorm shift."""
@@ -657,6 +680,10 @@ class PPDownBlock(nn.Module):
         #: opens the block as one fused fp16-operand kernel too (csrc/pp_conv_s2_f16.hip: conv and epilogue in one
         #: pass, no MIOpen call); where the pillar-driven stem takes down1's first layer, it keeps it, in f32
         self.half_mma_s2 = False
+        #: opt-in (``PillarPipeline(split_strided=True)``): that layer at f32 grade on the fp16 MFMA pipe instead of
+        #: MIOpen's conv and an epilogue pass (csrc/pp_conv_s2_split.hip: split-fp16 operands, results within the
+        #: Winograd kernel's error bound); ``half_mma_s2`` comes first, and the pillar-driven stem keeps down1's
+        self.split_mma_s2 = False
         self._fused = [_FusedConv() for _ in range(num_layers)]
 
     def stem(self, feats, inds, h, w):
@@ -700,6 +727,10 @@ class PPUpBlock(nn.Module):
         #: opt-in "fp16-up" inference: a stride-2 or stride-4 block as one fused fp16-operand kernel
         #: (csrc/pp_convt_f16.hip: transposed conv and epilogue in one pass, no MIOpen call, no zero fill)
         self.half_mma_up = False
+        #: opt-in (``PillarPipeline(split_strided=True)``): a stride-2 or stride-4 block at f32 grade on the fp16 MFMA
+        #: pipe instead of MIOpen's transposed conv and an epilogue pass (csrc/pp_convt_split.hip: split-fp16 operands);
+        #: ``half_mma_up`` comes first; ``split_mma`` stays without effect on these blocks
+        self.split_mma_up = False
         self._fused = _FusedConv()
 
     def forward(self, x, out=None, channel_offset=0, defer=False):

@@ -29,7 +29,7 @@ class PillarPipeline:
     def __init__(self, vox_cfg: VoxelConfig, anchor_cfg: boxes.AnchorConfig = None,
                  feature_channels=64, num_classes=9, reg_dims=8, device=None, seed=0,
                  pos_thresh=0.6, with_targets=False, data_mean=None, precision="f32",
-                 strided=False, augment=None, paste=None, fused_loss=False, split_mma=True):
+                 strided=False, augment=None, paste=None, fused_loss=False, split_mma=True, split_strided=False):
         """``augment``: an ``augment.AugmentConfig`` -- ``train_forward_backward(..., augment_rng=rng)`` then augments
         the points and the boxes on the device before the voxelizer and the assigner (needs ``with_targets``).
         ``paste``: ``(augment.GtBank, augment.PasteConfig)`` -- ground-truth sampling before that augmentation, so
@@ -42,9 +42,15 @@ class PillarPipeline:
         kernel (``PPDownBlock.split_mma``, csrc/pp_conv_split.hip: f32-grade results on the fp16 matrix pipe) instead
         of the Winograd kernel; False keeps every block on Winograd, and so does ``with_targets`` (a training
         pipeline: activations beyond the kernel's window, |x| >= 65520, come out as NaN).
+        ``split_strided``: with ``precision="f32"`` only, and not with ``with_targets`` (both a ``ValueError``): the
+        stride-2 convolutions that open down1, down2 and down3 (``PPDownBlock.split_mma_s2``) and the transposed
+        convolutions of up2 and up3 (``PPUpBlock.split_mma_up``) run split-fp16 MFMA kernels of their own
+        (csrc/pp_conv_s2_split.hip, csrc/pp_convt_split.hip) instead of MIOpen's convolutions and an epilogue pass:
+        with it the f32 backbone makes no MIOpen 3x3 call.  Independent of ``split_mma``; the same window.
         ``fused_loss``: ``train_forward_backward`` computes the loss and its gradients with ``loss.FusedPPLoss`` (three
         HIP launches, no host wait) instead of ``PPLoss``."""
         check_inference_precision(precision, strided)      # before anything is built
+        self.check_split_strided(split_strided, precision, with_targets)
         self.check_paste_argument(paste, augment)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.vox_cfg = vox_cfg
@@ -65,6 +71,13 @@ class PillarPipeline:
         # bounds, and the kernel's window ends at |x| < 65520 (a step at lr 0.05 took down3's inputs to 7.9e4)
         for name in SPLIT_MMA_BLOCKS if split_mma and precision == "f32" and not with_targets else ():
             getattr(self.model.backbone, name).split_mma = True
+        # ... and, on request, the strided layers on their split-fp16 kernels
+        if split_strided:
+            bb = self.model.backbone
+            for blk in (bb.down1, bb.down2, bb.down3):
+                blk.split_mma_s2 = True
+            for blk in (bb.up2, bb.up3):
+                blk.split_mma_up = True
         self.loss = FusedPPLoss(return_p=False) if fused_loss else PPLoss()
         self.assigner = None
         if with_targets:
@@ -87,6 +100,19 @@ class PillarPipeline:
         self._canvas_key = None
         #: forward_fused also fuses PPScatter and runs the backbone channels-last
         self.fused_scatter = True
+
+    @staticmethod
+    def check_split_strided(split_strided, precision, with_targets):
+        """The constructor's check of ``split_strided``, before any device is touched."""
+        if not split_strided:
+            return
+        if precision != "f32":
+            raise ValueError(f"split_strided=True goes with precision \"f32\" only, not {precision!r}: the fp16 modes "
+                             "have kernels of their own for these layers (\"fp16-up\", strided=True)")
+        if with_targets:
+            # an explicit request, unlike the default split_mma, which a training pipeline quietly leaves off
+            raise ValueError("split_strided=True is for inference pipelines: nothing bounds a training pipeline's "
+                             "activations between optimizer steps, and the kernels' window ends at |x| < 65520")
 
     @staticmethod
     def check_paste_argument(paste, augment):

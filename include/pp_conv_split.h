@@ -47,6 +47,35 @@
  *
  * Resources on gfx950: 256 threads per 32 x 8 pixels x 64 channels, 117248 bytes of LDS (both planes of A and B,
  * double buffered), 128 accumulator registers per lane: one workgroup per compute unit.  No scratch.
+ *
+ * The strided layers: pp_conv3x3_s2_split_nhwc_dev (csrc/pp_conv_s2_split.hip) and pp_convt3x3_split_nhwc_dev
+ * (csrc/pp_convt_split.hip).  The layers, signatures and argument checks are pp_conv3x3_s2_f16_nhwc_dev's (3x3,
+ * stride 2, padding 1: Ho = (height+1)/2, Wo = (width+1)/2) and pp_convt3x3_f16_nhwc_dev's (ConvTranspose 3x3,
+ * padding 1, stride 2 or 4, 0 <= output_padding < stride: Ho = (height-1)*stride + 1 + output_padding); the
+ * arithmetic is the one above, word for word:
+ *   x is split by the stager: x_hi = f16(x), x_lo = f16((x - x_hi) * 2^11), round to nearest even, subnormals kept;
+ *   a tap outside the image reads zeros in both planes.
+ *   Weights arrive as _split_filter makes them: scale 2^e_c per OUTPUT channel with max|w_c| * 2^e_c in [1, 2),
+ *   planes w_hi, w_lo, then the scales 2^-e_c.  The stride-2 conv reads the operand above unchanged.  The
+ *   transposed conv reads that of the ConvTranspose weight w_t[in][out][kh][kw] with its first two axes exchanged
+ *   (model.py, _convt_split_filter): plane p of w_t[ci][co][kh][kw] at the element formula above, tap 3*kh + kw,
+ *   not flipped, the scales per output channel of the transposed conv.
+ *   main += x_hi * w_hi,  corr += x_hi * w_lo + x_lo * w_hi on v_mfma_f32_32x32x16_f16; lo * lo is dropped.
+ *   v = (main + 2^-11 * corr) * 2^-e_c, then the f32 epilogue y = relu(v + b_c) * s_c + t_c, whose ReLU keeps a NaN
+ *   (u < 0 ? 0 : u).  Fixed schedule: no split-K, no atomics, bit-identical from call to call.
+ * Window: |x| >= 65520 or a NaN makes exactly the outputs that have a tap on that pixel non-finite, and changes no
+ *   other output.  Stride-2 conv: the (oy, ox) with |2*oy - iy| <= 1 and |2*ox - ix| <= 1.  Transposed conv:
+ *   oy = S*iy - 1 + k, ox = S*ix - 1 + k', k, k' in {0, 1, 2}, inside the output.
+ * The tapless pixels of the stride-4 transposed conv (phase 3 and the output-padding rows and columns) are written
+ * by the same epilogue from v = 0.  Every pixel of the slice is written exactly once; no other channel is touched.
+ * Launches only: no allocation, no synchronisation.
+ *
+ * Resources on gfx950 (256 threads, 64 output channels, both planes of A and B double buffered, one workgroup per
+ * compute unit but for the last, no scratch):
+ *   stride-2 conv         32 x 4 output pixels, 150016 bytes of LDS,  4 accumulators (64 registers) per lane
+ *   transposed, stride 2  32 x 2 blocks of 2x2,  86400 bytes of LDS,  8 accumulators (128 registers)
+ *   transposed, stride 4  32 x 1 blocks of 4x4,  77824 bytes of LDS, 10 accumulators (160 registers): the nine
+ *                         one-tap phases of 32 channels split 5 + 4 over two waves; two workgroups per compute unit
  */
 #ifndef PP_CONV_SPLIT_H
 #define PP_CONV_SPLIT_H
@@ -61,6 +90,16 @@ int pp_conv3x3_split_nhwc_dev(pp_ctx_t *ctx, void *stream, const float *x_dev, i
                               int width, int in_channels, const void *w_split_dev, int out_channels,
                               const float *params_dev, float *y_dev, int64_t y_channels,
                               int64_t y_channel_offset);
+
+int pp_conv3x3_s2_split_nhwc_dev(pp_ctx_t *ctx, void *stream, const float *x_dev, int batch, int height,
+                                 int width, int in_channels, const void *w_split_dev, int out_channels,
+                                 const float *params_dev, float *y_dev, int64_t y_channels,
+                                 int64_t y_channel_offset);
+
+int pp_convt3x3_split_nhwc_dev(pp_ctx_t *ctx, void *stream, const float *x_dev, int batch, int height,
+                               int width, int in_channels, const void *w_split_dev, int out_channels, int stride,
+                               int output_padding, const float *params_dev, float *y_dev, int64_t y_channels,
+                               int64_t y_channel_offset);
 
 #ifdef __cplusplus
 }
