@@ -77,9 +77,11 @@ __device__ __forceinline__ void tile_of_block(int tiles_x, int tiles_y, int &bx,
 // not predicated on purpose: under a branch with a zero default, the compiler waits for each load
 // inside its branch (vmcnt(1), vmcnt(0) after every pair), which serialises the halo loads and puts
 // their latency ahead of the MFMAs.
-template <class G>
+// XS: every activation is multiplied by xs on its way in (a power of two: exact), ahead of the casts and the split.
+template <class G, bool XS = false>
 struct Stager {
   const int tid = threadIdx.x;
+  float xs = 1.0f;
   const float *xb;
   const uint4 *wb;
   int xoff[G::kNItem], adst[G::kNItem];
@@ -133,7 +135,11 @@ struct Stager {
 #pragma unroll
     for (int k = 0; k < G::kNItem; ++k)
       if (has(k)) {
-        const float4 lo = xr[k][0], hi = xr[k][1];
+        float4 lo = xr[k][0], hi = xr[k][1];
+        if constexpr (XS) {
+          lo = make_float4(lo.x * xs, lo.y * xs, lo.z * xs, lo.w * xs);
+          hi = make_float4(hi.x * xs, hi.y * xs, hi.z * xs, hi.w * xs);
+        }
         // f32 -> f16 casts: v_cvt_f16_f32, round to nearest even, +-inf beyond the range
         f16x8 v = {(_Float16)lo.x, (_Float16)lo.y, (_Float16)lo.z, (_Float16)lo.w,
                    (_Float16)hi.x, (_Float16)hi.y, (_Float16)hi.z, (_Float16)hi.w};
@@ -165,8 +171,8 @@ struct Stager {
 // its loads and another around its stores (the per-thread predicates of the partial items remain):
 // with that pair, the compiler's wait insertion assumes loads pending across the back edge and waits
 // for the first new load ahead of the MFMAs.
-template <class G, class Mfmas>
-__device__ __forceinline__ void chunk_pipeline(Stager<G> &st, unsigned char *lds, int nchunks, Mfmas &&mfmas) {
+template <class G, bool XS, class Mfmas>
+__device__ __forceinline__ void chunk_pipeline(Stager<G, XS> &st, unsigned char *lds, int nchunks, Mfmas &&mfmas) {
   st.load(0);
   st.store(lds);
   __syncthreads();

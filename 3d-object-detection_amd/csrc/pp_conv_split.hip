@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "pp_conv_split.h"
+#include "pp_conv_train.h"
 #include "pp_conv_split_tile.h"
 
 namespace pp {
@@ -39,6 +40,9 @@ using G = TileGeo<8, 1, 1, 2>;               // pp_conv_f16.hip's tile, two oper
 // prm [Cout][3] (bias, scale, shift).
 // y   pixel p, channel c at y[p*y_stride + c] (y already offset to the channel slice).
 // grid: x = B * ceil(H/8) * ceil(W/32), y = Cout/64.
+// BARE (pp_conv3x3_split_bare_nhwc_dev, include/pp_conv_train.h): y = v, no epilogue; prm is NULL or {s, 1/s}, s a
+// power of two: the stager multiplies x by s ahead of the split and the output is multiplied by 1/s.
+template <bool BARE>
 __global__ __launch_bounds__(256, 1) void k_conv3x3_split(const float *__restrict__ x,
                                                           const uint4 *__restrict__ w,
                                                           const float *__restrict__ esc,
@@ -53,7 +57,8 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_split(const float *__restric
   const int oy0 = by * G::kRows, ox0 = bx * kTw;
   const int co0 = blockIdx.y * kCo;
   const int nchunks = Cin / kKc;
-  Stager<G> stage(x, w, b, H, W, Cin, oy0 - 1, ox0 - 1, nchunks);
+  Stager<G, BARE> stage(x, w, b, H, W, Cin, oy0 - 1, ox0 - 1, nchunks);
+  if constexpr (BARE) stage.xs = prm ? prm[0] : 1.0f;
 
   // ---- MFMA role, as in k_conv3x3_f16: lane (r = lane&31, h = lane>>5) holds A[pixel r of the
   // row][channels 8h..8h+7] and B[channels 8h..8h+7][cout r (+32 for the second column block)]; the lo
@@ -103,7 +108,12 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_split(const float *__restric
   // v = (main + 2^-11 corr) * 2^-e_c: both scalings are by powers of two
   const int co = co0 + l32;
   const float e0 = esc[co], e1 = esc[co + 32];
-  const Epilogue<2> ep(prm, co);
+  const auto ep = [&] {
+    if constexpr (BARE)
+      return Unscale{prm ? prm[1] : 1.0f};
+    else
+      return Epilogue<2>(prm, co);
+  }();
 #pragma unroll
   for (int m = 0; m < 2; ++m) {
     const int oy = oy0 + 2 * wave + m;
@@ -115,8 +125,8 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_split(const float *__restric
       const int px = (r & 3) + 8 * (r >> 2) + 4 * h;
       if (ox0 + px < W) {
         float *yp = yrow + px * y_stride;
-        yp[0] = split_output(v0[r], d0[r], e0, ep, 0);
-        yp[32] = split_output(v1[r], d1[r], e1, ep, 1);
+        yp[0] = split_output<BARE>(v0[r], d0[r], e0, ep, 0);
+        yp[32] = split_output<BARE>(v1[r], d1[r], e1, ep, 1);
       }
     }
   }
@@ -126,25 +136,48 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_split(const float *__restric
 
 using namespace pp;
 
-extern "C" int pp_conv3x3_split_nhwc_dev(pp_ctx_t *ctx, void *stream_, const float *x_dev, int batch,
-                                         int height, int width, int in_channels, const void *w_split_dev,
-                                         int out_channels, const float *params_dev, float *y_dev,
-                                         int64_t y_channels, int64_t y_channel_offset) {
-  if (int rc = check_conv_f16_args("pp_conv3x3_split_nhwc_dev", ctx, x_dev, w_split_dev, params_dev, y_dev, batch,
-                                   height, width, in_channels, out_channels, y_channels, y_channel_offset))
+// Both entry points: the shared checks, the grid, the launch.  prm: the epilogue table, or BARE's x_scale_dev.
+template <bool BARE>
+static int conv3x3_split(const char *fn, pp_ctx_t *ctx, void *stream_, const float *x_dev, int batch, int height,
+                         int width, int in_channels, const void *w_split_dev, int out_channels, const float *prm,
+                         float *y_dev, int64_t y_channels, int64_t y_channel_offset) {
+  // the bare form has no table: its checks are the shared ones minus the params pointer
+  if (int rc = check_conv_f16_args(fn, ctx, x_dev, w_split_dev, BARE ? x_dev : prm, y_dev, batch, height, width,
+                                   in_channels, out_channels, y_channels, y_channel_offset))
     return rc;
   const int64_t tiles_x = (width + kTw - 1) / kTw, tiles_y = (height + G::kRows - 1) / G::kRows;
   const int64_t blocks = (int64_t)batch * tiles_x * tiles_y;
   if (blocks > 0x7fffffff ||
       (int64_t)batch * height * width * std::max<int64_t>(in_channels, y_channels) > ((int64_t)1 << 40)) {
-    set_error("pp_conv3x3_split_nhwc_dev: tensor too large");
+    set_error("%s: tensor too large", fn);
     return PP_ERR_VALUE;
   }
   const uint4 *w = static_cast<const uint4 *>(w_split_dev);
   const float *esc = split_scales(w_split_dev, out_channels, in_channels);
   return launch_on_device(ctx, "k_conv3x3_split", [&] {
-    hipLaunchKernelGGL(k_conv3x3_split, dim3((unsigned)blocks, (unsigned)(out_channels / 64)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream_), x_dev, w, esc, params_dev, y_dev + y_channel_offset, height,
-                       width, in_channels, y_channels, (int)tiles_x, (int)tiles_y);
+    hipLaunchKernelGGL(k_conv3x3_split<BARE>, dim3((unsigned)blocks, (unsigned)(out_channels / 64)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream_), x_dev, w, esc, prm, y_dev + y_channel_offset, height, width,
+                       in_channels, y_channels, (int)tiles_x, (int)tiles_y);
   });
+}
+
+extern "C" int pp_conv3x3_split_nhwc_dev(pp_ctx_t *ctx, void *stream_, const float *x_dev, int batch,
+                                         int height, int width, int in_channels, const void *w_split_dev,
+                                         int out_channels, const float *params_dev, float *y_dev,
+                                         int64_t y_channels, int64_t y_channel_offset) {
+  return conv3x3_split<false>("pp_conv3x3_split_nhwc_dev", ctx, stream_, x_dev, batch, height, width, in_channels,
+                              w_split_dev, out_channels, params_dev, y_dev, y_channels, y_channel_offset);
+}
+
+extern "C" int pp_conv3x3_split_bare_nhwc_dev(pp_ctx_t *ctx, void *stream_, const float *x_dev, int batch,
+                                              int height, int width, int in_channels, const void *w_split_dev,
+                                              int out_channels, const float *x_scale_dev, float *y_dev,
+                                              int64_t y_channels, int64_t y_channel_offset) {
+  if (reinterpret_cast<uintptr_t>(x_scale_dev) & 3) {
+    set_error("pp_conv3x3_split_bare_nhwc_dev: x_scale_dev is not 4-byte aligned");
+    return PP_ERR_VALUE;
+  }
+  return conv3x3_split<true>("pp_conv3x3_split_bare_nhwc_dev", ctx, stream_, x_dev, batch, height, width,
+                             in_channels, w_split_dev, out_channels, x_scale_dev, y_dev, y_channels,
+                             y_channel_offset);
 }

@@ -13,10 +13,19 @@ namespace {
 // range gives main = +-inf and corr = -+inf or NaN, so v is NaN wherever that pixel is read: it has to stay loud
 __device__ __forceinline__ float relu_keeps_nan(float u) { return u < 0.0f ? 0.0f : u; }
 
-// y = relu((main + 2^-11 corr) * 2^-e_c + b_c) * s_c + t_c for column block n of ep; both scalings are by powers of two
-template <int NCB>
-__device__ __forceinline__ float split_output(float main, float corr, float esc, const Epilogue<NCB> &ep, int n) {
-  return relu_keeps_nan((main + 0x1p-11f * corr) * esc + ep.b[n]) * ep.s[n] + ep.t[n];
+// The bare form's tail (include/pp_conv_train.h): y = v * (1/s), s the power of two the stager multiplied x by.
+struct Unscale {
+  float inv;
+};
+
+// y = relu((main + 2^-11 corr) * 2^-e_c + b_c) * s_c + t_c for column block n of ep; both scalings are by powers of two.
+// BARE (ep an Unscale): y = (main + 2^-11 corr) * 2^-e_c * (1/s), no epilogue
+template <bool BARE = false, class Ep>
+__device__ __forceinline__ float split_output(float main, float corr, float esc, const Ep &ep, int n) {
+  if constexpr (BARE)
+    return (main + 0x1p-11f * corr) * esc * ep.inv;
+  else
+    return relu_keeps_nan((main + 0x1p-11f * corr) * esc + ep.b[n]) * ep.s[n] + ep.t[n];
 }
 
 // _split_filter's operand: the two fp16 planes of the weight, then the channel scales 2^-e_c as f32

@@ -173,6 +173,12 @@ def _conv_f16(x, w16, table, cout, out=None, channel_offset=0):
     return _conv3x3_nhwc("pp_conv3x3_f16_nhwc_dev", x, w16, table, cout, out, channel_offset)
 
 
+def _pow2(e):
+    """2^e in f64 for an integer-valued tensor (|e| < 1023), made of the exponent field: exact on every device.
+    ``torch.ldexp`` goes through ``pow``, which on the GPU is a unit in the last place off for some exponents."""
+    return ((e.to(torch.int64) + 1023) << 52).view(torch.float64)
+
+
 def _split_filter(w):
     """Conv weight [Cout,Cin,3,3] -> pp_conv3x3_split_nhwc_dev's operand (include/pp_conv_split.h), made in f64: per
     output channel the power-of-two scale 2^e_c with max|w_c| * 2^e_c in [1, 2) (e_c = 0 for an all-zero channel),
@@ -183,11 +189,11 @@ def _split_filter(w):
     amax = wd.abs().reshape(co, -1).amax(1)
     e = -torch.frexp(amax)[1].double() + 1.0                  # amax = m * 2^k, m in [0.5, 1): e = 1 - k
     e = torch.where(amax > 0, e, torch.zeros_like(e))
-    ws = torch.ldexp(wd, e.view(co, 1, 1, 1).to(torch.int32))
+    ws = wd * _pow2(e).view(co, 1, 1, 1)                      # exact
     hi = ws.half()
     lo = ((ws - hi.double()) * 2048.0).half()
     planes = torch.stack([hi, lo], 0).reshape(2, co // 64, 64, ci // 16, 2, 8, 9).permute(1, 3, 0, 6, 4, 2, 5)
-    scale = torch.ldexp(torch.ones_like(e), (-e).to(torch.int32)).float()
+    scale = _pow2(-e).float()
     return torch.cat([planes.reshape(-1), scale.contiguous().view(torch.float16)])
 
 
@@ -195,6 +201,38 @@ def _conv_split(x, ws, table, cout, out=None, channel_offset=0):
     """pp_conv3x3_split_nhwc_dev: ``_conv_wino``'s layer at f32 grade on the fp16 MFMA pipe (``ws`` from
     ``_split_filter``); f32 activations in and out."""
     return _conv3x3_nhwc("pp_conv3x3_split_nhwc_dev", x, ws, table, cout, out, channel_offset)
+
+
+def _split_pack(weight, into=None):
+    """pp_split_pack_dev: ``(_split_filter(weight), _split_filter(weight.transpose(0, 1).flip(2, 3)))`` -- the
+    operands of the training forward conv and of the conv that computes its data gradient -- in one launch, bit for
+    bit.  ``into``: an earlier result, overwritten where it fits this weight.  Cout % 64 == Cin % 64 == 0."""
+    co, ci = weight.shape[:2]
+    sizes = (co * ci * 18 + 2 * co, co * ci * 18 + 2 * ci)        # flat fp16: planes, then scales
+    if into is not None and all(t.device == weight.device and t.numel() == n for t, n in zip(into, sizes)):
+        fwd, dgrad = into
+    else:
+        fwd, dgrad = (torch.empty(n, dtype=torch.float16, device=weight.device) for n in sizes)
+    w = weight.detach()
+    _call("pp_split_pack_dev", w.device, _vp(w if w.is_contiguous() else w.contiguous()), co, ci, _vp(fwd), _vp(dgrad))
+    return fwd, dgrad
+
+
+def _conv_split_bare(x, ws, cout, x_scale=None):
+    """pp_conv3x3_split_bare_nhwc_dev (include/pp_conv_train.h): ``_conv_split``'s layer without an epilogue, the
+    bare conv output, into a new channels-last tensor.  ``x_scale``: None, or the device pair ``{s, 1/s}`` of
+    ``_pow2_scale``: x is multiplied by s on its way in and the output by 1/s."""
+    B, C, H, W = x.shape
+    out = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    _call("pp_conv3x3_split_bare_nhwc_dev", x.device, _vp(x), B, H, W, C, _vp(ws), cout, _vp(x_scale), _vp(out), cout, 0)
+    return out
+
+
+def _pow2_scale(x):
+    """pp_pow2_scale_dev: the device pair ``{s, 1/s}``, s the power of two that lifts max|x| into [2^13, 2^14)."""
+    scale = torch.empty((2,), dtype=torch.float32, device=x.device)
+    _call("pp_pow2_scale_dev", x.device, _vp(x), x.numel(), _vp(scale))
+    return scale
 
 
 def _conv_s2_f16(x, w16, table, cout, out=None, channel_offset=0):
@@ -388,6 +426,13 @@ class _FusedConv:
             cache = self._packed[kind] = _LayoutCache()
         return cache.get((weight,), lambda: pack(weight.transpose(0, 1).flip(2, 3) if transposed else weight))
 
+    def train_operands(self, weight):
+        """``_split_pack(weight)``: one launch per version of ``weight``, into buffers allocated once."""
+        cache = self._packed.get("split_train")
+        if cache is None:
+            cache = self._packed["split_train"] = _LayoutCache()
+        return cache.get((weight,), lambda: _split_pack(weight, cache._val))
+
     def __call__(self, module, conv, bn, x, out=None, channel_offset=0, transposed=False, defer=False):
         """``bn(relu(conv(x)))`` into a new tensor, or into channels [channel_offset, +Cout) of ``out``: the first
         eligible row of ``_KERNELS``, else MIOpen's conv (``transposed``: ConvTranspose) and the epilogue kernel.
@@ -481,7 +526,8 @@ class _ReluBnTrain(torch.autograd.Function):
     """``BatchNorm2d(ReLU(z + conv_bias))`` in training mode as two passes forward and two
     backward over the activation (csrc/pp_bn_train.hip) instead of a bias kernel, a ReLU kernel
     and MIOpen's BatchNorm each way (plus the bias-gradient reduction); only ``z`` is kept for
-    the backward.  ``conv_bias`` may be None (z already carries it)."""
+    the backward.  ``conv_bias`` may be None (z already carries it).  ``z`` is NCHW-contiguous, or channels-last
+    (``_relu_bn_nhwc``: csrc/pp_bn_train_nhwc.hip); ``y`` and ``dz`` come back in its layout."""
 
     @staticmethod
     def forward(ctx, z, conv_bias, gamma, beta, running_mean, running_var, momentum, eps):
@@ -490,7 +536,8 @@ class _ReluBnTrain(torch.autograd.Function):
         y = torch.empty_like(z)
         mean = torch.empty((C,), dtype=torch.float32, device=dev)
         invstd = torch.empty((C,), dtype=torch.float32, device=dev)
-        _call("pp_relu_bn_train_fwd_dev", dev, _vp(z), _vp(conv_bias), B, C, H * W, _vp(gamma), _vp(beta), float(eps),
+        _call("pp_relu_bn_train_fwd_nhwc_dev" if _relu_bn_nhwc(z) else "pp_relu_bn_train_fwd_dev", dev, _vp(z),
+              _vp(conv_bias), B, C, H * W, _vp(gamma), _vp(beta), float(eps),
               float(momentum), _vp(running_mean), _vp(running_var), _vp(y), _vp(mean), _vp(invstd))
         ctx.save_for_backward(z, conv_bias, gamma, mean, invstd)
         return y
@@ -500,6 +547,15 @@ class _ReluBnTrain(torch.autograd.Function):
         z, conv_bias, gamma, mean, invstd = ctx.saved_tensors
         B, C, H, W = z.shape
         dev = z.device
+        if _relu_bn_nhwc(z):
+            if not (_nhwc_f32(dy) and dy.shape == z.shape):
+                dy = dy.float().contiguous(memory_format=torch.channels_last)
+            dz = torch.empty_like(z)
+            dgamma, dbeta = (torch.empty((C,), dtype=torch.float32, device=dev) for _ in range(2))
+            dbias = torch.empty((C,), dtype=torch.float32, device=dev) if conv_bias is not None else None
+            _call("pp_relu_bn_train_bwd_nhwc_dev", dev, _vp(z), _vp(conv_bias), _vp(dy), B, C, H * W, _vp(gamma),
+                  _vp(mean), _vp(invstd), _vp(dz), _vp(dgamma), _vp(dbeta), _vp(dbias))
+            return dz, dbias, dgamma, dbeta, None, None, None, None
         # a channel slice of a wider NCHW tensor (torch.cat's gradient) is read in place
         if not (dy.dtype == torch.float32 and dy.stride(3) == 1 and dy.stride(2) == W and dy.stride(1) == H * W
                 and (B == 1 or dy.stride(0) >= C * H * W)):
@@ -519,16 +575,51 @@ def _relu_bn_fusable(z, bn):
             and z.numel() > 0)
 
 
+def _relu_bn_nhwc(z):
+    """The channels-last kernels take ``z`` as it lies: dense channels-last f32, 16-byte aligned, C % 4 == 0."""
+    return _nhwc_f32(z) and z.shape[1] % 4 == 0
+
+
 def _relu_bn(z, bn, enabled=True, conv_bias=None):
-    """``bn(relu(z + conv_bias))``; in training mode on the GPU through the fused HIP kernels."""
+    """``bn(relu(z + conv_bias))``; in training mode on the GPU through the fused HIP kernels, NCHW or channels-last
+    (the result comes back in ``z``'s layout)."""
     if enabled and _relu_bn_fusable(z, bn):
-        y = _ReluBnTrain.apply(z if z.is_contiguous() else z.contiguous(), conv_bias, bn.weight, bn.bias,
+        y = _ReluBnTrain.apply(z if z.is_contiguous() or _relu_bn_nhwc(z) else z.contiguous(), conv_bias, bn.weight, bn.bias,
                                bn.running_mean, bn.running_var, float(bn.momentum), float(bn.eps))
         bn.num_batches_tracked.add_(1)
         return y
     if conv_bias is not None:
         z = z + conv_bias.view(1, -1, 1, 1)
     return bn(F.relu(z))
+
+
+class _Conv3x3Train(torch.autograd.Function):
+    """The bare 3x3, stride-1, padding-1 conv of a training layer on the split-fp16 MFMA kernel, forward and data
+    gradient (include/pp_conv_train.h): ``z = conv(x, weight)`` with ``x`` channels-last; the layer's bias and its
+    gradient stay with ``_relu_bn(..., conv_bias=)``.  The data gradient is the same conv on ``dz`` with the weight's
+    first two axes exchanged and its taps flipped, ``dz`` rescaled by a power of two of its own (``_pow2_scale``: the
+    split arithmetic resolves 2^-35 absolutely, which gradients fall under).  The weight gradient is MIOpen's.
+    ``fused``: the layer's ``_FusedConv``, which keeps both packed operands per version of the weight."""
+
+    @staticmethod
+    def forward(ctx, x, weight, fused):
+        fwd, dgrad = fused.train_operands(weight)
+        ctx.save_for_backward(x, weight)
+        ctx.dgrad = dgrad
+        return _conv_split_bare(x, fwd, weight.shape[0])
+
+    @staticmethod
+    def backward(ctx, dz):
+        x, weight = ctx.saved_tensors
+        if not _nhwc_f32(dz):
+            dz = dz.float().contiguous(memory_format=torch.channels_last)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = _conv_split_bare(dz, ctx.dgrad, weight.shape[1], _pow2_scale(dz))
+        if ctx.needs_input_grad[1]:
+            dw = torch.ops.aten.convolution_backward(dz, x, weight, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1,
+                                                     (False, True, False))[1]
+        return dx, dw, None
 
 
 class PPFeatureNet(nn.Module):
@@ -684,6 +775,11 @@ class PPDownBlock(nn.Module):
         #: MIOpen's conv and an epilogue pass (csrc/pp_conv_s2_split.hip: split-fp16 operands, results within the
         #: Winograd kernel's error bound); ``half_mma_s2`` comes first, and the pillar-driven stem keeps down1's
         self.split_mma_s2 = False
+        #: opt-in (``PillarPipeline(with_targets=True, split_train=True)``): in train(), with ``fused_train``, the
+        #: stride-1 layers' forward conv and data gradient on the split-fp16 MFMA kernel and their ReLU -> BatchNorm
+        #: tail channels-last (``_Conv3x3Train``, include/pp_conv_train.h) instead of MIOpen's NCHW f32 convolutions;
+        #: the weight gradient stays MIOpen's.  Forward activations with |x| >= 65520 give NaN
+        self.split_train = False
         self._fused = [_FusedConv() for _ in range(num_layers)]
 
     def stem(self, feats, inds, h, w):
@@ -694,17 +790,30 @@ class PPDownBlock(nn.Module):
         w_taps = fused.packed("stem", conv.weight, _stem_filter)
         return _conv_stem(feats, inds, h, w, w_taps, fused.table(conv.bias, bn), conv.out_channels)
 
+    def _split_train_ok(self, x):
+        """``split_train`` applies: a CUDA f32 tensor and stride-1 layers the kernels take, every one of them."""
+        convs = [self.block[3 * i] for i in range(1, len(self._fused))]
+        return bool(self.split_train and convs and x.is_cuda and x.dtype == torch.float32
+                    and all(_conv_kind(c) == "s1" and c.in_channels % 64 == 0 and c.out_channels % 64 == 0
+                            and c.weight.dtype == torch.float32 for c in convs))
+
     def forward(self, x, first=0):
         """``first`` = 1: ``x`` is ``stem``'s output and has passed layer 0 already."""
         if not _use_fused_epilogue(self, x):
             if first:
                 raise RuntimeError("PPDownBlock: a tensor past layer 0 needs the fused inference path")
             if self.training and self.fused_train and x.is_cuda:
+                split = self._split_train_ok(x)
                 for i in range(len(self._fused)):
                     conv, bn = self.block[3 * i], self.block[3 * i + 2]
+                    if split and i > 0:
+                        x = _relu_bn(_Conv3x3Train.apply(x, conv.weight, self._fused[i]), bn, conv_bias=conv.bias)
+                        continue
                     x = _relu_bn(F.conv2d(x, conv.weight, None, conv.stride, conv.padding), bn,
                                  conv_bias=conv.bias)
-                return x
+                    if split:           # past layer 0: the stride-1 layers run channels-last
+                        x = x.contiguous(memory_format=torch.channels_last)
+                return x.contiguous() if split else x
             return self.block(x)
         for i in range(first, len(self._fused)):
             x = self._fused[i](self, self.block[3 * i], self.block[3 * i + 2], x)

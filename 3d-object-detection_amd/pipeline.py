@@ -29,7 +29,8 @@ class PillarPipeline:
     def __init__(self, vox_cfg: VoxelConfig, anchor_cfg: boxes.AnchorConfig = None,
                  feature_channels=64, num_classes=9, reg_dims=8, device=None, seed=0,
                  pos_thresh=0.6, with_targets=False, data_mean=None, precision="f32",
-                 strided=False, augment=None, paste=None, fused_loss=False, split_mma=True, split_strided=False):
+                 strided=False, augment=None, paste=None, fused_loss=False, split_mma=True, split_strided=False,
+                 split_train=False):
         """``augment``: an ``augment.AugmentConfig`` -- ``train_forward_backward(..., augment_rng=rng)`` then augments
         the points and the boxes on the device before the voxelizer and the assigner (needs ``with_targets``).
         ``paste``: ``(augment.GtBank, augment.PasteConfig)`` -- ground-truth sampling before that augmentation, so
@@ -47,10 +48,18 @@ class PillarPipeline:
         convolutions of up2 and up3 (``PPUpBlock.split_mma_up``) run split-fp16 MFMA kernels of their own
         (csrc/pp_conv_s2_split.hip, csrc/pp_convt_split.hip) instead of MIOpen's convolutions and an epilogue pass:
         with it the f32 backbone makes no MIOpen 3x3 call.  Independent of ``split_mma``; the same window.
+        ``split_train``: with ``with_targets`` and ``precision="f32"`` only (else a ``ValueError``): in train() the
+        stride-1 layers of down1, down2 and down3 (``PPDownBlock.split_train``) run their forward conv and their data
+        gradient on the split-fp16 MFMA kernel and their ReLU -> BatchNorm tail channels-last
+        (include/pp_conv_train.h) instead of MIOpen's NCHW f32 convolutions; the weight gradient stays MIOpen's.
+        Window: forward activations with |x| >= 65520 give NaN.  A stride-1 layer's input is always a BatchNorm
+        output, ``optim.FusedAdam(skip_nonfinite=True)`` drops such a step, and the gradients are rescaled per tensor
+        by a power of two and have no window.  eval() is untouched.
         ``fused_loss``: ``train_forward_backward`` computes the loss and its gradients with ``loss.FusedPPLoss`` (three
         HIP launches, no host wait) instead of ``PPLoss``."""
         check_inference_precision(precision, strided)      # before anything is built
         self.check_split_strided(split_strided, precision, with_targets)
+        self.check_split_train(split_train, precision, with_targets)
         self.check_paste_argument(paste, augment)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.vox_cfg = vox_cfg
@@ -78,6 +87,10 @@ class PillarPipeline:
                 blk.split_mma_s2 = True
             for blk in (bb.up2, bb.up3):
                 blk.split_mma_up = True
+        # ... and, on request, the training step's stride-1 convs (forward and data gradient) on the split-fp16 kernel
+        if split_train:
+            for blk in (self.model.backbone.down1, self.model.backbone.down2, self.model.backbone.down3):
+                blk.split_train = True
         self.loss = FusedPPLoss(return_p=False) if fused_loss else PPLoss()
         self.assigner = None
         if with_targets:
@@ -113,6 +126,17 @@ class PillarPipeline:
             # an explicit request, unlike the default split_mma, which a training pipeline quietly leaves off
             raise ValueError("split_strided=True is for inference pipelines: nothing bounds a training pipeline's "
                              "activations between optimizer steps, and the kernels' window ends at |x| < 65520")
+
+    @staticmethod
+    def check_split_train(split_train, precision, with_targets):
+        """The constructor's check of ``split_train``, before any device is touched."""
+        if not split_train:
+            return
+        if not with_targets:
+            raise ValueError("split_train=True needs with_targets=True: it switches the training step's convolutions")
+        if precision != "f32":
+            raise ValueError(f"split_train=True goes with precision \"f32\" only, not {precision!r}: the fp16 modes "
+                             "change the inference path of the same blocks")
 
     @staticmethod
     def check_paste_argument(paste, augment):

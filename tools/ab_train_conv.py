@@ -1,0 +1,103 @@
+"""Dev tool: ``train_forward_backward`` with ``split_train`` off and on (include/pp_conv_train.h: the 13 stride-1
+layers of down1-3 on the split-fp16 kernel forward and data gradient, channels-last ReLU -> BatchNorm tail), by the
+protocol of profiles/r24/NOTES.md: two pipelines with the same weights in one process, 4 warm-up steps each, then three
+alternating runs of 10 steps at B = 4, 60 000 points per sweep, 500x500 grid, 40 boxes per sample; an event pair
+(device ms) and a host clock (host ms: first call to the return of the last, no synchronise) around each run.  Prints
+one JSON line, and the two legs' loss scalars and largest gradient difference for orientation.
+
+usage: ab_train_conv.py [rounds] [steps per run]         (default 3 x 10)
+       ab_train_conv.py trace off|on [steps]             (default 10; one leg alone, to run under a kernel trace)"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from pp_amd import synth  # noqa: E402
+from pp_amd.pipeline import PillarPipeline  # noqa: E402
+from pp_amd.voxelizer import VoxelConfig  # noqa: E402
+
+B, WARM = 4, 4
+dev = torch.device("cuda", 0)
+cfg = VoxelConfig.square(50.0, 0.2, 12000, 100)
+
+
+def make(split):
+    pipe = PillarPipeline(cfg, device=dev, seed=0, with_targets=True, fused_loss=True, split_train=split)
+    pipe.model.train()
+    return pipe
+
+
+pts = torch.from_numpy(np.stack([synth.lidar_like(60000, 50.0, s) for s in range(B)])).to(dev)
+
+
+def stepper(pipe):
+    gts = [pipe.upload_ground_truth(synth.gt_boxes(40, cfg.canvas_height, s)) for s in range(B)]
+
+    def step():
+        pipe.model.zero_grad(set_to_none=True)
+        return pipe.train_forward_backward(pts, gts)
+    return step
+
+
+def run(step, n):
+    """(device ms, host ms) per step of n back-to-back steps."""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    a.record()
+    for _ in range(n):
+        step()
+    b.record()
+    host = (time.perf_counter() - t) * 1e3 / n
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / n, host
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "trace":
+    step = stepper(make(sys.argv[2] == "on"))
+    for _ in range(WARM + (int(sys.argv[3]) if len(sys.argv) > 3 else 10)):
+        step()
+    torch.cuda.synchronize()
+    sys.exit(0)
+
+rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 3
+steps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
+pipes = {"off": make(False), "on": make(True)}
+pipes["on"].model.load_state_dict(pipes["off"].model.state_dict())          # the same weights (the same seed made them)
+steppers = {k: stepper(p) for k, p in pipes.items()}
+for k, step in steppers.items():
+    for _ in range(WARM):
+        step()
+    torch.cuda.synchronize()
+legs = {k: {"device_ms": [], "host_ms": []} for k in pipes}
+for r in range(rounds):
+    for k in (("on", "off") if r % 2 == 0 else ("off", "on")):
+        d, h = run(steppers[k], steps)
+        legs[k]["device_ms"].append(d)
+        legs[k]["host_ms"].append(h)
+res = {k: {**v, "device_median": float(np.median(v["device_ms"])),
+           "device_spread": max(v["device_ms"]) - min(v["device_ms"]),
+           "host_median": float(np.median(v["host_ms"]))} for k, v in legs.items()}
+res["margin_ms"] = min(legs["off"]["device_ms"]) - max(legs["on"]["device_ms"])     # > 0: every on run ahead of every off run
+res["spread_ms"] = max(res["off"]["device_spread"], res["on"]["device_spread"])
+print(json.dumps({"ab_train_conv": res}))
+
+# orientation: one more step each from the same running statistics is not comparable bit for bit (each leg has updated
+# its own), so compare the scalars and the gradients' scale only
+out = {}
+for k, step in steppers.items():
+    losses = step()
+    torch.cuda.synchronize()
+    out[k] = ([float(v) for v in losses], {n: p.grad.detach().clone() for n, p in pipes[k].model.named_parameters()})
+diffs = {n: float((out["on"][1][n] - g).abs().max()) / max(float(g.abs().max()), 1e-30) for n, g in out["off"][1].items()}
+# a conv bias ahead of a training-mode BatchNorm has a zero gradient but for rounding: those tensors are listed apart
+noise = {n: d for n, d in diffs.items() if n.endswith(".bias") and (".block." in n or "conv2d_t" in n or "conv1" in n)}
+rest = {n: d for n, d in diffs.items() if n not in noise}
+worst = max(rest, key=rest.get)
+print(json.dumps({"losses_off": out["off"][0], "losses_on": out["on"][0],
+                  "worst_grad_diff_over_its_max": [worst, rest[worst]],
+                  "worst_among_biases_ahead_of_a_batchnorm": max(noise.values()) if noise else None}))
