@@ -30,11 +30,13 @@ I32 = ctypes.c_int32
 class Out:
     """One output of a call as it lies in memory.  ``align``: the alignment in bytes the header demands of the
     pointer (0: none -- the GPU tests then break 16-byte alignment by ``offset_elems`` elements).  ``zero_on_entry``:
-    the header wants it all zero before the call."""
+    the header wants it all zero before the call.  ``guard_bytes``: the least size of the guard band on either side
+    (0: the default of tests/abi_contract_run.py, 4 KiB or one innermost row)."""
 
-    def __init__(self, shape, dtype, align=16, offset_elems=0, zero_on_entry=False):
+    def __init__(self, shape, dtype, align=16, offset_elems=0, zero_on_entry=False, guard_bytes=0):
         self.shape, self.dtype = tuple(int(v) for v in shape), np.dtype(dtype)
         self.align, self.offset_elems, self.zero_on_entry = int(align), int(offset_elems), bool(zero_on_entry)
+        self.guard_bytes = int(guard_bytes)
         assert self.align or self.offset_elems, "an output without an alignment rule is tested off 16 bytes"
 
     @property
@@ -1021,7 +1023,8 @@ add("pp_conv3x3_s2_pillars_nhwc_dev", "canvas37x41", stem_case(37, 41))
 # ------------------------------------------------------------------------------------------------ stream order only
 # The entry points below have sentinel-filled destinations in tests of their own (tests/test_gpu_epilogue_abi.py,
 # tests/test_gpu_bn_train_abi.py, the channel-slice tests of the conv and head kernels): one smallest case each, for
-# tests/test_gpu_abi_stream_order.py.
+# tests/test_gpu_abi_stream_order.py.  The four conv kernels have an edge shape each, under both checks and with guards
+# in the pixel direction, in tests/conv_contract_cases.py.
 def subtract_mean_case(decoy):
     elems = 1021                                                  # the scalar path
     rng = np.random.default_rng(21 + decoy)
@@ -1099,6 +1102,13 @@ add("pp_bias_relu_bn_dev", "1x7x1003", epilogue_case(False), stream_only=True)
 add("pp_bias_relu_bn_nhwc_dev", "5x12", epilogue_case(True), stream_only=True)
 
 
+def bn_train_check(got, want):
+    """compare()'s bound of tests/test_gpu_bn_train_abi.py without PyTorch's own f32 error: e <= 1e-5 of max|ref|."""
+    for k, r in want.items():
+        scale = max(float(np.abs(r).max()), 1e-30)
+        assert np.isfinite(got[k]).all() and np.abs(got[k] - r).max() / scale <= 1e-5, k
+
+
 def bn_train_case(direction):
     def builder(decoy):
         import test_gpu_bn_train_abi as BN
@@ -1108,11 +1118,7 @@ def bn_train_case(direction):
         prm = BN._params(rng, C)
         z, dy = BN._well_conditioned(rng, shape)
         ref = BN.bn_train_ref(z, prm["bias"], prm["gamma"], prm["beta"], BN.EPS, BN.MOMENTUM, prm["rm"], prm["rv"], dy)
-
-        def check(got, want):            # compare()'s bound without PyTorch's own f32 error: e <= 1e-5 of max|ref|
-            for k, r in want.items():
-                scale = max(float(np.abs(r).max()), 1e-30)
-                assert np.isfinite(got[k]).all() and np.abs(got[k] - r).max() / scale <= 1e-5, k
+        check = bn_train_check
         if direction == "fwd":
             inputs = {"z": z, "bias": prm["bias"], "gamma": prm["gamma"], "beta": prm["beta"], "rm": prm["rm"], "rv": prm["rv"]}
             outputs = {"y": Out(shape, np.float32, align=4), "mean": Out((C,), np.float32, align=4),

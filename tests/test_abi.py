@@ -10,8 +10,9 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def declared_functions():
-    text = open(os.path.join(ROOT, "include", "pp_hip.h")).read()
+def declared_functions(header="pp_hip.h"):
+    """The pp_* functions that include/<header> declares, sorted."""
+    text = open(os.path.join(ROOT, "include", header)).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(pp_[a-z0-9_]+)\s*\(", text)))
 

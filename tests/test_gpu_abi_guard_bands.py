@@ -18,8 +18,11 @@ the same bits: the call does not depend on stale contents.  (Before it, a zero-o
 in/out input restored -- the header's own preconditions.)
 
 The network-side entry points have sentinel-filled destinations in tests/test_gpu_epilogue_abi.py,
-tests/test_gpu_bn_train_abi.py and the channel-slice tests of the conv and head kernels; their cases are in the table
-for tests/test_gpu_abi_stream_order.py only.
+tests/test_gpu_bn_train_abi.py and the head kernel's tests; their cases are in the table for
+tests/test_gpu_abi_stream_order.py only.  The conv kernels' channel-slice tests prefill neighbouring CHANNELS of the
+same tensor and cannot see a store in front of pixel 0 or behind the last pixel: the conv entry points run under this
+module's test in tests/test_gpu_conv_contract.py, on the cases of tests/conv_contract_cases.py, with guards that reach
+a row and a tile of pixels and with ``guard_inputs``.
 
 Wall time of the module on an MI355X: 4 s for its 198 cases; the slowest takes 0.4 s."""
 import numpy as np
@@ -47,12 +50,13 @@ def check_guards(placed, state, when):
 
 
 @pytest.mark.parametrize("case", T.guard_cases(), ids=lambda c: c.id)
-def test_writes_only_what_the_header_says(gpu, oracle, case):
+def test_writes_only_what_the_header_says(gpu, oracle, case, guard_inputs=False):
+    """``guard_inputs`` (tests/test_gpu_conv_contract.py): every float input between two bands of the NaN sentinel."""
     import torch
     A = Abi(gpu)
     built = case.build(False)
     want = built.expected(oracle)
-    placed = Placed(gpu, built)
+    placed = Placed(gpu, built, guard_inputs=guard_inputs)
     placed.call(A.L, A.h, A.stream)
     torch.cuda.synchronize()
     first = placed.read_outputs()
@@ -83,6 +87,7 @@ def test_writes_only_what_the_header_says(gpu, oracle, case):
     torch.cuda.synchronize()
     second = placed.read_outputs()
     check_guards(placed, second, "second call")
+    assert not placed.broken_input_guards(), f"wrote next to the inputs {placed.broken_input_guards()}"
     for k in built.outputs:
         assert np.array_equal(T.bits(second[k][1]), T.bits(first[k][1])), f"{k}: a second call gave other bits"
     again = placed.read_inputs()

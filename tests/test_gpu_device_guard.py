@@ -6,6 +6,9 @@ point per source file, at its smallest legal shape; the values are dyadic, so th
 and of the torch expression they are compared with is exact and the comparison is for equality.  The one value
 that is not dyadic, invstd = 1/sqrt(eps) of the training BatchNorm, is held to 1e-6 relative: a handful of f32
 roundings of 2^-24 each.
+
+test_first_case_of_every_entry_point does the same generically, for every device entry point that has a case in one
+of the three ABI case tables, at the case's own criterion.
 """
 import ctypes
 
@@ -158,3 +161,39 @@ def test_ctx_set_timing(env):          # pp_runtime.hip
     env.ok(env.L.pp_ctx_set_timing, env.h, 1)
     env.ok(env.L.pp_ctx_set_timing, env.h, 0)
     env.rejected(env.L.pp_ctx_set_timing, env.h, -1)
+
+
+def _first_cases():
+    """The first case of every entry point of the three ABI case tables."""
+    import abi_contract_cases as T
+    import adam_contract_cases as AC
+    import conv_contract_cases as CC
+    seen, out = set(), []
+    for c in T.CASES + AC.CASES + CC.CASES:
+        if c.entry not in seen:
+            seen.add(c.entry)
+            out.append(c)
+    return out
+
+
+@pytest.mark.parametrize("case", _first_cases(), ids=lambda c: c.id)
+def test_first_case_of_every_entry_point(env, oracle, case):
+    """Every device entry point that has a case in tests/abi_contract_cases.py, tests/adam_contract_cases.py or
+    tests/conv_contract_cases.py, generically: the thread on device 0, the context, the stream and every buffer on
+    device 1.  The thread is back on device 0 when the call returns, and the outputs pass the case's criterion."""
+    from abi_contract_run import Placed
+    torch = env.torch
+    built = case.build(False)
+    want = built.expected(oracle)
+    placed = Placed(env.dev, built)
+    torch.cuda.synchronize(env.dev)
+    assert torch.cuda.current_device() == 0
+    placed.call(env.L, env.h, env.stream)
+    assert torch.cuda.current_device() == 0, f"{case.id} left the thread on another device"
+    torch.cuda.synchronize(env.dev)
+    assert torch.cuda.current_device() == 0
+    got = {k: v[1] for k, v in placed.read_outputs().items() if k in built.outputs}
+    after = placed.read_inputs()
+    for k in built.inout:
+        got[k] = after[k]
+    built.check(got, want)
