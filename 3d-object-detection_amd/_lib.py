@@ -12,12 +12,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("PP_HIP_LIB") or os.path.join(_HERE, "libpp_hip.so")
 SOURCES = [os.path.join(_HERE, "csrc", f)
-           for f in ("pp_runtime.hip", "pp_voxelize.hip", "pp_iou.hip", "pp_ingest.hip", "pp_decode.hip", "pp_epilogue.hip", "pp_pfn.hip", "pp_pfn_train.hip", "pp_bn_train.hip", "pp_bn_train_nhwc.hip", "pp_eval.hip", "pp_wino.hip", "pp_conv_f16.hip", "pp_convt_f16.hip", "pp_conv_s2_f16.hip", "pp_conv_split.hip", "pp_conv_s2_split.hip", "pp_convt_split.hip", "pp_conv_train.hip", "pp_stem.hip", "pp_head.hip", "pp_augment.hip", "pp_paste.hip", "pp_loss.hip", "pp_optim.hip")]
+           for f in ("pp_runtime.hip", "pp_voxelize.hip", "pp_iou.hip", "pp_ingest.hip", "pp_decode.hip", "pp_epilogue.hip", "pp_pfn.hip", "pp_pfn_train.hip", "pp_bn_train.hip", "pp_bn_train_nhwc.hip", "pp_eval.hip", "pp_wino.hip", "pp_conv_f16.hip", "pp_convt_f16.hip", "pp_conv_s2_f16.hip", "pp_conv_split.hip", "pp_conv_s2_split.hip", "pp_convt_split.hip", "pp_conv_train.hip", "pp_conv_wgrad.hip", "pp_stem.hip", "pp_head.hip", "pp_augment.hip", "pp_paste.hip", "pp_loss.hip", "pp_optim.hip")]
 HEADERS = [os.path.join(_HERE, "csrc", "pp_common.h"), os.path.join(_HERE, "csrc", "pp_conv_f16_tile.h"),
            os.path.join(_HERE, "csrc", "pp_conv_split_tile.h"),
            os.path.join(_HERE, "csrc", "pp_box_geom.h"),
            os.path.join(_ROOT, "include", "pp_hip.h"), os.path.join(_ROOT, "include", "pp_optim.h"),
-           os.path.join(_ROOT, "include", "pp_conv_split.h"), os.path.join(_ROOT, "include", "pp_conv_train.h")]
+           os.path.join(_ROOT, "include", "pp_conv_split.h"), os.path.join(_ROOT, "include", "pp_conv_train.h"),
+           os.path.join(_ROOT, "include", "train", "pp_conv_wgrad.h")]
 
 PP_OK, PP_ERR_INDEX, PP_ERR_VALUE, PP_ERR_WINDING = 0, -2, -3, -4
 PP_ERR_NOMEM, PP_ERR_HIP, PP_ERR_INTERNAL = -5, -6, -7
@@ -45,6 +46,8 @@ SPLIT_STRIDED_EXPORTS = ["pp_conv3x3_s2_split_nhwc_dev", "pp_convt3x3_split_nhwc
 # the split-fp16 training convs and their channels-last ReLU -> BatchNorm tail: declared in include/pp_conv_train.h
 TRAIN_CONV_EXPORTS = ["pp_conv3x3_split_bare_nhwc_dev", "pp_pow2_scale_dev", "pp_split_pack_dev",
                       "pp_relu_bn_train_fwd_nhwc_dev", "pp_relu_bn_train_bwd_nhwc_dev"]
+# the split-fp16 weight gradient of those convs: declared in include/train/pp_conv_wgrad.h, a header of its own
+WGRAD_EXPORTS = ["pp_conv3x3_split_wgrad_workspace_bytes", "pp_conv3x3_split_wgrad_nhwc_dev"]
 
 
 class VoxelParams(ctypes.Structure):
@@ -323,6 +326,10 @@ def _load(path):
     L.pp_relu_bn_train_bwd_nhwc_dev.argtypes = [vp, vp, vp, vp, vp, i64, c_int, i64, vp, vp, vp, vp, vp, vp, vp]
     for name in TRAIN_CONV_EXPORTS:
         getattr(L, name).restype = c_int
+    L.pp_conv3x3_split_wgrad_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    L.pp_conv3x3_split_wgrad_workspace_bytes.restype = i64
+    L.pp_conv3x3_split_wgrad_nhwc_dev.argtypes = [vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, vp, vp, i64, vp]
+    L.pp_conv3x3_split_wgrad_nhwc_dev.restype = c_int
     L.pp_ctx_set_timing.argtypes = [vp, c_int]
     L.pp_ctx_read_emit_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), c_int,
                                       ctypes.POINTER(c_int)]

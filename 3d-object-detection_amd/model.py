@@ -235,6 +235,28 @@ def _pow2_scale(x):
     return scale
 
 
+def _wgrad_split(x, dz, dz_scale, fused):
+    """pp_conv3x3_split_wgrad_nhwc_dev (include/train/pp_conv_wgrad.h): the weight gradient [Cout,Cin,3,3] of the
+    stride-1 3x3 conv from its channels-last input ``x`` and output gradient ``dz``, as they lie.  ``dz_scale``:
+    ``_pow2_scale(dz)``.  ``fused``: the layer's ``_FusedConv``, which keeps the split-K workspace."""
+    B, C, H, W = x.shape
+    cout = dz.shape[1]
+    nbytes = _lib.lib().pp_conv3x3_split_wgrad_workspace_bytes(B, H, W, C, cout)
+    if nbytes < 0:
+        raise ValueError(f"pp_conv3x3_split_wgrad_nhwc_dev does not take x {tuple(x.shape)}, dz {tuple(dz.shape)}")
+    ws = fused.wgrad_workspace(nbytes, x.device)
+    dw = torch.empty((cout, C, 3, 3), dtype=torch.float32, device=x.device)
+    _call("pp_conv3x3_split_wgrad_nhwc_dev", x.device, _vp(x), _vp(dz), B, H, W, C, cout, _vp(dz_scale), _vp(ws),
+          nbytes, _vp(dw))
+    return dw
+
+
+def _wgrad_miopen(dz, x, weight):
+    """MIOpen's weight gradient of the stride-1, padding-1 3x3 conv: ``_Conv3x3Train``'s without ``split_wgrad``."""
+    return torch.ops.aten.convolution_backward(dz, x, weight, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1,
+                                               (False, True, False))[1]
+
+
 def _conv_s2_f16(x, w16, table, cout, out=None, channel_offset=0):
     """pp_conv3x3_s2_f16_nhwc_dev: Conv2d(3x3, padding 1, stride 2) + bias/ReLU/BatchNorm of ``x`` (NHWC) with fp16
     operands (``w16`` from ``_f16_filter``) and f32 accumulation, into a new channels-last tensor or into channels
@@ -405,6 +427,7 @@ class _FusedConv:
     def __init__(self):
         self._table = _LayoutCache()
         self._packed = {}           # kind ("nhwc", "stem" or a ``_Kernel.cache``) -> _LayoutCache
+        self._wgrad_ws = None       # ``_wgrad_split``'s workspace
 
     def table(self, bias, bn):
         """[C,3] f32: conv bias, BatchNorm scale, BatchNorm shift."""
@@ -432,6 +455,13 @@ class _FusedConv:
         if cache is None:
             cache = self._packed["split_train"] = _LayoutCache()
         return cache.get((weight,), lambda: _split_pack(weight, cache._val))
+
+    def wgrad_workspace(self, nbytes, device):
+        """``_wgrad_split``'s workspace: allocated once and reused while the layer's shape, hence ``nbytes``, holds."""
+        ws = self._wgrad_ws
+        if ws is None or ws.device != device or ws.numel() != nbytes:
+            ws = self._wgrad_ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        return ws
 
     def __call__(self, module, conv, bn, x, out=None, channel_offset=0, transposed=False, defer=False):
         """``bn(relu(conv(x)))`` into a new tensor, or into channels [channel_offset, +Cout) of ``out``: the first
@@ -598,14 +628,17 @@ class _Conv3x3Train(torch.autograd.Function):
     gradient (include/pp_conv_train.h): ``z = conv(x, weight)`` with ``x`` channels-last; the layer's bias and its
     gradient stay with ``_relu_bn(..., conv_bias=)``.  The data gradient is the same conv on ``dz`` with the weight's
     first two axes exchanged and its taps flipped, ``dz`` rescaled by a power of two of its own (``_pow2_scale``: the
-    split arithmetic resolves 2^-35 absolutely, which gradients fall under).  The weight gradient is MIOpen's.
+    split arithmetic resolves 2^-35 absolutely, which gradients fall under).  The weight gradient is MIOpen's
+    (``_wgrad_miopen``) or, with ``split_wgrad``, the split-K kernel's on the saved ``x`` and on ``dz`` with the same
+    scale (``_wgrad_split``, include/train/pp_conv_wgrad.h).
     ``fused``: the layer's ``_FusedConv``, which keeps both packed operands per version of the weight."""
 
     @staticmethod
-    def forward(ctx, x, weight, fused):
+    def forward(ctx, x, weight, fused, split_wgrad=False):
         fwd, dgrad = fused.train_operands(weight)
         ctx.save_for_backward(x, weight)
         ctx.dgrad = dgrad
+        ctx.wgrad_fused = fused if split_wgrad else None
         return _conv_split_bare(x, fwd, weight.shape[0])
 
     @staticmethod
@@ -614,12 +647,15 @@ class _Conv3x3Train(torch.autograd.Function):
         if not _nhwc_f32(dz):
             dz = dz.float().contiguous(memory_format=torch.channels_last)
         dx = dw = None
+        split_wgrad = ctx.wgrad_fused is not None and ctx.needs_input_grad[1]
+        scale = _pow2_scale(dz) if ctx.needs_input_grad[0] or split_wgrad else None     # one for dx and dw
         if ctx.needs_input_grad[0]:
-            dx = _conv_split_bare(dz, ctx.dgrad, weight.shape[1], _pow2_scale(dz))
-        if ctx.needs_input_grad[1]:
-            dw = torch.ops.aten.convolution_backward(dz, x, weight, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1,
-                                                     (False, True, False))[1]
-        return dx, dw, None
+            dx = _conv_split_bare(dz, ctx.dgrad, weight.shape[1], scale)
+        if split_wgrad:
+            dw = _wgrad_split(x, dz, scale, ctx.wgrad_fused)
+        elif ctx.needs_input_grad[1]:
+            dw = _wgrad_miopen(dz, x, weight)
+        return dx, dw, None, None
 
 
 class PPFeatureNet(nn.Module):
@@ -780,6 +816,11 @@ class PPDownBlock(nn.Module):
         #: tail channels-last (``_Conv3x3Train``, include/pp_conv_train.h) instead of MIOpen's NCHW f32 convolutions;
         #: the weight gradient stays MIOpen's.  Forward activations with |x| >= 65520 give NaN
         self.split_train = False
+        #: opt-in, with ``split_train`` (``PillarPipeline(..., split_train=True, split_wgrad=True)``): those layers'
+        #: weight gradient on the split-fp16 MFMA pipe too, a deterministic split-K kernel on the channels-last
+        #: tensors as they lie (csrc/pp_conv_wgrad.hip, include/train/pp_conv_wgrad.h) instead of MIOpen's; without
+        #: ``split_train`` it does nothing
+        self.split_wgrad = False
         self._fused = [_FusedConv() for _ in range(num_layers)]
 
     def stem(self, feats, inds, h, w):
@@ -807,7 +848,8 @@ class PPDownBlock(nn.Module):
                 for i in range(len(self._fused)):
                     conv, bn = self.block[3 * i], self.block[3 * i + 2]
                     if split and i > 0:
-                        x = _relu_bn(_Conv3x3Train.apply(x, conv.weight, self._fused[i]), bn, conv_bias=conv.bias)
+                        x = _relu_bn(_Conv3x3Train.apply(x, conv.weight, self._fused[i], bool(self.split_wgrad)), bn,
+                                     conv_bias=conv.bias)
                         continue
                     x = _relu_bn(F.conv2d(x, conv.weight, None, conv.stride, conv.padding), bn,
                                  conv_bias=conv.bias)

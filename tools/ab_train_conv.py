@@ -1,12 +1,14 @@
 """Dev tool: ``train_forward_backward`` with ``split_train`` off and on (include/pp_conv_train.h: the 13 stride-1
-layers of down1-3 on the split-fp16 kernel forward and data gradient, channels-last ReLU -> BatchNorm tail), by the
-protocol of profiles/r24/NOTES.md: two pipelines with the same weights in one process, 4 warm-up steps each, then three
+layers of down1-3 on the split-fp16 kernel forward and data gradient, channels-last ReLU -> BatchNorm tail), and a
+third leg ``wgrad``: ``split_train`` with ``split_wgrad`` (include/train/pp_conv_wgrad.h: those layers' weight
+gradient on the split-K kernel too).  By the
+protocol of profiles/r24/NOTES.md: the pipelines with the same weights in one process, 4 warm-up steps each, then three
 alternating runs of 10 steps at B = 4, 60 000 points per sweep, 500x500 grid, 40 boxes per sample; an event pair
 (device ms) and a host clock (host ms: first call to the return of the last, no synchronise) around each run.  Prints
-one JSON line, and the two legs' loss scalars and largest gradient difference for orientation.
+one JSON line, and the legs' loss scalars and largest gradient differences from ``off`` for orientation.
 
 usage: ab_train_conv.py [rounds] [steps per run]         (default 3 x 10)
-       ab_train_conv.py trace off|on [steps]             (default 10; one leg alone, to run under a kernel trace)"""
+       ab_train_conv.py trace off|on|wgrad [steps]            (default 10; one leg alone, to run under a kernel trace)"""
 import json
 import os
 import sys
@@ -25,8 +27,9 @@ dev = torch.device("cuda", 0)
 cfg = VoxelConfig.square(50.0, 0.2, 12000, 100)
 
 
-def make(split):
-    pipe = PillarPipeline(cfg, device=dev, seed=0, with_targets=True, fused_loss=True, split_train=split)
+def make(leg):
+    pipe = PillarPipeline(cfg, device=dev, seed=0, with_targets=True, fused_loss=True, split_train=leg != "off",
+                          split_wgrad=leg == "wgrad")
     pipe.model.train()
     return pipe
 
@@ -58,7 +61,7 @@ def run(step, n):
 
 
 if len(sys.argv) > 1 and sys.argv[1] == "trace":
-    step = stepper(make(sys.argv[2] == "on"))
+    step = stepper(make(sys.argv[2]))
     for _ in range(WARM + (int(sys.argv[3]) if len(sys.argv) > 3 else 10)):
         step()
     torch.cuda.synchronize()
@@ -66,8 +69,9 @@ if len(sys.argv) > 1 and sys.argv[1] == "trace":
 
 rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
-pipes = {"off": make(False), "on": make(True)}
-pipes["on"].model.load_state_dict(pipes["off"].model.state_dict())          # the same weights (the same seed made them)
+pipes = {k: make(k) for k in ("off", "on", "wgrad")}
+for k in ("on", "wgrad"):
+    pipes[k].model.load_state_dict(pipes["off"].model.state_dict())         # the same weights (the same seed made them)
 steppers = {k: stepper(p) for k, p in pipes.items()}
 for k, step in steppers.items():
     for _ in range(WARM):
@@ -75,7 +79,7 @@ for k, step in steppers.items():
     torch.cuda.synchronize()
 legs = {k: {"device_ms": [], "host_ms": []} for k in pipes}
 for r in range(rounds):
-    for k in (("on", "off") if r % 2 == 0 else ("off", "on")):
+    for k in (("wgrad", "on", "off") if r % 2 == 0 else ("off", "on", "wgrad")):
         d, h = run(steppers[k], steps)
         legs[k]["device_ms"].append(d)
         legs[k]["host_ms"].append(h)
@@ -84,6 +88,9 @@ res = {k: {**v, "device_median": float(np.median(v["device_ms"])),
            "host_median": float(np.median(v["host_ms"]))} for k, v in legs.items()}
 res["margin_ms"] = min(legs["off"]["device_ms"]) - max(legs["on"]["device_ms"])     # > 0: every on run ahead of every off run
 res["spread_ms"] = max(res["off"]["device_spread"], res["on"]["device_spread"])
+# the same for split_wgrad against split_train alone: > spread: every wgrad run ahead of every on run by more than it
+res["wgrad_margin_ms"] = min(legs["on"]["device_ms"]) - max(legs["wgrad"]["device_ms"])
+res["wgrad_spread_ms"] = max(res["on"]["device_spread"], res["wgrad"]["device_spread"])
 print(json.dumps({"ab_train_conv": res}))
 
 # orientation: one more step each from the same running statistics is not comparable bit for bit (each leg has updated
@@ -93,11 +100,15 @@ for k, step in steppers.items():
     losses = step()
     torch.cuda.synchronize()
     out[k] = ([float(v) for v in losses], {n: p.grad.detach().clone() for n, p in pipes[k].model.named_parameters()})
-diffs = {n: float((out["on"][1][n] - g).abs().max()) / max(float(g.abs().max()), 1e-30) for n, g in out["off"][1].items()}
-# a conv bias ahead of a training-mode BatchNorm has a zero gradient but for rounding: those tensors are listed apart
-noise = {n: d for n, d in diffs.items() if n.endswith(".bias") and (".block." in n or "conv2d_t" in n or "conv1" in n)}
-rest = {n: d for n, d in diffs.items() if n not in noise}
-worst = max(rest, key=rest.get)
-print(json.dumps({"losses_off": out["off"][0], "losses_on": out["on"][0],
-                  "worst_grad_diff_over_its_max": [worst, rest[worst]],
-                  "worst_among_biases_ahead_of_a_batchnorm": max(noise.values()) if noise else None}))
+report = {"losses_" + k: v[0] for k, v in out.items()}
+for k in ("on", "wgrad"):
+    diffs = {n: float((out[k][1][n] - g).abs().max()) / max(float(g.abs().max()), 1e-30)
+             for n, g in out["off"][1].items()}
+    # a conv bias ahead of a training-mode BatchNorm has a zero gradient but for rounding: those tensors are listed apart
+    noise = {n: d for n, d in diffs.items()
+             if n.endswith(".bias") and (".block." in n or "conv2d_t" in n or "conv1" in n)}
+    rest = {n: d for n, d in diffs.items() if n not in noise}
+    worst = max(rest, key=rest.get)
+    report[k] = {"worst_grad_diff_over_its_max": [worst, rest[worst]],
+                 "worst_among_biases_ahead_of_a_batchnorm": max(noise.values()) if noise else None}
+print(json.dumps(report))
