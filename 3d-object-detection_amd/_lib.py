@@ -18,7 +18,8 @@ HEADERS = [os.path.join(_HERE, "csrc", "pp_common.h"), os.path.join(_HERE, "csrc
            os.path.join(_HERE, "csrc", "pp_box_geom.h"),
            os.path.join(_ROOT, "include", "pp_hip.h"), os.path.join(_ROOT, "include", "pp_optim.h"),
            os.path.join(_ROOT, "include", "pp_conv_split.h"), os.path.join(_ROOT, "include", "pp_conv_train.h"),
-           os.path.join(_ROOT, "include", "train", "pp_conv_wgrad.h")]
+           os.path.join(_ROOT, "include", "train", "pp_conv_wgrad.h"),
+           os.path.join(_ROOT, "include", "train", "pp_conv_s2_train.h")]
 
 PP_OK, PP_ERR_INDEX, PP_ERR_VALUE, PP_ERR_WINDING = 0, -2, -3, -4
 PP_ERR_NOMEM, PP_ERR_HIP, PP_ERR_INTERNAL = -5, -6, -7
@@ -48,6 +49,9 @@ TRAIN_CONV_EXPORTS = ["pp_conv3x3_split_bare_nhwc_dev", "pp_pow2_scale_dev", "pp
                       "pp_relu_bn_train_fwd_nhwc_dev", "pp_relu_bn_train_bwd_nhwc_dev"]
 # the split-fp16 weight gradient of those convs: declared in include/train/pp_conv_wgrad.h, a header of its own
 WGRAD_EXPORTS = ["pp_conv3x3_split_wgrad_workspace_bytes", "pp_conv3x3_split_wgrad_nhwc_dev"]
+# the training form of the stride-2 convs that open the down blocks: declared in include/train/pp_conv_s2_train.h
+TRAIN_S2_EXPORTS = ["pp_conv3x3_s2_split_bare_nhwc_dev", "pp_conv3x3_s2_split_dgrad_nhwc_dev", "pp_split_pack_s2_dev",
+                    "pp_conv3x3_s2_split_wgrad_workspace_bytes", "pp_conv3x3_s2_split_wgrad_nhwc_dev"]
 
 
 class VoxelParams(ctypes.Structure):
@@ -330,6 +334,15 @@ def _load(path):
     L.pp_conv3x3_split_wgrad_workspace_bytes.restype = i64
     L.pp_conv3x3_split_wgrad_nhwc_dev.argtypes = [vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, vp, vp, i64, vp]
     L.pp_conv3x3_split_wgrad_nhwc_dev.restype = c_int
+    L.pp_conv3x3_s2_split_bare_nhwc_dev.argtypes = L.pp_conv3x3_split_nhwc_dev.argtypes
+    L.pp_conv3x3_s2_split_dgrad_nhwc_dev.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, vp, c_int, c_int, c_int, vp,
+                                                     vp]
+    L.pp_split_pack_s2_dev.argtypes = L.pp_split_pack_dev.argtypes
+    L.pp_conv3x3_s2_split_wgrad_workspace_bytes.argtypes = L.pp_conv3x3_split_wgrad_workspace_bytes.argtypes
+    L.pp_conv3x3_s2_split_wgrad_nhwc_dev.argtypes = L.pp_conv3x3_split_wgrad_nhwc_dev.argtypes
+    for name in TRAIN_S2_EXPORTS:
+        getattr(L, name).restype = c_int
+    L.pp_conv3x3_s2_split_wgrad_workspace_bytes.restype = i64
     L.pp_ctx_set_timing.argtypes = [vp, c_int]
     L.pp_ctx_read_emit_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), c_int,
                                       ctypes.POINTER(c_int)]

@@ -209,10 +209,12 @@ struct Epilogue {
 };
 
 // The argument checks the entry points share; fn names the entry point in the message.  No HIP call.
+// params_optional: the bare forms have no table; prm is then their optional scale pair and may be NULL.
 inline int check_conv_f16_args(const char *fn, const pp_ctx_t *ctx, const float *x, const void *w,
                                const float *prm, const float *y, int batch, int height, int width,
-                               int in_channels, int out_channels, int64_t y_channels, int64_t y_channel_offset) {
-  if (!ctx || !x || !w || !prm || !y) {
+                               int in_channels, int out_channels, int64_t y_channels, int64_t y_channel_offset,
+                               bool params_optional = false) {
+  if (!ctx || !x || !w || (!prm && !params_optional) || !y) {
     set_error("%s: NULL argument", fn);
     return PP_ERR_VALUE;
   }

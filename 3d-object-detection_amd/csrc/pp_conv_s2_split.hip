@@ -22,6 +22,7 @@
 
 #include "pp_conv_split.h"
 #include "pp_conv_split_tile.h"
+#include "train/pp_conv_s2_train.h"
 
 namespace pp {
 
@@ -50,6 +51,9 @@ static_assert(Geo::kBufBytes == 75008 && 2 * Geo::kBufBytes <= 160 * 1024, "the 
 // prm [Cout][3] (bias, scale, shift).
 // y   pixel p of [B][Ho][Wo], channel c at y[p*y_stride + c] (y already offset to the channel slice).
 // grid: x = B * ceil(Ho/4) * ceil(Wo/32), y = Cout/64.
+// BARE (pp_conv3x3_s2_split_bare_nhwc_dev, include/train/pp_conv_s2_train.h): y = v, no epilogue; prm is NULL or
+// {s, 1/s}, s a power of two: the stager multiplies x by s ahead of the split and the output is multiplied by 1/s.
+template <bool BARE>
 __global__ __launch_bounds__(256, 1) void k_conv3x3_s2_split(const float *__restrict__ x,
                                                              const uint4 *__restrict__ w,
                                                              const float *__restrict__ esc,
@@ -66,7 +70,13 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_s2_split(const float *__rest
   const int oy0 = by * G::kRows, ox0 = bx * kTw;
   const int co0 = blockIdx.y * kCo;
   const int nchunks = Cin / kKc;
-  Stager<G> stage(x, w, b, H, W, Cin, 2 * oy0 - 1, 2 * ox0 - 1, nchunks);
+  Stager<G, BARE> stage(x, w, b, H, W, Cin, 2 * oy0 - 1, 2 * ox0 - 1, nchunks);
+  float inv = 1.0f;
+  if constexpr (BARE)
+    if (prm) {
+      stage.xs = prm[0];
+      inv = prm[1];
+    }
 
   // ---- MFMA role, as in k_conv3x3_s2_f16: lane (r = lane&31, h = lane>>5) holds A[output pixel r of the
   // row][channels 8h..8h+7] and B[channels 8h..8h+7][cout r (+32 for the second column block)]; the lo plane of
@@ -109,7 +119,12 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_s2_split(const float *__rest
   // ox0 + (r&3) + 8(r>>2) + 4h of row oy0 + wave for accumulator register r
   const int co = co0 + l32;
   const float e0 = esc[co], e1 = esc[co + 32];
-  const Epilogue<2> ep(prm, co);
+  const auto ep = [&] {
+    if constexpr (BARE)
+      return Unscale{inv};
+    else
+      return Epilogue<2>(prm, co);
+  }();
   const int oy = oy0 + wave;
   if (oy >= Ho) return;                  // partial edge tiles: nothing past Ho or Wo is stored
   float *yrow = y + (((int64_t)b * Ho + oy) * Wo + ox0) * y_stride + co;
@@ -118,8 +133,8 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_s2_split(const float *__rest
     const int px = (r & 3) + 8 * (r >> 2) + 4 * h;
     if (ox0 + px < Wo) {
       float *yp = yrow + px * y_stride;
-      yp[0] = split_output(m0[r], c0[r], e0, ep, 0);
-      yp[32] = split_output(m1[r], c1[r], e1, ep, 1);
+      yp[0] = split_output<BARE>(m0[r], c0[r], e0, ep, 0);
+      yp[32] = split_output<BARE>(m1[r], c1[r], e1, ep, 1);
     }
   }
 }
@@ -128,13 +143,14 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_s2_split(const float *__rest
 
 using namespace pp;
 
-extern "C" int pp_conv3x3_s2_split_nhwc_dev(pp_ctx_t *ctx, void *stream_, const float *x_dev, int batch,
-                                            int height, int width, int in_channels, const void *w_split_dev,
-                                            int out_channels, const float *params_dev, float *y_dev,
-                                            int64_t y_channels, int64_t y_channel_offset) {
-  const char *fn = "pp_conv3x3_s2_split_nhwc_dev";
-  if (int rc = check_conv_f16_args(fn, ctx, x_dev, w_split_dev, params_dev, y_dev, batch, height, width,
-                                   in_channels, out_channels, y_channels, y_channel_offset))
+// Both entry points: the shared checks, the grid, the launch.  prm: the epilogue table, or BARE's x_scale_dev.
+template <bool BARE>
+static int conv3x3_s2_split(const char *fn, pp_ctx_t *ctx, void *stream_, const float *x_dev, int batch, int height,
+                            int width, int in_channels, const void *w_split_dev, int out_channels, const float *prm,
+                            float *y_dev, int64_t y_channels, int64_t y_channel_offset) {
+  // the bare form has no table: its checks are the shared ones minus the params pointer
+  if (int rc = check_conv_f16_args(fn, ctx, x_dev, w_split_dev, prm, y_dev, batch, height, width, in_channels,
+                                   out_channels, y_channels, y_channel_offset, BARE))
     return rc;
   const int64_t ho = ((int64_t)height + 1) / 2, wo = ((int64_t)width + 1) / 2;
   const int64_t tiles_x = (wo + kTw - 1) / kTw, tiles_y = (ho + Geo::kRows - 1) / Geo::kRows;
@@ -147,9 +163,31 @@ extern "C" int pp_conv3x3_s2_split_nhwc_dev(pp_ctx_t *ctx, void *stream_, const 
   }
   const float *esc = split_scales(w_split_dev, out_channels, in_channels);
   return launch_on_device(ctx, "k_conv3x3_s2_split", [&] {
-    hipLaunchKernelGGL(k_conv3x3_s2_split, dim3((unsigned)blocks, (unsigned)(out_channels / 64)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream_), x_dev, static_cast<const uint4 *>(w_split_dev), esc,
-                       params_dev, y_dev + y_channel_offset, height, width, in_channels, (int)ho, (int)wo,
-                       y_channels, (int)tiles_x, (int)tiles_y);
+    hipLaunchKernelGGL(k_conv3x3_s2_split<BARE>, dim3((unsigned)blocks, (unsigned)(out_channels / 64)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream_), x_dev, static_cast<const uint4 *>(w_split_dev), esc, prm,
+                       y_dev + y_channel_offset, height, width, in_channels, (int)ho, (int)wo, y_channels,
+                       (int)tiles_x, (int)tiles_y);
   });
+}
+
+extern "C" int pp_conv3x3_s2_split_nhwc_dev(pp_ctx_t *ctx, void *stream_, const float *x_dev, int batch,
+                                            int height, int width, int in_channels, const void *w_split_dev,
+                                            int out_channels, const float *params_dev, float *y_dev,
+                                            int64_t y_channels, int64_t y_channel_offset) {
+  return conv3x3_s2_split<false>("pp_conv3x3_s2_split_nhwc_dev", ctx, stream_, x_dev, batch, height, width,
+                                 in_channels, w_split_dev, out_channels, params_dev, y_dev, y_channels,
+                                 y_channel_offset);
+}
+
+extern "C" int pp_conv3x3_s2_split_bare_nhwc_dev(pp_ctx_t *ctx, void *stream_, const float *x_dev, int batch,
+                                                 int height, int width, int in_channels, const void *w_split_dev,
+                                                 int out_channels, const float *x_scale_dev, float *y_dev,
+                                                 int64_t y_channels, int64_t y_channel_offset) {
+  if (reinterpret_cast<uintptr_t>(x_scale_dev) & 3) {
+    set_error("pp_conv3x3_s2_split_bare_nhwc_dev: x_scale_dev is not 4-byte aligned");
+    return PP_ERR_VALUE;
+  }
+  return conv3x3_s2_split<true>("pp_conv3x3_s2_split_bare_nhwc_dev", ctx, stream_, x_dev, batch, height, width,
+                                in_channels, w_split_dev, out_channels, x_scale_dev, y_dev, y_channels,
+                                y_channel_offset);
 }

@@ -446,8 +446,8 @@ static int conv3x3_split(const char *fn, pp_ctx_t *ctx, void *stream_, const flo
                          int width, int in_channels, const void *w_split_dev, int out_channels, const float *prm,
                          float *y_dev, int64_t y_channels, int64_t y_channel_offset) {
   // the bare form has no table: its checks are the shared ones minus the params pointer
-  if (int rc = check_conv_f16_args(fn, ctx, x_dev, w_split_dev, BARE ? x_dev : prm, y_dev, batch, height, width,
-                                   in_channels, out_channels, y_channels, y_channel_offset))
+  if (int rc = check_conv_f16_args(fn, ctx, x_dev, w_split_dev, prm, y_dev, batch, height, width, in_channels,
+                                   out_channels, y_channels, y_channel_offset, BARE))
     return rc;
   const int64_t tiles_x = (width + kTw - 1) / kTw, tiles_y = (height + G::kRows - 1) / G::kRows;
   const int64_t groups = out_channels / 64, items = (int64_t)batch * tiles_x * tiles_y * groups;

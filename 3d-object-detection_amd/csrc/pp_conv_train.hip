@@ -11,6 +11,7 @@
 
 #include "pp_common.h"
 #include "pp_conv_train.h"
+#include "train/pp_conv_s2_train.h"
 
 namespace pp {
 
@@ -80,6 +81,9 @@ __global__ __launch_bounds__(kAmaxThreads) void k_pow2_scale(const unsigned *__r
 // operand), blocks [Co, Co + Ci) channel a of w2[a][b][kh][kw] = w[b][a][2-kh][2-kw] (the data gradient's operand:
 // the weight with its first two axes exchanged and its taps flipped).  _split_filter's arithmetic in f64; the casts to
 // fp16 go through f32, as torch's .half() of a double tensor does.
+// FLIP = false (pp_split_pack_s2_dev, include/train/pp_conv_s2_train.h): the data gradient's operand keeps the taps
+// as they lie, w2[a][b][kh][kw] = w[b][a][kh][kw]: the transposed conv's operand, model.py's _convt_split_filter(w).
+template <bool FLIP>
 __global__ __launch_bounds__(256) void k_split_pack(const float *__restrict__ w, int Co, int Ci,
                                                     _Float16 *__restrict__ fwd, _Float16 *__restrict__ dgrad) {
   __shared__ unsigned s_red[4];
@@ -90,7 +94,7 @@ __global__ __launch_bounds__(256) void k_split_pack(const float *__restrict__ w,
   const int n = nin * 9;
   auto src = [&](int idx) {                                   // idx = (input channel of the operand) * 9 + tap
     const int i = idx / 9, tap = idx - 9 * i;
-    return is_fwd ? w[((int64_t)c * Ci + i) * 9 + tap] : w[((int64_t)i * Ci + c) * 9 + (8 - tap)];
+    return is_fwd ? w[((int64_t)c * Ci + i) * 9 + tap] : w[((int64_t)i * Ci + c) * 9 + (FLIP ? 8 - tap : tap)];
   };
   unsigned mb = 0;
   for (int idx = threadIdx.x; idx < n; idx += 256) mb = max(mb, __float_as_uint(src(idx)) & 0x7fffffffu);
@@ -140,24 +144,37 @@ extern "C" int pp_pow2_scale_dev(pp_ctx_t *ctx, void *stream_, const float *x_de
   });
 }
 
-extern "C" int pp_split_pack_dev(pp_ctx_t *ctx, void *stream_, const float *w_dev, int out_channels, int in_channels,
-                                 void *fwd_dev, void *dgrad_dev) {
+// Both pack entry points: the checks and the launch
+template <bool FLIP>
+static int split_pack(const char *fn, pp_ctx_t *ctx, void *stream_, const float *w_dev, int out_channels,
+                      int in_channels, void *fwd_dev, void *dgrad_dev) {
   if (!ctx || !w_dev || !fwd_dev) {
-    set_error("pp_split_pack_dev: NULL argument");
+    set_error("%s: NULL argument", fn);
     return PP_ERR_VALUE;
   }
   if (out_channels < 64 || out_channels % 64 || in_channels < 64 || in_channels % 64 || out_channels > 16384 ||
       in_channels > 16384 ||
       ((reinterpret_cast<uintptr_t>(w_dev) & 3) |
        ((reinterpret_cast<uintptr_t>(fwd_dev) | reinterpret_cast<uintptr_t>(dgrad_dev)) & 15))) {
-    set_error("pp_split_pack_dev: need out_channels and in_channels multiples of 64 (at most 16384), 16-byte aligned "
-              "operands (out=%d in=%d)", out_channels, in_channels);
+    set_error("%s: need out_channels and in_channels multiples of 64 (at most 16384), 16-byte aligned "
+              "operands (out=%d in=%d)", fn, out_channels, in_channels);
     return PP_ERR_VALUE;
   }
   const unsigned blocks = (unsigned)out_channels + (dgrad_dev ? (unsigned)in_channels : 0u);
   return launch_on_device(ctx, "k_split_pack", [&] {
-    hipLaunchKernelGGL(k_split_pack, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream_), w_dev,
+    hipLaunchKernelGGL(k_split_pack<FLIP>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream_), w_dev,
                        out_channels, in_channels, static_cast<_Float16 *>(fwd_dev),
                        static_cast<_Float16 *>(dgrad_dev));
   });
+}
+
+extern "C" int pp_split_pack_dev(pp_ctx_t *ctx, void *stream_, const float *w_dev, int out_channels, int in_channels,
+                                 void *fwd_dev, void *dgrad_dev) {
+  return split_pack<true>("pp_split_pack_dev", ctx, stream_, w_dev, out_channels, in_channels, fwd_dev, dgrad_dev);
+}
+
+extern "C" int pp_split_pack_s2_dev(pp_ctx_t *ctx, void *stream_, const float *w_dev, int out_channels,
+                                    int in_channels, void *fwd_dev, void *dgrad_dev) {
+  return split_pack<false>("pp_split_pack_s2_dev", ctx, stream_, w_dev, out_channels, in_channels, fwd_dev,
+                           dgrad_dev);
 }

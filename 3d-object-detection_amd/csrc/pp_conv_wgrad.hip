@@ -21,6 +21,7 @@
 
 #include "pp_common.h"
 #include "train/pp_conv_wgrad.h"
+#include "train/pp_conv_s2_train.h"
 
 namespace pp {
 
@@ -202,6 +203,165 @@ __global__ __launch_bounds__(256) void k_conv3x3_wgrad_sum(const float *__restri
   dw[((int64_t)(cob * 64 + co) * Cin + cib * 64 + ci) * 9 + tap] = (float)acc;
 }
 
+// ---- the stride-2 form (include/train/pp_conv_s2_train.h): dz [B][Ho][Wo][Cout], Ho = (H+1)/2, Wo = (W+1)/2,
+//   dw[co][ci][ky][kx] = sum over pixels of dz[b][oy][ox][co] * x[b][2oy+ky-1][2ox+kx-1][ci].
+// The same operands, split, transposed reads, wave roles and output as k_conv3x3_wgrad; what differs is the geometry.
+// A partial is 16 rows x 32 columns of dz.  Its x row has 65 pixels (columns 2 xs - 1 .. 2 xs + 63) and is stored
+// de-interleaved: the 33 even halo columns in slots 0..32, the 32 odd ones in slots 33..64, so that the 8 consecutive
+// dz columns a lane reads meet 8 consecutive slots for every tap (kx = 0: slot j, kx = 1: slot 33 + j, kx = 2: slot
+// j + 1), 320 bytes apart as in the stride-1 kernel.  Left interleaved, consecutive dz columns would be 640 bytes = 32
+// banks (mod 64) apart and the 4 pixels of a transposed read would fall on two bank groups twice each.  The odd part
+// starts 64 bytes further on (16 banks), which by the bank arithmetic puts two neighbouring halo columns -- the two
+// pixels that the 32 lanes of one ds_write pass store, now a slot of each part -- on disjoint halves of the banks
+// (reasoned, not measured).
+// dz row oy meets x rows 2oy-1, 2oy, 2oy+1, and the ring advances two x rows per dz row: while row oy is multiplied,
+// x rows 2oy+2 and 2oy+3 are staged.  Even rows 2m live in two slots (m & 1), odd rows 2m+1 in four ((m & 3) + 2): the
+// five rows alive at a time never share one.  Three odd slots would do (two are read while a third is written); the
+// fourth, 20864 bytes that nothing else wants, buys a mask instead of a remainder by three per row.  6 x (65 pixels of 320 bytes + 64) + 2 x 32 x 320: 145664 bytes of LDS.
+
+namespace {
+
+constexpr int kS2Tw = 32;                          // dz columns of a partial
+constexpr int kS2Hw = 2 * kS2Tw + 1;               // pixels of an x row
+constexpr int kS2Odd = (kS2Tw + 1) * kPix + 64;    // byte offset of a row's first odd halo column
+constexpr int kS2XRow = kS2Hw * kPix + 64;
+constexpr int kS2DzRow = kS2Tw * kPix;
+constexpr int kS2XBytes = 6 * kS2XRow;
+constexpr int kS2LdsBytes = kS2XBytes + 2 * kS2DzRow;
+static_assert(kS2LdsBytes == 145664 && kS2LdsBytes <= 160 * 1024, "the LDS budget of the header");
+static_assert(kThreads == 48 * 16 && kS2Hw == 48 + 17 && kS2Tw <= 48, "the stager's three x items and one dz item");
+
+// the ring slot of x row `row` (row >= -2)
+__device__ __forceinline__ int s2_slot(int row) { return (row & 1) ? 2 + ((row >> 1) & 3) : ((row >> 1) & 1); }
+
+}  // namespace
+
+// grid: as k_conv3x3_wgrad's; partial = (b * bands + band) * segs + seg: dz rows [16 band, +16) and dz columns
+// [32 seg, +32) of sample b
+__global__ __launch_bounds__(kThreads) void k_conv3x3_s2_wgrad(const float *__restrict__ x,
+                                                              const float *__restrict__ dz, int H, int W, int Ho,
+                                                              int Wo, int Cin, int Cout, int bands, int segs,
+                                                              const float *__restrict__ dz_scale,
+                                                              float *__restrict__ ws) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[kS2LdsBytes];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nci = Cin >> 6, pairs = nci * (Cout >> 6);
+  const int pair = blockIdx.x % pairs, part = blockIdx.x / pairs;
+  const int cob = pair / nci, cib = pair - cob * nci;
+  const int seg = part % segs, band = part / segs % bands, b = part / segs / bands;
+  const int y0 = band * kRb, y1 = min(Ho, y0 + kRb), xs = seg * kS2Tw, xe = min(Wo, xs + kS2Tw);
+  const int segw = xe - xs, nsteps = (segw + 15) >> 4;
+  const float s = dz_scale ? dz_scale[0] : 1.0f, inv = dz_scale ? dz_scale[1] : 1.0f;
+  const float *xb = x + (int64_t)b * H * W * Cin + cib * 64;
+  const float *db = dz + (int64_t)b * Ho * Wo * Cout + cob * 64;
+
+  // the stager's items of this thread, 4 channels (4 (tid & 15) .. +3 of the block) of one pixel each; pos = tid >> 4
+  // in [0, 48).  Of the two x rows staged per dz row: halo column pos of either row (items 0 and 1: one offset, one
+  // LDS column), and for pos < 34 one of the 17 columns 48 .. 64 that are left, of the first row (pos < 17) or the
+  // second (item 2).  Halo column hx is image column 2 xs - 1 + hx.  The dz item (pos < 32): dz column xs + pos
+  const int pos = tid >> 4, ch = (tid & 15) * 4;
+  const bool sel2 = pos >= 17, ok2 = pos < 34;
+  const int hx2 = 48 + pos - (sel2 ? 17 : 0);
+  const int col01 = 2 * xs - 1 + pos, col2 = 2 * xs - 1 + hx2;
+  const bool cin01 = col01 >= 0 && col01 < W, cin2 = ok2 && col2 < W;
+  const int xoff01 = col01 * Cin + ch, xoff2 = col2 * Cin + ch;
+  const int xdst01 = (pos & 1) * kS2Odd + (pos >> 1) * kPix + ch * 2;
+  const int xdst2 = (hx2 & 1) * kS2Odd + (hx2 >> 1) * kPix + ch * 2;
+  const int doff = (xs + pos) * Cout + ch, ddst = pos * kPix + ch * 2;
+  const bool dok = pos < kS2Tw, din = dok && xs + pos < xe;
+  float4 rx[3], rd;
+  // a branch, not a select between the loaded value and a zero: the select becomes one between two addresses, the
+  // zero's in private memory
+  auto load4 = [](bool in, const float *p) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (in) v = *reinterpret_cast<const float4 *>(p);
+    return v;
+  };
+  // x rows row0 (even; only if `first`) and row0 + 1, zero outside the image, and dz row `drow` (a row of the
+  // partial), to registers
+  auto load_rows = [&](int row0, bool first, int drow) {
+    const bool in0 = first && row0 >= 0 && row0 < H, in1 = row0 + 1 >= 0 && row0 + 1 < H;
+    const int o0 = in0 ? row0 * W * Cin : 0, o1 = in1 ? (row0 + 1) * W * Cin : 0;
+    rx[0] = load4(in0 && cin01, xb + (o0 + xoff01));
+    rx[1] = load4(in1 && cin01, xb + (o1 + xoff01));
+    rx[2] = load4((sel2 ? in1 : in0) && cin2, xb + ((sel2 ? o1 : o0) + xoff2));
+    rd = load4(din, db + (drow * Wo * Cout + doff));
+  };
+  auto store_rows = [&](int row0, int drow) {
+    unsigned char *r0 = lds + s2_slot(row0) * kS2XRow, *r1 = lds + s2_slot(row0 + 1) * kS2XRow;
+    split_store(r0 + xdst01, rx[0], 1.0f);
+    split_store(r1 + xdst01, rx[1], 1.0f);
+    if (ok2) split_store((sel2 ? r1 : r0) + xdst2, rx[2], 1.0f);
+    if (dok) split_store(lds + kS2XBytes + (drow & 1) * kS2DzRow + ddst, rd, s);
+  };
+
+  // the reads of this lane: k_conv3x3_wgrad's
+  const int ky = wave >> 2, coh = wave >> 1 & 1, cih = wave & 1;
+  const int q = lane >> 2 & 3, p = lane & 3, c16 = lane >> 4 & 1, kh = lane >> 5;
+  const int aoff = (8 * kh + q) * kPix + (coh * 32 + c16 * 16 + 4 * p) * 2;
+  const int boff = (8 * kh + q) * kPix + (cih * 32 + c16 * 16 + 4 * p) * 2;
+  // the last step of a row where the partial's width is no multiple of 16: dz is zero past the edge, and x is made
+  // zero there too, so that a NaN of x stays with the taps that read it
+  const int nv = segw - 16 * (nsteps - 1);
+  const bool tail = nv < 16;
+  const int rem = nv - 8 * kh;                       // this lane's pixels of that step that are inside
+
+  f32x16 acc_main[3], acc_corr[3];
+#pragma unroll
+  for (int kx = 0; kx < 3; ++kx) acc_main[kx] = acc_corr[kx] = f32x16{};
+
+  // x rows 2 y0 - 1, 2 y0, 2 y0 + 1 and dz row y0
+  load_rows(2 * y0 - 2, false, y0);
+  store_rows(2 * y0 - 2, y0);
+  load_rows(2 * y0, true, y0);
+  store_rows(2 * y0, y0);
+  __syncthreads();
+
+#pragma unroll 1
+  for (int y = y0; y < y1; ++y) {
+    const bool more = y + 1 < y1;
+    if (more) load_rows(2 * y + 2, true, y + 1);
+    const unsigned char *xrow = lds + s2_slot(2 * y - 1 + ky) * kS2XRow + boff;
+    const unsigned char *drow = lds + kS2XBytes + (y & 1) * kS2DzRow + aoff;
+#pragma unroll 1
+    for (int st = 0; st < nsteps; ++st) {
+      const bool mask = tail && st == nsteps - 1;
+      const f16x8 ah = __builtin_bit_cast(f16x8, read_tr8(drow + st * 16 * kPix));
+      const f16x8 al = __builtin_bit_cast(f16x8, read_tr8(drow + st * 16 * kPix + kLo));
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const int col = kx == 1 ? kS2Odd : (kx >> 1) * kPix;    // halo column 2 j + kx: slot j, 33 + j, j + 1
+        u32x4 uh = read_tr8(xrow + st * 16 * kPix + col), ul = read_tr8(xrow + st * 16 * kPix + col + kLo);
+        if (mask) {
+#pragma unroll
+          for (int d = 0; d < 4; ++d) {
+            const unsigned m = (2 * d < rem ? 0xffffu : 0u) | (2 * d + 1 < rem ? 0xffff0000u : 0u);
+            uh[d] &= m;
+            ul[d] &= m;
+          }
+        }
+        const f16x8 bh = __builtin_bit_cast(f16x8, uh), bl = __builtin_bit_cast(f16x8, ul);
+        acc_main[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc_main[kx], 0, 0, 0);
+        acc_corr[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc_corr[kx], 0, 0, 0);
+        acc_corr[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc_corr[kx], 0, 0, 0);
+      }
+    }
+    if (more) store_rows(2 * y + 2, y + 1);
+    __syncthreads();
+  }
+
+  // accumulator i of lane l: output channel (i & 3) + 8 (i >> 2) + 4 (l >> 5), input channel l & 31 of the tile
+  float *out = ws + ((int64_t)pair * (gridDim.x / pairs) + part) * kPartFloats;
+#pragma unroll
+  for (int kx = 0; kx < 3; ++kx) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int co = coh * 32 + (i & 3) + 8 * (i >> 2) + 4 * kh, ci = cih * 32 + (lane & 31);
+      out[((ky * 3 + kx) * 64 + co) * 64 + ci] = (acc_main[kx][i] + acc_corr[kx][i] * (1.0f / 2048.0f)) * inv;
+    }
+  }
+}
+
 namespace {
 
 // the partials of one channel block and the channel blocks; false for arguments the entry point refuses
@@ -274,6 +434,72 @@ extern "C" int pp_conv3x3_split_wgrad_nhwc_dev(pp_ctx_t *ctx, void *stream_, con
   return launch_on_device(ctx, "k_conv3x3_wgrad / k_conv3x3_wgrad_sum", [&] {
     hipLaunchKernelGGL(k_conv3x3_wgrad, dim3((unsigned)(nparts * pairs)), dim3(kThreads), 0, st, x_dev, dz_dev, height,
                        width, in_channels, out_channels, bands, segs, dz_scale_dev, ws);
+    hipLaunchKernelGGL(k_conv3x3_wgrad_sum, dim3((unsigned)(pairs * (kPartFloats / 256))), dim3(256), 0, st, ws,
+                       (int)nparts, in_channels, dw_dev);
+  });
+}
+
+// ---- the stride-2 form: the stride-1 pair's checks on x's extent, the partials counted on dz's
+
+namespace {
+
+bool wgrad_s2_plan(int batch, int height, int width, int in_channels, int out_channels, int64_t *nparts,
+                   int64_t *pairs, bool *too_large) {
+  if (!wgrad_plan(batch, height, width, in_channels, out_channels, nparts, pairs, too_large)) return false;
+  const int ho = (height + 1) / 2, wo = (width + 1) / 2;
+  *nparts = (int64_t)batch * ((ho + kRb - 1) / kRb) * ((wo + kS2Tw - 1) / kS2Tw);
+  // ceil(Ho / 16) <= ceil(H / 16) and ceil(Wo / 32) = ceil(W / 64): no more partials than the stride-1 plan has checked
+  return true;
+}
+
+}  // namespace
+
+extern "C" int64_t pp_conv3x3_s2_split_wgrad_workspace_bytes(int batch, int height, int width, int in_channels,
+                                                             int out_channels) {
+  int64_t nparts = 0, pairs = 0;
+  bool too_large = false;
+  if (!wgrad_s2_plan(batch, height, width, in_channels, out_channels, &nparts, &pairs, &too_large)) return -1;
+  return nparts * pairs * kPartFloats * (int64_t)sizeof(float);
+}
+
+extern "C" int pp_conv3x3_s2_split_wgrad_nhwc_dev(pp_ctx_t *ctx, void *stream_, const float *x_dev,
+                                                  const float *dz_dev, int batch, int height, int width,
+                                                  int in_channels, int out_channels, const float *dz_scale_dev,
+                                                  void *workspace_dev, int64_t workspace_bytes, float *dw_dev) {
+  static const char fn[] = "pp_conv3x3_s2_split_wgrad_nhwc_dev";
+  if (!ctx || !x_dev || !dz_dev || !workspace_dev || !dw_dev) {
+    set_error("%s: NULL argument", fn);
+    return PP_ERR_VALUE;
+  }
+  int64_t nparts = 0, pairs = 0;
+  bool too_large = false;
+  const bool ok = wgrad_s2_plan(batch, height, width, in_channels, out_channels, &nparts, &pairs, &too_large);
+  if (too_large) {
+    set_error("%s: tensor too large", fn);
+    return PP_ERR_VALUE;
+  }
+  if (!ok ||
+      ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(dz_dev) |
+        reinterpret_cast<uintptr_t>(workspace_dev) | reinterpret_cast<uintptr_t>(dw_dev)) & 15) ||
+      (reinterpret_cast<uintptr_t>(dz_scale_dev) & 3)) {
+    set_error("%s: need in_channels and out_channels multiples of 64 (at most 16384), 16-byte aligned x, dz, "
+              "workspace and dw, a 4-byte aligned dz_scale (batch=%d %dx%d in=%d out=%d)", fn, batch, height, width,
+              in_channels, out_channels);
+    return PP_ERR_VALUE;
+  }
+  const int64_t need = nparts * pairs * kPartFloats * (int64_t)sizeof(float);
+  if (workspace_bytes < need) {
+    set_error("%s: the workspace has %lld bytes, pp_conv3x3_s2_split_wgrad_workspace_bytes asks for %lld", fn,
+              (long long)workspace_bytes, (long long)need);
+    return PP_ERR_VALUE;
+  }
+  const int ho = (height + 1) / 2, wo = (width + 1) / 2;
+  const int bands = (ho + kRb - 1) / kRb, segs = (wo + kS2Tw - 1) / kS2Tw;
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  float *ws = static_cast<float *>(workspace_dev);
+  return launch_on_device(ctx, "k_conv3x3_s2_wgrad / k_conv3x3_wgrad_sum", [&] {
+    hipLaunchKernelGGL(k_conv3x3_s2_wgrad, dim3((unsigned)(nparts * pairs)), dim3(kThreads), 0, st, x_dev, dz_dev,
+                       height, width, ho, wo, in_channels, out_channels, bands, segs, dz_scale_dev, ws);
     hipLaunchKernelGGL(k_conv3x3_wgrad_sum, dim3((unsigned)(pairs * (kPartFloats / 256))), dim3(256), 0, st, ws,
                        (int)nparts, in_channels, dw_dev);
   });

@@ -32,8 +32,11 @@
 // The schedule is fixed (no split-K, no atomics): channel chunks in order, taps in order within a chunk,
 // so results are bit-identical from call to call.
 
+#include <algorithm>
+
 #include "pp_conv_split.h"
 #include "pp_conv_split_tile.h"
+#include "train/pp_conv_s2_train.h"
 
 namespace pp {
 
@@ -55,7 +58,10 @@ static_assert(2 * Geo<2>::kBufBytes == 86400 && 2 * Geo<4>::kBufBytes == 77824, 
 // prm [Cout][3] (bias, scale, shift).
 // y   pixel p of [B][Ho][Wo], channel c at y[p*y_stride + c] (y already offset to the channel slice).
 // grid: x = B * ceil((Ho/S+1)/kRows) * ceil((Wo/S+1)/32), y = Cout/64.
-template <int S>
+// BARE (pp_conv3x3_s2_split_dgrad_nhwc_dev, include/train/pp_conv_s2_train.h): y = v, no epilogue; prm is NULL or
+// {s, 1/s}, s a power of two: the stager multiplies x by s ahead of the split and the output is multiplied by 1/s.
+// Ho and Wo bound the stores per axis, so the two axes may carry different output paddings.
+template <int S, bool BARE = false>
 __global__ __launch_bounds__(256, S == 4 ? 2 : 1) void k_convt3x3_split(const float *__restrict__ x,
                                                            const uint4 *__restrict__ w,
                                                            const float *__restrict__ esc,
@@ -72,7 +78,13 @@ __global__ __launch_bounds__(256, S == 4 ? 2 : 1) void k_convt3x3_split(const fl
   const int jy0 = by * G::kRows, jx0 = bx * kTw;
   const int co0 = blockIdx.y * kCo;
   const int nchunks = Cin / kKc;
-  Stager<G> stage(x, w, b, H, W, Cin, jy0 - G::kHl, jx0 - G::kHl, nchunks);
+  Stager<G, BARE> stage(x, w, b, H, W, Cin, jy0 - G::kHl, jx0 - G::kHl, nchunks);
+  float inv = 1.0f;
+  if constexpr (BARE)
+    if (prm) {
+      stage.xs = prm[0];
+      inv = prm[1];
+    }
 
   // ---- MFMA role: lane (r = lane&31, h = lane>>5) holds A[block r of the row][channels 8h..8h+7] and
   // B[channels 8h..8h+7][cout r of the wave's column block]; the lo plane of either lies kAPart / kBPart bytes
@@ -128,7 +140,12 @@ __global__ __launch_bounds__(256, S == 4 ? 2 : 1) void k_convt3x3_split(const fl
   // register r; every phase of a block is stored by the one wave that owns it, the tapless ones from v = 0
   const int co = co0 + cb * 32 + l32;
   const float e = esc[co];
-  const Epilogue<1> ep(prm, co);
+  const auto ep = [&] {
+    if constexpr (BARE)
+      return Unscale{inv};
+    else
+      return Epilogue<1>(prm, co);
+  }();
   const int jy = jy0 + row;
 #pragma unroll
   for (int py = 0; py < S; ++py) {
@@ -147,7 +164,7 @@ __global__ __launch_bounds__(256, S == 4 ? 2 : 1) void k_convt3x3_split(const fl
       for (int r = 0; r < 16; ++r) {
         const int ox = S * (jx0 + (r & 3) + 8 * (r >> 2) + 4 * h) - 1 + px;
         if (ox >= 0 && ox < Wo)
-          yrow[(int64_t)ox * y_stride] = split_output(live ? m[p][r] : 0.0f, live ? c[p][r] : 0.0f, e, ep, 0);
+          yrow[(int64_t)ox * y_stride] = split_output<BARE>(live ? m[p][r] : 0.0f, live ? c[p][r] : 0.0f, e, ep, 0);
       }
     }
   }
@@ -190,5 +207,43 @@ extern "C" int pp_convt3x3_split_nhwc_dev(pp_ctx_t *ctx, void *stream_, const fl
                        static_cast<hipStream_t>(stream_), x_dev, static_cast<const uint4 *>(w_split_dev), esc,
                        params_dev, y_dev + y_channel_offset, height, width, in_channels, (int)ho, (int)wo,
                        y_channels, (int)tiles_x, (int)tiles_y);
+  });
+}
+
+// The data gradient of Conv2d(3x3, stride 2, padding 1): conv_transpose2d(dz, w, stride 2, padding 1) with an output
+// padding per axis, H - 2 Ho + 1 and W - 2 Wo + 1.  dz is the kernel's input, Cout its input channels.
+extern "C" int pp_conv3x3_s2_split_dgrad_nhwc_dev(pp_ctx_t *ctx, void *stream_, const float *dz_dev, int batch,
+                                                  int out_height, int out_width, int out_channels,
+                                                  const void *w_dgrad_dev, int height, int width, int in_channels,
+                                                  const float *dz_scale_dev, float *dx_dev) {
+  const char *fn = "pp_conv3x3_s2_split_dgrad_nhwc_dev";
+  if (int rc = check_conv_f16_args(fn, ctx, dz_dev, w_dgrad_dev, dz_scale_dev, dx_dev, batch, out_height, out_width,
+                                   out_channels, in_channels, in_channels, 0, true))
+    return rc;
+  if (reinterpret_cast<uintptr_t>(dz_scale_dev) & 3) {
+    set_error("%s: dz_scale_dev is not 4-byte aligned", fn);
+    return PP_ERR_VALUE;
+  }
+  const int64_t ho = out_height, wo = out_width;
+  if ((height != 2 * ho - 1 && height != 2 * ho) || (width != 2 * wo - 1 && width != 2 * wo)) {
+    set_error("%s: need height in {2 Ho - 1, 2 Ho} and width in {2 Wo - 1, 2 Wo} (dz %dx%d, dx %dx%d)", fn,
+              out_height, out_width, height, width);
+    return PP_ERR_VALUE;
+  }
+  const int64_t tiles_x = (width / 2 + 1 + kTw - 1) / kTw;
+  const int64_t tiles_y = (height / 2 + 1 + Geo<2>::kRows - 1) / Geo<2>::kRows;
+  const int64_t blocks = (int64_t)batch * tiles_x * tiles_y;
+  // the kernel indexes output rows and columns with int
+  if (blocks > 0x7fffffff || height > 0x3fffffff || width > 0x3fffffff ||
+      (int64_t)batch * height * width * std::max(in_channels, out_channels) > ((int64_t)1 << 40)) {
+    set_error("%s: tensor too large", fn);
+    return PP_ERR_VALUE;
+  }
+  const float *esc = split_scales(w_dgrad_dev, in_channels, out_channels);
+  return launch_on_device(ctx, "k_convt3x3_split", [&] {
+    hipLaunchKernelGGL((k_convt3x3_split<2, true>), dim3((unsigned)blocks, (unsigned)(in_channels / 64)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream_), dz_dev, static_cast<const uint4 *>(w_dgrad_dev), esc,
+                       dz_scale_dev, dx_dev, out_height, out_width, out_channels, height, width,
+                       (int64_t)in_channels, (int)tiles_x, (int)tiles_y);
   });
 }

@@ -203,10 +203,12 @@ def _conv_split(x, ws, table, cout, out=None, channel_offset=0):
     return _conv3x3_nhwc("pp_conv3x3_split_nhwc_dev", x, ws, table, cout, out, channel_offset)
 
 
-def _split_pack(weight, into=None):
+def _split_pack(weight, into=None, s2=False):
     """pp_split_pack_dev: ``(_split_filter(weight), _split_filter(weight.transpose(0, 1).flip(2, 3)))`` -- the
     operands of the training forward conv and of the conv that computes its data gradient -- in one launch, bit for
-    bit.  ``into``: an earlier result, overwritten where it fits this weight.  Cout % 64 == Cin % 64 == 0."""
+    bit.  ``into``: an earlier result, overwritten where it fits this weight.  Cout % 64 == Cin % 64 == 0.
+    ``s2``: pp_split_pack_s2_dev (include/train/pp_conv_s2_train.h), the pair of a stride-2 conv, whose data gradient
+    is a transposed conv: ``(_split_filter(weight), _convt_split_filter(weight))``, the taps not flipped."""
     co, ci = weight.shape[:2]
     sizes = (co * ci * 18 + 2 * co, co * ci * 18 + 2 * ci)        # flat fp16: planes, then scales
     if into is not None and all(t.device == weight.device and t.numel() == n for t, n in zip(into, sizes)):
@@ -214,7 +216,8 @@ def _split_pack(weight, into=None):
     else:
         fwd, dgrad = (torch.empty(n, dtype=torch.float16, device=weight.device) for n in sizes)
     w = weight.detach()
-    _call("pp_split_pack_dev", w.device, _vp(w if w.is_contiguous() else w.contiguous()), co, ci, _vp(fwd), _vp(dgrad))
+    _call("pp_split_pack_s2_dev" if s2 else "pp_split_pack_dev", w.device, _vp(w if w.is_contiguous() else w.contiguous()),
+          co, ci, _vp(fwd), _vp(dgrad))
     return fwd, dgrad
 
 
@@ -254,6 +257,49 @@ def _wgrad_split(x, dz, dz_scale, fused):
 def _wgrad_miopen(dz, x, weight):
     """MIOpen's weight gradient of the stride-1, padding-1 3x3 conv: ``_Conv3x3Train``'s without ``split_wgrad``."""
     return torch.ops.aten.convolution_backward(dz, x, weight, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1,
+                                               (False, True, False))[1]
+
+
+def _conv_s2_split_bare(x, ws, cout, x_scale=None):
+    """pp_conv3x3_s2_split_bare_nhwc_dev (include/train/pp_conv_s2_train.h): the bare output of Conv2d(3x3, stride 2,
+    padding 1) of the channels-last ``x`` into a new channels-last tensor; ``ws`` and ``x_scale`` as in
+    ``_conv_split_bare``."""
+    B, C, H, W = x.shape
+    out = torch.empty((B, cout, (H + 1) // 2, (W + 1) // 2), dtype=torch.float32, device=x.device,
+                      memory_format=torch.channels_last)
+    _call("pp_conv3x3_s2_split_bare_nhwc_dev", x.device, _vp(x), B, H, W, C, _vp(ws), cout, _vp(x_scale), _vp(out),
+          cout, 0)
+    return out
+
+
+def _dgrad_s2_split(dz, ws, cin, height, width, dz_scale=None):
+    """pp_conv3x3_s2_split_dgrad_nhwc_dev: the data gradient [B,cin,height,width] of that conv from the channels-last
+    ``dz``, a transposed conv with ``ws`` from ``_split_pack(..., s2=True)`` (``_convt_split_filter`` of the conv
+    weight); ``dz_scale``: ``_pow2_scale(dz)``."""
+    B, cout, ho, wo = dz.shape
+    dx = torch.empty((B, cin, height, width), dtype=torch.float32, device=dz.device, memory_format=torch.channels_last)
+    _call("pp_conv3x3_s2_split_dgrad_nhwc_dev", dz.device, _vp(dz), B, ho, wo, cout, _vp(ws), height, width, cin,
+          _vp(dz_scale), _vp(dx))
+    return dx
+
+
+def _wgrad_s2_split(x, dz, dz_scale, fused):
+    """pp_conv3x3_s2_split_wgrad_nhwc_dev: ``_wgrad_split`` for the stride-2 conv, ``dz`` at half of ``x``'s extent."""
+    B, C, H, W = x.shape
+    cout = dz.shape[1]
+    nbytes = _lib.lib().pp_conv3x3_s2_split_wgrad_workspace_bytes(B, H, W, C, cout)
+    if nbytes < 0 or tuple(dz.shape[2:]) != ((H + 1) // 2, (W + 1) // 2):
+        raise ValueError(f"pp_conv3x3_s2_split_wgrad_nhwc_dev does not take x {tuple(x.shape)}, dz {tuple(dz.shape)}")
+    ws = fused.wgrad_workspace(nbytes, x.device)
+    dw = torch.empty((cout, C, 3, 3), dtype=torch.float32, device=x.device)
+    _call("pp_conv3x3_s2_split_wgrad_nhwc_dev", x.device, _vp(x), _vp(dz), B, H, W, C, cout, _vp(dz_scale), _vp(ws),
+          nbytes, _vp(dw))
+    return dw
+
+
+def _wgrad_s2_miopen(dz, x, weight):
+    """MIOpen's weight gradient of the stride-2, padding-1 3x3 conv: ``_Conv3x3S2Train``'s without ``split_wgrad``."""
+    return torch.ops.aten.convolution_backward(dz, x, weight, None, (2, 2), (1, 1), (1, 1), False, (0, 0), 1,
                                                (False, True, False))[1]
 
 
@@ -449,12 +495,13 @@ class _FusedConv:
             cache = self._packed[kind] = _LayoutCache()
         return cache.get((weight,), lambda: pack(weight.transpose(0, 1).flip(2, 3) if transposed else weight))
 
-    def train_operands(self, weight):
-        """``_split_pack(weight)``: one launch per version of ``weight``, into buffers allocated once."""
+    def train_operands(self, weight, s2=False):
+        """``_split_pack(weight)``: one launch per version of ``weight``, into buffers allocated once.  ``s2``: the
+        layer is a stride-2 conv and takes that pack."""
         cache = self._packed.get("split_train")
         if cache is None:
             cache = self._packed["split_train"] = _LayoutCache()
-        return cache.get((weight,), lambda: _split_pack(weight, cache._val))
+        return cache.get((weight,), lambda: _split_pack(weight, cache._val, s2))
 
     def wgrad_workspace(self, nbytes, device):
         """``_wgrad_split``'s workspace: allocated once and reused while the layer's shape, hence ``nbytes``, holds."""
@@ -658,6 +705,38 @@ class _Conv3x3Train(torch.autograd.Function):
         return dx, dw, None, None
 
 
+class _Conv3x3S2Train(torch.autograd.Function):
+    """``_Conv3x3Train`` for the 3x3, stride-2, padding-1 conv that opens a down block
+    (include/train/pp_conv_s2_train.h): ``z = conv(x, weight)`` with ``x`` channels-last on the bare stride-2 split
+    kernel.  The data gradient is the transposed conv of ``dz`` with the weight as it lies (taps not flipped), at
+    ``x``'s extent, ``dz`` rescaled by ``_pow2_scale``; the weight gradient is MIOpen's (``_wgrad_s2_miopen``) or, with
+    ``split_wgrad``, the stride-2 split-K kernel's with the same scale (``_wgrad_s2_split``)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, fused, split_wgrad=False):
+        fwd, dgrad = fused.train_operands(weight, s2=True)
+        ctx.save_for_backward(x, weight)
+        ctx.dgrad = dgrad
+        ctx.wgrad_fused = fused if split_wgrad else None
+        return _conv_s2_split_bare(x, fwd, weight.shape[0])
+
+    @staticmethod
+    def backward(ctx, dz):
+        x, weight = ctx.saved_tensors
+        if not _nhwc_f32(dz):
+            dz = dz.float().contiguous(memory_format=torch.channels_last)
+        dx = dw = None
+        split_wgrad = ctx.wgrad_fused is not None and ctx.needs_input_grad[1]
+        scale = _pow2_scale(dz) if ctx.needs_input_grad[0] or split_wgrad else None     # one for dx and dw
+        if ctx.needs_input_grad[0]:
+            dx = _dgrad_s2_split(dz, ctx.dgrad, weight.shape[1], x.shape[2], x.shape[3], scale)
+        if split_wgrad:
+            dw = _wgrad_s2_split(x, dz, scale, ctx.wgrad_fused)
+        elif ctx.needs_input_grad[1]:
+            dw = _wgrad_s2_miopen(dz, x, weight)
+        return dx, dw, None, None
+
+
 class PPFeatureNet(nn.Module):
     """model/model.py:13-40: 1x1 conv D->C, ReLU, THEN BatchNorm, max over N."""
 
@@ -821,6 +900,12 @@ class PPDownBlock(nn.Module):
         #: tensors as they lie (csrc/pp_conv_wgrad.hip, include/train/pp_conv_wgrad.h) instead of MIOpen's; without
         #: ``split_train`` it does nothing
         self.split_wgrad = False
+        #: opt-in, with ``split_train`` (``PillarPipeline(..., split_train=True, split_train_s2=True)``): the stride-2
+        #: conv that opens the block too, forward and data gradient on the split-fp16 kernels with the channels-last
+        #: tail (``_Conv3x3S2Train``, include/train/pp_conv_s2_train.h), its weight gradient MIOpen's or, with
+        #: ``split_wgrad``, the stride-2 split-K kernel's; the block then takes and returns channels-last tensors and
+        #: copies no layout inside.  Without ``split_train`` it does nothing
+        self.split_train_s2 = False
         self._fused = [_FusedConv() for _ in range(num_layers)]
 
     def stem(self, feats, inds, h, w):
@@ -838,6 +923,14 @@ class PPDownBlock(nn.Module):
                     and all(_conv_kind(c) == "s1" and c.in_channels % 64 == 0 and c.out_channels % 64 == 0
                             and c.weight.dtype == torch.float32 for c in convs))
 
+    def _split_train_s2_ok(self, x):
+        """``split_train_s2`` applies: ``split_train`` does, and layer 0 is a stride-2 conv the kernels take."""
+        conv = self.block[0]
+        # a dense channels-last tensor off 16 bytes would not be moved by the conversion: it stays with MIOpen
+        return bool(self.split_train_s2 and self._split_train_ok(x) and _conv_kind(conv) == "s2"
+                    and (not _is_nhwc(x) or x.data_ptr() % 16 == 0)
+                    and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0 and conv.weight.dtype == torch.float32)
+
     def forward(self, x, first=0):
         """``first`` = 1: ``x`` is ``stem``'s output and has passed layer 0 already."""
         if not _use_fused_epilogue(self, x):
@@ -845,6 +938,16 @@ class PPDownBlock(nn.Module):
                 raise RuntimeError("PPDownBlock: a tensor past layer 0 needs the fused inference path")
             if self.training and self.fused_train and x.is_cuda:
                 split = self._split_train_ok(x)
+                if split and self._split_train_s2_ok(x):
+                    # every layer channels-last, in and out: the next block takes the result as it lies
+                    if not _nhwc_f32(x):
+                        x = x.contiguous(memory_format=torch.channels_last)
+                    for i in range(len(self._fused)):
+                        conv, bn = self.block[3 * i], self.block[3 * i + 2]
+                        fn = _Conv3x3Train if i else _Conv3x3S2Train
+                        x = _relu_bn(fn.apply(x, conv.weight, self._fused[i], bool(self.split_wgrad)), bn,
+                                     conv_bias=conv.bias)
+                    return x
                 for i in range(len(self._fused)):
                     conv, bn = self.block[3 * i], self.block[3 * i + 2]
                     if split and i > 0:

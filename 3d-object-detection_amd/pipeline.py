@@ -30,7 +30,7 @@ class PillarPipeline:
                  feature_channels=64, num_classes=9, reg_dims=8, device=None, seed=0,
                  pos_thresh=0.6, with_targets=False, data_mean=None, precision="f32",
                  strided=False, augment=None, paste=None, fused_loss=False, split_mma=True, split_strided=False,
-                 split_train=False, split_wgrad=False):
+                 split_train=False, split_wgrad=False, split_train_s2=False):
         """``augment``: an ``augment.AugmentConfig`` -- ``train_forward_backward(..., augment_rng=rng)`` then augments
         the points and the boxes on the device before the voxelizer and the assigner (needs ``with_targets``).
         ``paste``: ``(augment.GtBank, augment.PasteConfig)`` -- ground-truth sampling before that augmentation, so
@@ -59,12 +59,18 @@ class PillarPipeline:
         (``PPDownBlock.split_wgrad``) runs on the split-fp16 MFMA pipe, a deterministic split-K kernel on the
         channels-last tensors as they lie (include/train/pp_conv_wgrad.h), with the data gradient's power-of-two scale
         of ``dz``: no MIOpen call is left in those 13 layers.  The same window as ``split_train``.
+        ``split_train_s2``: with ``split_train`` only (else a ``ValueError``): the stride-2 conv that opens each of
+        down1, down2 and down3 (``PPDownBlock.split_train_s2``) runs forward and data gradient on the split-fp16
+        kernels too, channels-last with the channels-last tail (include/train/pp_conv_s2_train.h), and the blocks hand
+        channels-last tensors on: no layout copy is left inside a down block.  Its weight gradient stays MIOpen's
+        unless ``split_wgrad`` is on as well, which then covers these three layers too.  The same window.
         ``fused_loss``: ``train_forward_backward`` computes the loss and its gradients with ``loss.FusedPPLoss`` (three
         HIP launches, no host wait) instead of ``PPLoss``."""
         check_inference_precision(precision, strided)      # before anything is built
         self.check_split_strided(split_strided, precision, with_targets)
         self.check_split_train(split_train, precision, with_targets)
         self.check_split_wgrad(split_wgrad, split_train)
+        self.check_split_train_s2(split_train_s2, split_train)
         self.check_paste_argument(paste, augment)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.vox_cfg = vox_cfg
@@ -97,6 +103,7 @@ class PillarPipeline:
             for blk in (self.model.backbone.down1, self.model.backbone.down2, self.model.backbone.down3):
                 blk.split_train = True
                 blk.split_wgrad = bool(split_wgrad)       # ... and their weight gradient
+                blk.split_train_s2 = bool(split_train_s2)  # ... and the stride-2 conv that opens the block
         self.loss = FusedPPLoss(return_p=False) if fused_loss else PPLoss()
         self.assigner = None
         if with_targets:
@@ -149,6 +156,13 @@ class PillarPipeline:
         """The constructor's check of ``split_wgrad``, before any device is touched."""
         if split_wgrad and not split_train:
             raise ValueError("split_wgrad=True needs split_train=True: it is the weight gradient of the layers that "
+                             "split_train moves to the split-fp16 kernels")
+
+    @staticmethod
+    def check_split_train_s2(split_train_s2, split_train):
+        """The constructor's check of ``split_train_s2``, before any device is touched."""
+        if split_train_s2 and not split_train:
+            raise ValueError("split_train_s2=True needs split_train=True: it is the first layer of the blocks that "
                              "split_train moves to the split-fp16 kernels")
 
     @staticmethod

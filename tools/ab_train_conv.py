@@ -1,14 +1,18 @@
 """Dev tool: ``train_forward_backward`` with ``split_train`` off and on (include/pp_conv_train.h: the 13 stride-1
 layers of down1-3 on the split-fp16 kernel forward and data gradient, channels-last ReLU -> BatchNorm tail), and a
 third leg ``wgrad``: ``split_train`` with ``split_wgrad`` (include/train/pp_conv_wgrad.h: those layers' weight
-gradient on the split-K kernel too).  By the
+gradient on the split-K kernel too), and the legs of ``split_train_s2`` (include/train/pp_conv_s2_train.h: the stride-2
+conv that opens each block on the split-fp16 kernels as well, everything on): ``s2``, ``s2_nd1`` (down1's attribute
+flipped off by hand: its layer 0 pays a channels-last conversion of the whole canvas) and ``s2_nchw`` (the blocks hand
+on NCHW copies, as ``split_train`` alone does, instead of the channels-last tensors) and ``s2_up`` (channels-last
+between the down blocks, an NCHW copy for each up block).  By the
 protocol of profiles/r24/NOTES.md: the pipelines with the same weights in one process, 4 warm-up steps each, then three
 alternating runs of 10 steps at B = 4, 60 000 points per sweep, 500x500 grid, 40 boxes per sample; an event pair
 (device ms) and a host clock (host ms: first call to the return of the last, no synchronise) around each run.  Prints
 one JSON line, and the legs' loss scalars and largest gradient differences from ``off`` for orientation.
 
 usage: ab_train_conv.py [rounds] [steps per run]         (default 3 x 10)
-       ab_train_conv.py trace off|on|wgrad [steps]            (default 10; one leg alone, to run under a kernel trace)"""
+       ab_train_conv.py trace LEG [steps]                     (default 10; one leg alone, to run under a kernel trace)"""
 import json
 import os
 import sys
@@ -27,9 +31,22 @@ dev = torch.device("cuda", 0)
 cfg = VoxelConfig.square(50.0, 0.2, 12000, 100)
 
 
+LEGS = ("off", "on", "wgrad", "s2", "s2_nd1", "s2_nchw", "s2_up")
+
+
 def make(leg):
+    s2 = leg.startswith("s2")
     pipe = PillarPipeline(cfg, device=dev, seed=0, with_targets=True, fused_loss=True, split_train=leg != "off",
-                          split_wgrad=leg == "wgrad")
+                          split_wgrad=leg == "wgrad" or s2, split_train_s2=s2)
+    bb = pipe.model.backbone
+    if leg == "s2_nd1":
+        bb.down1.split_train_s2 = False
+    if leg == "s2_nchw":
+        for blk in (bb.down1, bb.down2, bb.down3):
+            blk.register_forward_hook(lambda m, args, out: out.contiguous())
+    if leg == "s2_up":
+        for blk in (bb.up1, bb.up2, bb.up3):
+            blk.register_forward_pre_hook(lambda m, args: (args[0].contiguous(),) + tuple(args[1:]))
     pipe.model.train()
     return pipe
 
@@ -69,8 +86,8 @@ if len(sys.argv) > 1 and sys.argv[1] == "trace":
 
 rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
-pipes = {k: make(k) for k in ("off", "on", "wgrad")}
-for k in ("on", "wgrad"):
+pipes = {k: make(k) for k in LEGS}
+for k in LEGS[1:]:
     pipes[k].model.load_state_dict(pipes["off"].model.state_dict())         # the same weights (the same seed made them)
 steppers = {k: stepper(p) for k, p in pipes.items()}
 for k, step in steppers.items():
@@ -79,7 +96,7 @@ for k, step in steppers.items():
     torch.cuda.synchronize()
 legs = {k: {"device_ms": [], "host_ms": []} for k in pipes}
 for r in range(rounds):
-    for k in (("wgrad", "on", "off") if r % 2 == 0 else ("off", "on", "wgrad")):
+    for k in (LEGS[::-1] if r % 2 == 0 else LEGS):
         d, h = run(steppers[k], steps)
         legs[k]["device_ms"].append(d)
         legs[k]["host_ms"].append(h)
@@ -91,6 +108,10 @@ res["spread_ms"] = max(res["off"]["device_spread"], res["on"]["device_spread"])
 # the same for split_wgrad against split_train alone: > spread: every wgrad run ahead of every on run by more than it
 res["wgrad_margin_ms"] = min(legs["on"]["device_ms"]) - max(legs["wgrad"]["device_ms"])
 res["wgrad_spread_ms"] = max(res["on"]["device_spread"], res["wgrad"]["device_spread"])
+# ... and for each split_train_s2 leg against the parent's best configuration, wgrad
+for k in LEGS[3:]:
+    res[k + "_margin_ms"] = min(legs["wgrad"]["device_ms"]) - max(legs[k]["device_ms"])
+    res[k + "_spread_ms"] = max(res["wgrad"]["device_spread"], res[k]["device_spread"])
 print(json.dumps({"ab_train_conv": res}))
 
 # orientation: one more step each from the same running statistics is not comparable bit for bit (each leg has updated
@@ -101,7 +122,7 @@ for k, step in steppers.items():
     torch.cuda.synchronize()
     out[k] = ([float(v) for v in losses], {n: p.grad.detach().clone() for n, p in pipes[k].model.named_parameters()})
 report = {"losses_" + k: v[0] for k, v in out.items()}
-for k in ("on", "wgrad"):
+for k in LEGS[1:]:
     diffs = {n: float((out[k][1][n] - g).abs().max()) / max(float(g.abs().max()), 1e-30)
              for n, g in out["off"][1].items()}
     # a conv bias ahead of a training-mode BatchNorm has a zero gradient but for rounding: those tensors are listed apart
