@@ -12,14 +12,15 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("PP_HIP_LIB") or os.path.join(_HERE, "libpp_hip.so")
 SOURCES = [os.path.join(_HERE, "csrc", f)
-           for f in ("pp_runtime.hip", "pp_voxelize.hip", "pp_iou.hip", "pp_ingest.hip", "pp_decode.hip", "pp_epilogue.hip", "pp_pfn.hip", "pp_pfn_train.hip", "pp_bn_train.hip", "pp_bn_train_nhwc.hip", "pp_eval.hip", "pp_wino.hip", "pp_conv_f16.hip", "pp_convt_f16.hip", "pp_conv_s2_f16.hip", "pp_conv_split.hip", "pp_conv_s2_split.hip", "pp_convt_split.hip", "pp_conv_train.hip", "pp_conv_wgrad.hip", "pp_stem.hip", "pp_head.hip", "pp_augment.hip", "pp_paste.hip", "pp_loss.hip", "pp_optim.hip")]
+           for f in ("pp_runtime.hip", "pp_voxelize.hip", "pp_iou.hip", "pp_ingest.hip", "pp_decode.hip", "pp_epilogue.hip", "pp_pfn.hip", "pp_pfn_train.hip", "pp_bn_train.hip", "pp_bn_train_nhwc.hip", "pp_eval.hip", "pp_wino.hip", "pp_conv_f16.hip", "pp_convt_f16.hip", "pp_conv_s2_f16.hip", "pp_conv_split.hip", "pp_conv_s2_split.hip", "pp_conv_s4_split.hip", "pp_convt_split.hip", "pp_conv_train.hip", "pp_conv_wgrad.hip", "pp_stem.hip", "pp_head.hip", "pp_augment.hip", "pp_paste.hip", "pp_loss.hip", "pp_optim.hip")]
 HEADERS = [os.path.join(_HERE, "csrc", "pp_common.h"), os.path.join(_HERE, "csrc", "pp_conv_f16_tile.h"),
            os.path.join(_HERE, "csrc", "pp_conv_split_tile.h"),
            os.path.join(_HERE, "csrc", "pp_box_geom.h"),
            os.path.join(_ROOT, "include", "pp_hip.h"), os.path.join(_ROOT, "include", "pp_optim.h"),
            os.path.join(_ROOT, "include", "pp_conv_split.h"), os.path.join(_ROOT, "include", "pp_conv_train.h"),
            os.path.join(_ROOT, "include", "train", "pp_conv_wgrad.h"),
-           os.path.join(_ROOT, "include", "train", "pp_conv_s2_train.h")]
+           os.path.join(_ROOT, "include", "train", "pp_conv_s2_train.h"),
+           os.path.join(_ROOT, "include", "train", "pp_convt_train.h")]
 
 PP_OK, PP_ERR_INDEX, PP_ERR_VALUE, PP_ERR_WINDING = 0, -2, -3, -4
 PP_ERR_NOMEM, PP_ERR_HIP, PP_ERR_INTERNAL = -5, -6, -7
@@ -52,6 +53,9 @@ WGRAD_EXPORTS = ["pp_conv3x3_split_wgrad_workspace_bytes", "pp_conv3x3_split_wgr
 # the training form of the stride-2 convs that open the down blocks: declared in include/train/pp_conv_s2_train.h
 TRAIN_S2_EXPORTS = ["pp_conv3x3_s2_split_bare_nhwc_dev", "pp_conv3x3_s2_split_dgrad_nhwc_dev", "pp_split_pack_s2_dev",
                     "pp_conv3x3_s2_split_wgrad_workspace_bytes", "pp_conv3x3_s2_split_wgrad_nhwc_dev"]
+# the training form of the up blocks' transposed convs: declared in include/train/pp_convt_train.h
+TRAIN_UP_EXPORTS = ["pp_convt3x3_s4_split_bare_nhwc_dev", "pp_conv3x3_s4_split_bare_nhwc_dev",
+                    "pp_convt3x3_split_wgrad_workspace_bytes", "pp_convt3x3_split_wgrad_nhwc_dev"]
 
 
 class VoxelParams(ctypes.Structure):
@@ -343,6 +347,15 @@ def _load(path):
     for name in TRAIN_S2_EXPORTS:
         getattr(L, name).restype = c_int
     L.pp_conv3x3_s2_split_wgrad_workspace_bytes.restype = i64
+    L.pp_convt3x3_s4_split_bare_nhwc_dev.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, vp, c_int, c_int, c_int, vp,
+                                                     vp]
+    L.pp_conv3x3_s4_split_bare_nhwc_dev.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, vp, c_int, vp, vp]
+    L.pp_convt3x3_split_wgrad_workspace_bytes.argtypes = [c_int] * 8
+    L.pp_convt3x3_split_wgrad_nhwc_dev.argtypes = [vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                   vp, vp, i64, vp]
+    for name in TRAIN_UP_EXPORTS:
+        getattr(L, name).restype = c_int
+    L.pp_convt3x3_split_wgrad_workspace_bytes.restype = i64
     L.pp_ctx_set_timing.argtypes = [vp, c_int]
     L.pp_ctx_read_emit_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), c_int,
                                       ctypes.POINTER(c_int)]

@@ -4,7 +4,7 @@
 // double-buffered chunk pipeline, the epilogue constants, and the host-side argument checks.
 // A kernel brings its tile geometry, its MFMA role (which fragments feed which accumulators) and the
 // accumulator-to-pixel mapping of its stores.  Included by those four files and, through pp_conv_split_tile.h, by the
-// split kernels of the strided layers (pp_conv_s2_split.hip, pp_convt_split.hip) only.
+// split kernels of the strided layers (pp_conv_s2_split.hip, pp_conv_s4_split.hip, pp_convt_split.hip) only.
 //
 // One LDS buffer (bytes): A[2 half][halo pixel][8 fp16] then B[9 tap][2 half][64 cout][8 fp16]; half h
 // holds channels 8h .. 8h+7 of the chunk.  A lane's A fragment is 8 consecutive channels of one pixel,
@@ -55,6 +55,9 @@ struct HaloGeo {
   static constexpr int kItems = 2 * kHalo;                     // (pixel, half) pairs of the halo tile
   static constexpr int kNItem = (kItems + 255) / 256;          // ... per thread, the last round partial
   __device__ static __forceinline__ int slot(int pix, int /*hy*/, int /*hx*/) { return pix; }
+  // The image row or column, relative to the tile's first, that halo row or column h holds: consecutive here; a
+  // kernel whose windows are disjoint stages only the pixels it reads (pp_conv_s4_split.hip).
+  __device__ static __forceinline__ int src(int h) { return h; }
 };
 
 // The input tile of ROWS rows of kTw pixels plus LO / HI halo pixels on the low / high side of both axes.
@@ -101,7 +104,7 @@ struct Stager {
       const int i = tid + 256 * k;
       const int pix = i >> 1, hh = i & 1;
       const int hy = pix / G::kHw, hx = pix - hy * G::kHw;
-      const int iy = iy0 + hy, ix = ix0 + hx;
+      const int iy = iy0 + G::src(hy), ix = ix0 + G::src(hx);
       xin[k] = i < G::kItems && iy >= 0 && iy < H && ix >= 0 && ix < W;
       xoff[k] = (xin[k] ? (iy * W + ix) * Cin : 0) + 8 * hh;
       adst[k] = hh * G::kAPlane + G::slot(pix, hy, hx) * 16;

@@ -1,5 +1,5 @@
 // pp_conv_split_tile.h -- what the split-fp16 convolutions (pp_conv_split.hip, pp_conv_s2_split.hip,
-// pp_convt_split.hip) share beyond pp_conv_f16_tile.h: how an output is made of its two accumulators, and where
+// pp_conv_s4_split.hip, pp_convt_split.hip) share beyond pp_conv_f16_tile.h: how an output is made of its two accumulators, and where
 // the channel scales lie behind the packed weight.  include/pp_conv_split.h states the arithmetic.
 #pragma once
 

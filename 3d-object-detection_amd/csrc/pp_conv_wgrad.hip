@@ -22,6 +22,7 @@
 #include "pp_common.h"
 #include "train/pp_conv_wgrad.h"
 #include "train/pp_conv_s2_train.h"
+#include "train/pp_convt_train.h"
 
 namespace pp {
 
@@ -74,6 +75,9 @@ __device__ __forceinline__ u32x4 read_tr8(const unsigned char *p) {
 
 // grid: partial * pairs + pair, pair = (output-channel block) * (Cin / 64) + (input-channel block)
 // partial = (b * bands + band) * segs + seg: rows [16 band, +16) and columns [64 seg, +64) of sample b
+// SX (pp_convt3x3_split_wgrad_nhwc_dev, include/train/pp_convt_train.h: a transposed conv's weight gradient is this one
+// with the roles exchanged, the output gradient in the x role): the scale s multiplies x instead of dz
+template <bool SX = false>
 __global__ __launch_bounds__(kThreads) void k_conv3x3_wgrad(const float *__restrict__ x, const float *__restrict__ dz,
                                                            int H, int W, int Cin, int Cout, int bands, int segs,
                                                            const float *__restrict__ dz_scale,
@@ -115,8 +119,8 @@ __global__ __launch_bounds__(kThreads) void k_conv3x3_wgrad(const float *__restr
     unsigned char *xrow = lds + ((row + 4) & 3) * kXRow + dst0, *drow_p = lds + kXBytes + (drow & 1) * kDzRow + dst0;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-      if (pos0 + 48 * k < kTw + 2) split_store(xrow + 48 * k * kPix, rx[k], 1.0f);
-      if (want_dz && pos0 + 48 * k < kTw) split_store(drow_p + 48 * k * kPix, rd[k], s);
+      if (pos0 + 48 * k < kTw + 2) split_store(xrow + 48 * k * kPix, rx[k], SX ? s : 1.0f);
+      if (want_dz && pos0 + 48 * k < kTw) split_store(drow_p + 48 * k * kPix, rd[k], SX ? 1.0f : s);
     }
   };
 
@@ -237,7 +241,8 @@ __device__ __forceinline__ int s2_slot(int row) { return (row & 1) ? 2 + ((row >
 }  // namespace
 
 // grid: as k_conv3x3_wgrad's; partial = (b * bands + band) * segs + seg: dz rows [16 band, +16) and dz columns
-// [32 seg, +32) of sample b
+// [32 seg, +32) of sample b.  SX: as in k_conv3x3_wgrad
+template <bool SX = false>
 __global__ __launch_bounds__(kThreads) void k_conv3x3_s2_wgrad(const float *__restrict__ x,
                                                               const float *__restrict__ dz, int H, int W, int Ho,
                                                               int Wo, int Cin, int Cout, int bands, int segs,
@@ -289,10 +294,10 @@ __global__ __launch_bounds__(kThreads) void k_conv3x3_s2_wgrad(const float *__re
   };
   auto store_rows = [&](int row0, int drow) {
     unsigned char *r0 = lds + s2_slot(row0) * kS2XRow, *r1 = lds + s2_slot(row0 + 1) * kS2XRow;
-    split_store(r0 + xdst01, rx[0], 1.0f);
-    split_store(r1 + xdst01, rx[1], 1.0f);
-    if (ok2) split_store((sel2 ? r1 : r0) + xdst2, rx[2], 1.0f);
-    if (dok) split_store(lds + kS2XBytes + (drow & 1) * kS2DzRow + ddst, rd, s);
+    split_store(r0 + xdst01, rx[0], SX ? s : 1.0f);
+    split_store(r1 + xdst01, rx[1], SX ? s : 1.0f);
+    if (ok2) split_store((sel2 ? r1 : r0) + xdst2, rx[2], SX ? s : 1.0f);
+    if (dok) split_store(lds + kS2XBytes + (drow & 1) * kS2DzRow + ddst, rd, SX ? 1.0f : s);
   };
 
   // the reads of this lane: k_conv3x3_wgrad's
@@ -358,6 +363,127 @@ __global__ __launch_bounds__(kThreads) void k_conv3x3_s2_wgrad(const float *__re
     for (int i = 0; i < 16; ++i) {
       const int co = coh * 32 + (i & 3) + 8 * (i >> 2) + 4 * kh, ci = cih * 32 + (lane & 31);
       out[((ky * 3 + kx) * 64 + co) * 64 + ci] = (acc_main[kx][i] + acc_corr[kx][i] * (1.0f / 2048.0f)) * inv;
+    }
+  }
+}
+
+// ---- the weight gradient of the stride-4 transposed conv (include/train/pp_convt_train.h): x [B][H][W][Ci], dy [B][Ho]
+// [Wo][Co], Ho in [4H - 3, 4H],
+//   dw[ci][co][ky][kx] = sum over pixels of x[b][i][j][ci] * dy[b][4i-1+ky][4j-1+kx][co]   (zero outside dy).
+// The operands, split, transposed reads, wave roles and output of k_conv3x3_wgrad, with x in the dz role (unscaled, the
+// MFMA's A operand) and dy in the x role (scaled by s).  The 3x3 windows of neighbouring x pixels are disjoint: tap
+// (ky, kx) pairs x pixel (i, j) with exactly one dy pixel, so there is no ring of rows and no halo.  A partial is 32
+// rows x 16 columns of x; per x row the stager loads the three live dy rows 4i-1 .. 4i+1 and of each the three live
+// column phases, de-interleaved [ky][kx][j]: the 8 consecutive x columns a lane reads meet 8 consecutive 320-byte
+// slots for every tap.  16 columns are one MFMA step (K = 16), so a row is 9 MFMAs x {main, corr} per wave.  A dy slot
+// serves one x pixel only: past the partial's edge both are staged as zeros, which keeps a NaN with the taps that
+// read it without a mask in the loop.  Two buffers of (16 + 9 x 16) pixels x 320 bytes: 102400 bytes of LDS; while
+// row i is multiplied, row i + 1 is loaded to registers, then split and written to the other buffer; one barrier per
+// row.
+
+namespace {
+
+constexpr int kS4Tw = 16;                          // x columns of a partial
+constexpr int kS4Rb = 32;                          // x rows of a partial
+constexpr int kS4Run = kS4Tw * kPix;               // the x row, or the dy pixels of one tap
+constexpr int kS4Buf = 10 * kS4Run;
+constexpr int kS4LdsBytes = 2 * kS4Buf;
+static_assert(kS4LdsBytes == 102400 && kThreads == 3 * kS4Tw * 16, "one dy item per thread and live dy row");
+
+}  // namespace
+
+// grid: partial * pairs + pair, pair = (Ci block) * (Co / 64) + (Co block): dw's order, k_conv3x3_wgrad_sum's
+// partial = (b * bands + band) * segs + seg: x rows [32 band, +32) and x columns [16 seg, +16) of sample b
+__global__ __launch_bounds__(kThreads) void k_convt3x3_s4_wgrad(const float *__restrict__ x,
+                                                               const float *__restrict__ dy, int H, int W, int Ho,
+                                                               int Wo, int Ci, int Co, int bands, int segs,
+                                                               const float *__restrict__ dy_scale,
+                                                               float *__restrict__ ws) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[kS4LdsBytes];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nco = Co >> 6, pairs = nco * (Ci >> 6);
+  const int pair = blockIdx.x % pairs, part = blockIdx.x / pairs;
+  const int cib = pair / nco, cob = pair - cib * nco;
+  const int seg = part % segs, band = part / segs % bands, b = part / segs / bands;
+  const int y0 = band * kS4Rb, y1 = min(H, y0 + kS4Rb), xs = seg * kS4Tw, xe = min(W, xs + kS4Tw);
+  const float s = dy_scale ? dy_scale[0] : 1.0f, inv = dy_scale ? dy_scale[1] : 1.0f;
+  const float *xb = x + (int64_t)b * H * W * Ci + cib * 64;
+  const float *db = dy + (int64_t)b * Ho * Wo * Co + cob * 64;
+
+  // the stager's items of this thread, 4 channels (4 (tid & 15) .. +3 of the block) of one pixel each; pos = tid >> 4
+  // in [0, 48) is (kx, j) = (pos / 16, pos % 16): dy column 4 (xs + j) - 1 + kx of each of the three live rows, and
+  // for pos < 16 x column xs + pos.  Columns past the partial's edge are staged as zeros in both operands
+  const int pos = tid >> 4, ch = (tid & 15) * 4;
+  const int kxs = pos >> 4, j = pos & 15;
+  const bool jin = xs + j < xe;
+  const int dcol = 4 * (xs + j) - 1 + kxs;
+  const bool dcin = jin && dcol >= 0 && dcol < Wo;
+  const int doff = dcol * Co + ch, ddst = kS4Run + pos * kPix + ch * 2;
+  const bool xok = pos < kS4Tw, xin = xok && jin;
+  const int xoff = (xs + pos) * Ci + ch, xdst = pos * kPix + ch * 2;
+  float4 rd[3], rx;
+  auto load4 = [](bool in, const float *p) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (in) v = *reinterpret_cast<const float4 *>(p);
+    return v;
+  };
+  // x row i and dy rows 4i - 1, 4i, 4i + 1 (zero outside dy) to registers
+  auto load_row = [&](int i) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int r = 4 * i - 1 + k;
+      const bool in = dcin && r >= 0 && r < Ho;
+      rd[k] = load4(in, db + ((in ? r * Wo * Co : 0) + doff));
+    }
+    rx = load4(xin, xb + (i * W * Ci + xoff));
+  };
+  auto store_row = [&](unsigned char *buf) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) split_store(buf + ddst + 3 * k * kS4Run, rd[k], s);
+    if (xok) split_store(buf + xdst, rx, 1.0f);
+  };
+
+  // the reads of this lane: k_conv3x3_wgrad's, x's channels (Ci) on the MFMA's A side
+  const int ky = wave >> 2, cih = wave >> 1 & 1, coh = wave & 1;
+  const int q = lane >> 2 & 3, p = lane & 3, c16 = lane >> 4 & 1, kh = lane >> 5;
+  const int aoff = (8 * kh + q) * kPix + (cih * 32 + c16 * 16 + 4 * p) * 2;
+  const int boff = (1 + 3 * ky) * kS4Run + (8 * kh + q) * kPix + (coh * 32 + c16 * 16 + 4 * p) * 2;
+
+  f32x16 acc_main[3], acc_corr[3];
+#pragma unroll
+  for (int kx = 0; kx < 3; ++kx) acc_main[kx] = acc_corr[kx] = f32x16{};
+
+  load_row(y0);
+  store_row(lds);
+  __syncthreads();
+
+#pragma unroll 1
+  for (int y = y0; y < y1; ++y) {
+    const bool more = y + 1 < y1;
+    if (more) load_row(y + 1);
+    const unsigned char *cur = lds + ((y - y0) & 1) * kS4Buf;
+    const f16x8 ah = __builtin_bit_cast(f16x8, read_tr8(cur + aoff));
+    const f16x8 al = __builtin_bit_cast(f16x8, read_tr8(cur + aoff + kLo));
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx) {
+      const f16x8 bh = __builtin_bit_cast(f16x8, read_tr8(cur + boff + kx * kS4Run));
+      const f16x8 bl = __builtin_bit_cast(f16x8, read_tr8(cur + boff + kx * kS4Run + kLo));
+      acc_main[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc_main[kx], 0, 0, 0);
+      acc_corr[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc_corr[kx], 0, 0, 0);
+      acc_corr[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc_corr[kx], 0, 0, 0);
+    }
+    if (more) store_row(lds + ((y - y0 + 1) & 1) * kS4Buf);
+    __syncthreads();
+  }
+
+  // accumulator i of lane l: x channel (i & 3) + 8 (i >> 2) + 4 (l >> 5), dy channel l & 31 of the tile
+  float *out = ws + ((int64_t)pair * (gridDim.x / pairs) + part) * kPartFloats;
+#pragma unroll
+  for (int kx = 0; kx < 3; ++kx) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int ci = cih * 32 + (i & 3) + 8 * (i >> 2) + 4 * kh, co = coh * 32 + (lane & 31);
+      out[((ky * 3 + kx) * 64 + ci) * 64 + co] = (acc_main[kx][i] + acc_corr[kx][i] * (1.0f / 2048.0f)) * inv;
     }
   }
 }
@@ -432,7 +558,7 @@ extern "C" int pp_conv3x3_split_wgrad_nhwc_dev(pp_ctx_t *ctx, void *stream_, con
   hipStream_t st = static_cast<hipStream_t>(stream_);
   float *ws = static_cast<float *>(workspace_dev);
   return launch_on_device(ctx, "k_conv3x3_wgrad / k_conv3x3_wgrad_sum", [&] {
-    hipLaunchKernelGGL(k_conv3x3_wgrad, dim3((unsigned)(nparts * pairs)), dim3(kThreads), 0, st, x_dev, dz_dev, height,
+    hipLaunchKernelGGL(k_conv3x3_wgrad<false>, dim3((unsigned)(nparts * pairs)), dim3(kThreads), 0, st, x_dev, dz_dev, height,
                        width, in_channels, out_channels, bands, segs, dz_scale_dev, ws);
     hipLaunchKernelGGL(k_conv3x3_wgrad_sum, dim3((unsigned)(pairs * (kPartFloats / 256))), dim3(256), 0, st, ws,
                        (int)nparts, in_channels, dw_dev);
@@ -498,9 +624,100 @@ extern "C" int pp_conv3x3_s2_split_wgrad_nhwc_dev(pp_ctx_t *ctx, void *stream_, 
   hipStream_t st = static_cast<hipStream_t>(stream_);
   float *ws = static_cast<float *>(workspace_dev);
   return launch_on_device(ctx, "k_conv3x3_s2_wgrad / k_conv3x3_wgrad_sum", [&] {
-    hipLaunchKernelGGL(k_conv3x3_s2_wgrad, dim3((unsigned)(nparts * pairs)), dim3(kThreads), 0, st, x_dev, dz_dev,
+    hipLaunchKernelGGL(k_conv3x3_s2_wgrad<false>, dim3((unsigned)(nparts * pairs)), dim3(kThreads), 0, st, x_dev, dz_dev,
                        height, width, ho, wo, in_channels, out_channels, bands, segs, dz_scale_dev, ws);
     hipLaunchKernelGGL(k_conv3x3_wgrad_sum, dim3((unsigned)(pairs * (kPartFloats / 256))), dim3(256), 0, st, ws,
                        (int)nparts, in_channels, dw_dev);
+  });
+}
+
+// ---- the transposed convs' weight gradient (include/train/pp_convt_train.h): the kernels above with the roles
+// exchanged -- x [B][H][W][Ci] in the dz role, dy [B][Ho][Wo][Co] in the x role and carrying the scale
+
+namespace {
+
+bool convt_wgrad_plan(int batch, int height, int width, int in_channels, int out_channels, int stride, int out_height,
+                      int out_width, int64_t *nparts, int64_t *pairs, bool *too_large) {
+  *too_large = false;
+  if ((stride != 1 && stride != 2 && stride != 4) || height < 1 || width < 1) return false;
+  const int64_t s = stride;
+  if (out_height < s * height - s + 1 || out_height > s * height || out_width < s * width - s + 1 ||
+      out_width > s * width)
+    return false;
+  // dy is the larger tensor: the channel counts, its extent and the 32-bit offsets are checked on it
+  if (!wgrad_plan(batch, out_height, out_width, out_channels, in_channels, nparts, pairs, too_large)) return false;
+  const int rb = stride == 4 ? kS4Rb : kRb, tw = stride == 4 ? kS4Tw : stride == 2 ? kS2Tw : kTw;
+  *nparts = (int64_t)batch * ((height + rb - 1) / rb) * ((width + tw - 1) / tw);
+  if (*nparts > 0x7fffffff || *nparts * *pairs > 0x7fffffff) {
+    *too_large = true;
+    return false;
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" int64_t pp_convt3x3_split_wgrad_workspace_bytes(int batch, int height, int width, int in_channels,
+                                                           int out_channels, int stride, int out_height,
+                                                           int out_width) {
+  int64_t nparts = 0, pairs = 0;
+  bool too_large = false;
+  if (!convt_wgrad_plan(batch, height, width, in_channels, out_channels, stride, out_height, out_width, &nparts,
+                        &pairs, &too_large))
+    return -1;
+  return nparts * pairs * kPartFloats * (int64_t)sizeof(float);
+}
+
+extern "C" int pp_convt3x3_split_wgrad_nhwc_dev(pp_ctx_t *ctx, void *stream_, const float *x_dev, const float *dy_dev,
+                                                int batch, int height, int width, int in_channels, int out_channels,
+                                                int stride, int out_height, int out_width, const float *dy_scale_dev,
+                                                void *workspace_dev, int64_t workspace_bytes, float *dw_dev) {
+  static const char fn[] = "pp_convt3x3_split_wgrad_nhwc_dev";
+  if (!ctx || !x_dev || !dy_dev || !workspace_dev || !dw_dev) {
+    set_error("%s: NULL argument", fn);
+    return PP_ERR_VALUE;
+  }
+  int64_t nparts = 0, pairs = 0;
+  bool too_large = false;
+  const bool ok = convt_wgrad_plan(batch, height, width, in_channels, out_channels, stride, out_height, out_width,
+                                   &nparts, &pairs, &too_large);
+  if (too_large) {
+    set_error("%s: tensor too large", fn);
+    return PP_ERR_VALUE;
+  }
+  if (!ok ||
+      ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(dy_dev) |
+        reinterpret_cast<uintptr_t>(workspace_dev) | reinterpret_cast<uintptr_t>(dw_dev)) & 15) ||
+      (reinterpret_cast<uintptr_t>(dy_scale_dev) & 3)) {
+    set_error("%s: need stride 1, 2 or 4, out_height in [S H - S + 1, S H] and out_width likewise, in_channels and "
+              "out_channels multiples of 64 (at most 16384), 16-byte aligned x, dy, workspace and dw, a 4-byte aligned "
+              "dy_scale (batch=%d x %dx%d dy %dx%d stride=%d in=%d out=%d)", fn, batch, height, width, out_height,
+              out_width, stride, in_channels, out_channels);
+    return PP_ERR_VALUE;
+  }
+  const int64_t need = nparts * pairs * kPartFloats * (int64_t)sizeof(float);
+  if (workspace_bytes < need) {
+    set_error("%s: the workspace has %lld bytes, pp_convt3x3_split_wgrad_workspace_bytes asks for %lld", fn,
+              (long long)workspace_bytes, (long long)need);
+    return PP_ERR_VALUE;
+  }
+  const int rb = stride == 4 ? kS4Rb : kRb, tw = stride == 4 ? kS4Tw : stride == 2 ? kS2Tw : kTw;
+  const int bands = (height + rb - 1) / rb, segs = (width + tw - 1) / tw;
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  float *ws = static_cast<float *>(workspace_dev);
+  const dim3 grid((unsigned)(nparts * pairs));
+  // the conv kernels' x is dy (their Cin = out_channels), their dz is x (their Cout = in_channels)
+  return launch_on_device(ctx, "k_conv3x3_wgrad<SX> / k_conv3x3_s2_wgrad<SX> / k_convt3x3_s4_wgrad / k_conv3x3_wgrad_sum", [&] {
+    if (stride == 1)
+      hipLaunchKernelGGL(k_conv3x3_wgrad<true>, grid, dim3(kThreads), 0, st, dy_dev, x_dev, height, width, out_channels,
+                         in_channels, bands, segs, dy_scale_dev, ws);
+    else if (stride == 2)
+      hipLaunchKernelGGL(k_conv3x3_s2_wgrad<true>, grid, dim3(kThreads), 0, st, dy_dev, x_dev, out_height, out_width,
+                         height, width, out_channels, in_channels, bands, segs, dy_scale_dev, ws);
+    else
+      hipLaunchKernelGGL(k_convt3x3_s4_wgrad, grid, dim3(kThreads), 0, st, x_dev, dy_dev, height, width, out_height,
+                         out_width, in_channels, out_channels, bands, segs, dy_scale_dev, ws);
+    hipLaunchKernelGGL(k_conv3x3_wgrad_sum, dim3((unsigned)(pairs * (kPartFloats / 256))), dim3(256), 0, st, ws,
+                       (int)nparts, out_channels, dw_dev);
   });
 }

@@ -37,6 +37,7 @@
 #include "pp_conv_split.h"
 #include "pp_conv_split_tile.h"
 #include "train/pp_conv_s2_train.h"
+#include "train/pp_convt_train.h"
 
 namespace pp {
 
@@ -61,6 +62,8 @@ static_assert(2 * Geo<2>::kBufBytes == 86400 && 2 * Geo<4>::kBufBytes == 77824, 
 // BARE (pp_conv3x3_s2_split_dgrad_nhwc_dev, include/train/pp_conv_s2_train.h): y = v, no epilogue; prm is NULL or
 // {s, 1/s}, s a power of two: the stager multiplies x by s ahead of the split and the output is multiplied by 1/s.
 // Ho and Wo bound the stores per axis, so the two axes may carry different output paddings.
+// k_convt3x3_split<4, true> is up3's bare training forward (pp_convt3x3_s4_split_bare_nhwc_dev,
+// include/train/pp_convt_train.h).
 template <int S, bool BARE = false>
 __global__ __launch_bounds__(256, S == 4 ? 2 : 1) void k_convt3x3_split(const float *__restrict__ x,
                                                            const uint4 *__restrict__ w,
@@ -245,5 +248,44 @@ extern "C" int pp_conv3x3_s2_split_dgrad_nhwc_dev(pp_ctx_t *ctx, void *stream_, 
                        static_cast<hipStream_t>(stream_), dz_dev, static_cast<const uint4 *>(w_dgrad_dev), esc,
                        dz_scale_dev, dx_dev, out_height, out_width, out_channels, height, width,
                        (int64_t)in_channels, (int)tiles_x, (int)tiles_y);
+  });
+}
+
+// The bare forward of ConvTranspose2d(3x3, stride 4, padding 1) with an output padding per axis, out_height - (4 height
+// - 3) and out_width - (4 width - 3): up3 in training.
+extern "C" int pp_convt3x3_s4_split_bare_nhwc_dev(pp_ctx_t *ctx, void *stream_, const float *x_dev, int batch,
+                                                  int height, int width, int in_channels, const void *w_split_dev,
+                                                  int out_channels, int out_height, int out_width,
+                                                  const float *x_scale_dev, float *y_dev) {
+  const char *fn = "pp_convt3x3_s4_split_bare_nhwc_dev";
+  if (int rc = check_conv_f16_args(fn, ctx, x_dev, w_split_dev, x_scale_dev, y_dev, batch, height, width, in_channels,
+                                   out_channels, out_channels, 0, true))
+    return rc;
+  if (in_channels % 64 || (reinterpret_cast<uintptr_t>(x_scale_dev) & 3)) {
+    set_error("%s: need in_channels a multiple of 64 and a 4-byte aligned x_scale_dev (in=%d)", fn, in_channels);
+    return PP_ERR_VALUE;
+  }
+  const int64_t ho = out_height, wo = out_width;
+  if (ho < 4 * (int64_t)height - 3 || ho > 4 * (int64_t)height || wo < 4 * (int64_t)width - 3 ||
+      wo > 4 * (int64_t)width) {
+    set_error("%s: need out_height in [4 H - 3, 4 H] and out_width in [4 W - 3, 4 W] (x %dx%d, y %dx%d)", fn, height,
+              width, out_height, out_width);
+    return PP_ERR_VALUE;
+  }
+  const int64_t tiles_x = (wo / 4 + 1 + kTw - 1) / kTw, tiles_y = (ho / 4 + 1 + Geo<4>::kRows - 1) / Geo<4>::kRows;
+  const int64_t blocks = (int64_t)batch * tiles_x * tiles_y;
+  // the kernel indexes output rows and columns with int
+  if (blocks > 0x7fffffff || ho > 0x3fffffff || wo > 0x3fffffff ||
+      (double)batch * (double)ho * (double)wo * (double)std::max(in_channels, out_channels) >
+          (double)((int64_t)1 << 40)) {
+    set_error("%s: tensor too large", fn);
+    return PP_ERR_VALUE;
+  }
+  const float *esc = split_scales(w_split_dev, out_channels, in_channels);
+  return launch_on_device(ctx, "k_convt3x3_split", [&] {
+    hipLaunchKernelGGL((k_convt3x3_split<4, true>), dim3((unsigned)blocks, (unsigned)(out_channels / 64)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream_), x_dev, static_cast<const uint4 *>(w_split_dev), esc,
+                       x_scale_dev, y_dev, height, width, in_channels, out_height, out_width, (int64_t)out_channels,
+                       (int)tiles_x, (int)tiles_y);
   });
 }

@@ -303,6 +303,54 @@ def _wgrad_s2_miopen(dz, x, weight):
                                                (False, True, False))[1]
 
 
+def _convt_split_bare(x, ws, cout, stride, out_hw):
+    """The bare output [B,cout,*out_hw] of ConvTranspose2d(3x3, padding 1, ``stride`` 1, 2 or 4) of the channels-last
+    ``x`` (include/train/pp_convt_train.h): the stride-1 bare conv on the flipped operand, the stride-2 conv's data
+    gradient kernel with ``x`` for ``dz``, or pp_convt3x3_s4_split_bare_nhwc_dev; ``ws``: the forward operand of
+    ``_FusedConv.train_operands(..., transposed=True)``."""
+    if stride == 1:
+        return _conv_split_bare(x, ws, cout)
+    if stride == 2:
+        return _dgrad_s2_split(x, ws, cout, *out_hw)
+    B, C, H, W = x.shape
+    out = torch.empty((B, cout) + tuple(out_hw), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    _call("pp_convt3x3_s4_split_bare_nhwc_dev", x.device, _vp(x), B, H, W, C, _vp(ws), cout, out_hw[0], out_hw[1], None,
+          _vp(out))
+    return out
+
+
+def _convt_dgrad_split(dy, ws, cin, stride, dy_scale=None):
+    """The data gradient [B,cin,H,W] of that transposed conv from the channels-last ``dy``: ``conv2d(dy, w_t, stride,
+    padding 1)`` on the bare split kernel of that stride (stride 4: pp_conv3x3_s4_split_bare_nhwc_dev); ``ws``: the
+    data gradient's operand of ``train_operands``; ``dy_scale``: ``_pow2_scale(dy)``."""
+    if stride == 1:
+        return _conv_split_bare(dy, ws, cin, dy_scale)
+    if stride == 2:
+        return _conv_s2_split_bare(dy, ws, cin, dy_scale)
+    B, C, H, W = dy.shape
+    dx = torch.empty((B, cin, (H + 3) // 4, (W + 3) // 4), dtype=torch.float32, device=dy.device,
+                     memory_format=torch.channels_last)
+    _call("pp_conv3x3_s4_split_bare_nhwc_dev", dy.device, _vp(dy), B, H, W, C, _vp(ws), cin, _vp(dy_scale), _vp(dx))
+    return dx
+
+
+def _wgrad_convt_split(x, dy, stride, dy_scale, fused):
+    """pp_convt3x3_split_wgrad_nhwc_dev: the weight gradient [Cin,Cout,3,3] of that transposed conv from its
+    channels-last input ``x`` and output gradient ``dy``, as they lie; ``dy_scale``: ``_pow2_scale(dy)``; ``fused``
+    keeps the split-K workspace."""
+    B, C, H, W = x.shape
+    cout, ho, wo = dy.shape[1:]
+    nbytes = _lib.lib().pp_convt3x3_split_wgrad_workspace_bytes(B, H, W, C, cout, stride, ho, wo)
+    if nbytes < 0:
+        raise ValueError(f"pp_convt3x3_split_wgrad_nhwc_dev does not take x {tuple(x.shape)}, dy {tuple(dy.shape)}, "
+                         f"stride {stride}")
+    ws = fused.wgrad_workspace(nbytes, x.device)
+    dw = torch.empty((C, cout, 3, 3), dtype=torch.float32, device=x.device)
+    _call("pp_convt3x3_split_wgrad_nhwc_dev", x.device, _vp(x), _vp(dy), B, H, W, C, cout, stride, ho, wo,
+          _vp(dy_scale), _vp(ws), nbytes, _vp(dw))
+    return dw
+
+
 def _conv_s2_f16(x, w16, table, cout, out=None, channel_offset=0):
     """pp_conv3x3_s2_f16_nhwc_dev: Conv2d(3x3, padding 1, stride 2) + bias/ReLU/BatchNorm of ``x`` (NHWC) with fp16
     operands (``w16`` from ``_f16_filter``) and f32 accumulation, into a new channels-last tensor or into channels
@@ -495,13 +543,16 @@ class _FusedConv:
             cache = self._packed[kind] = _LayoutCache()
         return cache.get((weight,), lambda: pack(weight.transpose(0, 1).flip(2, 3) if transposed else weight))
 
-    def train_operands(self, weight, s2=False):
+    def train_operands(self, weight, s2=False, transposed=False):
         """``_split_pack(weight)``: one launch per version of ``weight``, into buffers allocated once.  ``s2``: the
-        layer is a stride-2 conv and takes that pack."""
+        layer is a stride-2 conv and takes that pack.  ``transposed``: ``weight`` is a ConvTranspose's, read as the
+        weight of the conv whose data gradient the layer computes (``s2``: its stride is 2 or 4); the pair comes back
+        exchanged, the layer's forward operand first."""
         cache = self._packed.get("split_train")
         if cache is None:
             cache = self._packed["split_train"] = _LayoutCache()
-        return cache.get((weight,), lambda: _split_pack(weight, cache._val, s2))
+        pair = cache.get((weight,), lambda: _split_pack(weight, cache._val, s2))
+        return pair[::-1] if transposed else pair
 
     def wgrad_workspace(self, nbytes, device):
         """``_wgrad_split``'s workspace: allocated once and reused while the layer's shape, hence ``nbytes``, holds."""
@@ -735,6 +786,34 @@ class _Conv3x3S2Train(torch.autograd.Function):
         elif ctx.needs_input_grad[1]:
             dw = _wgrad_s2_miopen(dz, x, weight)
         return dx, dw, None, None
+
+
+class _ConvT3x3Train(torch.autograd.Function):
+    """``_Conv3x3S2Train``'s counterpart for the 3x3, padding-1 transposed conv of an up block, stride 1, 2 or 4
+    (include/train/pp_convt_train.h): ``y = conv_transpose2d(x, weight)`` at ``out_hw`` with ``x`` channels-last.  With
+    ``weight`` read as the weight of a conv of that stride, the forward is that conv's data gradient, the data
+    gradient its forward on ``dy`` rescaled by ``_pow2_scale``, and the weight gradient its split-K weight gradient
+    with the roles exchanged (``_wgrad_convt_split``) and the same scale; there is no MIOpen variant."""
+
+    @staticmethod
+    def forward(ctx, x, weight, fused, stride, out_hw):
+        fwd, dgrad = fused.train_operands(weight, s2=stride != 1, transposed=True)
+        ctx.save_for_backward(x, weight)
+        ctx.dgrad, ctx.fused, ctx.stride = dgrad, fused, stride
+        return _convt_split_bare(x, fwd, weight.shape[1], stride, out_hw)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        if not _nhwc_f32(dy):
+            dy = dy.float().contiguous(memory_format=torch.channels_last)
+        dx = dw = None
+        scale = _pow2_scale(dy) if ctx.needs_input_grad[0] or ctx.needs_input_grad[1] else None   # one for dx and dw
+        if ctx.needs_input_grad[0]:
+            dx = _convt_dgrad_split(dy, ctx.dgrad, weight.shape[0], ctx.stride, scale)
+        if ctx.needs_input_grad[1]:
+            dw = _wgrad_convt_split(x, dy, ctx.stride, scale, ctx.fused)
+        return dx, dw, None, None, None
 
 
 class PPFeatureNet(nn.Module):
@@ -985,7 +1064,26 @@ class PPUpBlock(nn.Module):
         #: pipe instead of MIOpen's transposed conv and an epilogue pass (csrc/pp_convt_split.hip: split-fp16 operands);
         #: ``half_mma_up`` comes first; ``split_mma`` stays without effect on these blocks
         self.split_mma_up = False
+        #: opt-in (``PillarPipeline(with_targets=True, split_train_up=True)``): in train(), with ``fused_train``, the
+        #: transposed conv on the split-fp16 MFMA kernels in all three directions, forward, data gradient and weight
+        #: gradient, with the channels-last ReLU -> BatchNorm tail (``_ConvT3x3Train``,
+        #: include/train/pp_convt_train.h) instead of MIOpen's; the block converts an input that does not arrive
+        #: channels-last once and returns its channels-last tensor as it lies.  Forward activations with
+        #: |x| >= 65520 give NaN
+        self.split_train_up = False
         self._fused = _FusedConv()
+
+    def _split_train_up_ok(self, x):
+        """``split_train_up`` applies: a CUDA f32 tensor and a 3x3, padding-1 transposed conv of stride 1, 2 or 4 with
+        channel counts the kernels take."""
+        ct = self.conv2d_t
+        s, op = tuple(ct.stride), tuple(ct.output_padding)
+        # a dense channels-last tensor off 16 bytes would not be moved by the conversion: it stays with MIOpen
+        return bool(self.split_train_up and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+                    and (not _is_nhwc(x) or x.data_ptr() % 16 == 0)
+                    and tuple(ct.kernel_size) == (3, 3) and tuple(ct.padding) == (1, 1) and tuple(ct.dilation) == (1, 1)
+                    and ct.groups == 1 and s in ((1, 1), (2, 2), (4, 4)) and 0 <= op[0] < s[0] and 0 <= op[1] < s[0]
+                    and ct.in_channels % 64 == 0 and ct.out_channels % 64 == 0 and ct.weight.dtype == torch.float32)
 
     def forward(self, x, out=None, channel_offset=0, defer=False):
         """``defer``: ``_FusedConv.__call__``'s, on the fused inference path only."""
@@ -994,6 +1092,13 @@ class PPUpBlock(nn.Module):
                 raise RuntimeError("PPUpBlock: a deferred epilogue needs the fused inference path")
             if self.fused_train and _relu_bn_fusable(x, self.bn):
                 ct = self.conv2d_t
+                if self._split_train_up_ok(x):
+                    if not _nhwc_f32(x):
+                        x = x.contiguous(memory_format=torch.channels_last)
+                    s, op = ct.stride[0], ct.output_padding
+                    out_hw = ((x.shape[2] - 1) * s + 1 + op[0], (x.shape[3] - 1) * s + 1 + op[1])
+                    return _relu_bn(_ConvT3x3Train.apply(x, ct.weight, self._fused, s, out_hw), self.bn,
+                                    conv_bias=ct.bias)
                 return _relu_bn(F.conv_transpose2d(x, ct.weight, None, ct.stride, ct.padding, ct.output_padding),
                                 self.bn, conv_bias=ct.bias)
             return self.bn(F.relu(self.conv2d_t(x)))

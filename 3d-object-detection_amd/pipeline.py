@@ -30,7 +30,7 @@ class PillarPipeline:
                  feature_channels=64, num_classes=9, reg_dims=8, device=None, seed=0,
                  pos_thresh=0.6, with_targets=False, data_mean=None, precision="f32",
                  strided=False, augment=None, paste=None, fused_loss=False, split_mma=True, split_strided=False,
-                 split_train=False, split_wgrad=False, split_train_s2=False):
+                 split_train=False, split_wgrad=False, split_train_s2=False, split_train_up=False):
         """``augment``: an ``augment.AugmentConfig`` -- ``train_forward_backward(..., augment_rng=rng)`` then augments
         the points and the boxes on the device before the voxelizer and the assigner (needs ``with_targets``).
         ``paste``: ``(augment.GtBank, augment.PasteConfig)`` -- ground-truth sampling before that augmentation, so
@@ -64,6 +64,11 @@ class PillarPipeline:
         kernels too, channels-last with the channels-last tail (include/train/pp_conv_s2_train.h), and the blocks hand
         channels-last tensors on: no layout copy is left inside a down block.  Its weight gradient stays MIOpen's
         unless ``split_wgrad`` is on as well, which then covers these three layers too.  The same window.
+        ``split_train_up``: with ``with_targets`` and ``precision="f32"`` only (else a ``ValueError``), independent of
+        the down blocks' switches: in train() the transposed convs of up1, up2 and up3 (``PPUpBlock.split_train_up``) run
+        on the split-fp16 MFMA kernels in all three directions, forward, data gradient and weight gradient, with the
+        channels-last tail (include/train/pp_convt_train.h) instead of MIOpen's; there is no MIOpen weight-gradient
+        variant for these blocks.  The same window: the up blocks' inputs are BatchNorm outputs.  eval() is untouched.
         ``fused_loss``: ``train_forward_backward`` computes the loss and its gradients with ``loss.FusedPPLoss`` (three
         HIP launches, no host wait) instead of ``PPLoss``."""
         check_inference_precision(precision, strided)      # before anything is built
@@ -71,6 +76,7 @@ class PillarPipeline:
         self.check_split_train(split_train, precision, with_targets)
         self.check_split_wgrad(split_wgrad, split_train)
         self.check_split_train_s2(split_train_s2, split_train)
+        self.check_split_train_up(split_train_up, precision, with_targets)
         self.check_paste_argument(paste, augment)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.vox_cfg = vox_cfg
@@ -104,6 +110,10 @@ class PillarPipeline:
                 blk.split_train = True
                 blk.split_wgrad = bool(split_wgrad)       # ... and their weight gradient
                 blk.split_train_s2 = bool(split_train_s2)  # ... and the stride-2 conv that opens the block
+        # ... and, on request, the up blocks' transposed convs in all three directions
+        if split_train_up:
+            for blk in (self.model.backbone.up1, self.model.backbone.up2, self.model.backbone.up3):
+                blk.split_train_up = True
         self.loss = FusedPPLoss(return_p=False) if fused_loss else PPLoss()
         self.assigner = None
         if with_targets:
@@ -157,6 +167,18 @@ class PillarPipeline:
         if split_wgrad and not split_train:
             raise ValueError("split_wgrad=True needs split_train=True: it is the weight gradient of the layers that "
                              "split_train moves to the split-fp16 kernels")
+
+    @staticmethod
+    def check_split_train_up(split_train_up, precision, with_targets):
+        """The constructor's check of ``split_train_up``, before any device is touched."""
+        if not split_train_up:
+            return
+        if not with_targets:
+            raise ValueError("split_train_up=True needs with_targets=True: it switches the training step's transposed "
+                             "convolutions")
+        if precision != "f32":
+            raise ValueError(f"split_train_up=True goes with precision \"f32\" only, not {precision!r}: the fp16 modes "
+                             "are inference modes")
 
     @staticmethod
     def check_split_train_s2(split_train_s2, split_train):

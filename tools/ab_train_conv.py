@@ -5,7 +5,9 @@ gradient on the split-K kernel too), and the legs of ``split_train_s2`` (include
 conv that opens each block on the split-fp16 kernels as well, everything on): ``s2``, ``s2_nd1`` (down1's attribute
 flipped off by hand: its layer 0 pays a channels-last conversion of the whole canvas) and ``s2_nchw`` (the blocks hand
 on NCHW copies, as ``split_train`` alone does, instead of the channels-last tensors) and ``s2_up`` (channels-last
-between the down blocks, an NCHW copy for each up block).  By the
+between the down blocks, an NCHW copy for each up block), and ``up``: everything on plus ``split_train_up``
+(include/train/pp_convt_train.h: the up blocks' transposed convs on the split-fp16 kernels in all three directions),
+judged against ``s2``.  By the
 protocol of profiles/r24/NOTES.md: the pipelines with the same weights in one process, 4 warm-up steps each, then three
 alternating runs of 10 steps at B = 4, 60 000 points per sweep, 500x500 grid, 40 boxes per sample; an event pair
 (device ms) and a host clock (host ms: first call to the return of the last, no synchronise) around each run.  Prints
@@ -31,13 +33,13 @@ dev = torch.device("cuda", 0)
 cfg = VoxelConfig.square(50.0, 0.2, 12000, 100)
 
 
-LEGS = ("off", "on", "wgrad", "s2", "s2_nd1", "s2_nchw", "s2_up")
+LEGS = ("off", "on", "wgrad", "s2", "s2_nd1", "s2_nchw", "s2_up", "up")
 
 
 def make(leg):
-    s2 = leg.startswith("s2")
+    s2 = leg.startswith("s2") or leg == "up"
     pipe = PillarPipeline(cfg, device=dev, seed=0, with_targets=True, fused_loss=True, split_train=leg != "off",
-                          split_wgrad=leg == "wgrad" or s2, split_train_s2=s2)
+                          split_wgrad=leg == "wgrad" or s2, split_train_s2=s2, split_train_up=leg == "up")
     bb = pipe.model.backbone
     if leg == "s2_nd1":
         bb.down1.split_train_s2 = False
@@ -109,9 +111,12 @@ res["spread_ms"] = max(res["off"]["device_spread"], res["on"]["device_spread"])
 res["wgrad_margin_ms"] = min(legs["on"]["device_ms"]) - max(legs["wgrad"]["device_ms"])
 res["wgrad_spread_ms"] = max(res["on"]["device_spread"], res["wgrad"]["device_spread"])
 # ... and for each split_train_s2 leg against the parent's best configuration, wgrad
-for k in LEGS[3:]:
+for k in LEGS[3:7]:
     res[k + "_margin_ms"] = min(legs["wgrad"]["device_ms"]) - max(legs[k]["device_ms"])
     res[k + "_spread_ms"] = max(res["wgrad"]["device_spread"], res[k]["device_spread"])
+# ... and for split_train_up against its parent's best configuration, s2
+res["up_margin_ms"] = min(legs["s2"]["device_ms"]) - max(legs["up"]["device_ms"])
+res["up_spread_ms"] = max(res["s2"]["device_spread"], res["up"]["device_spread"])
 print(json.dumps({"ab_train_conv": res}))
 
 # orientation: one more step each from the same running statistics is not comparable bit for bit (each leg has updated
