@@ -71,9 +71,42 @@ __device__ __forceinline__ u32x4 read_tr8(const unsigned char *p) {
   return u32x4{ua[0], ua[1], ub[0], ub[1]};
 }
 
+// ---- what the three partial kernels share.  The MFMA's A operand is the tensor whose channels are the rows of a
+// partial's [9][64][64] (dz; in k_convt3x3_s4_wgrad x), its B operand the one whose channels are the columns.  The
+// lane's read offsets and the write of the partial stay written out in each kernel: as helpers they change how the
+// compiler folds the index arithmetic, and with it the kernels' instructions
+
+// the workgroup's share.  grid: partial * pairs + pair, pair = (A-side channel block) * nb + (B-side channel block),
+// nb the B side's blocks of 64 channels and na the A side's; partial = (b * bands + band) * segs + seg
+struct Item {
+  int pairs, pair, part, ablk, bblk, seg, band, b;
+};
+__device__ __forceinline__ Item decode_item(int nb, int na, int bands, int segs) {
+  Item it;
+  it.pairs = nb * na;
+  it.pair = blockIdx.x % it.pairs, it.part = blockIdx.x / it.pairs;
+  it.ablk = it.pair / nb, it.bblk = it.pair - it.ablk * nb;
+  it.seg = it.part % segs, it.band = it.part / segs % bands, it.b = it.part / segs / bands;
+  return it;
+}
+
+// the last step of a row where the partial's width is no multiple of 16: the A operand is zero past the edge, and the
+// B operand is made zero there too, so that a NaN of it stays with the taps that read it.  The mask of dword d (pixels
+// 2d and 2d + 1) of a lane's 8 pixels; rem: this lane's pixels of that step that are inside
+__device__ __forceinline__ unsigned tail_mask(int d, int rem) {
+  return (2 * d < rem ? 0xffffu : 0u) | (2 * d + 1 < rem ? 0xffff0000u : 0u);
+}
+
+// the split product of pp_conv_train.h: hi * hi to main, hi * lo and lo * hi to corr
+__device__ __forceinline__ void mfma3(f16x8 ah, f16x8 al, f16x8 bh, f16x8 bl, f32x16 &main, f32x16 &corr) {
+  main = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, main, 0, 0, 0);
+  corr = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, corr, 0, 0, 0);
+  corr = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, corr, 0, 0, 0);
+}
+
 }  // namespace
 
-// grid: partial * pairs + pair, pair = (output-channel block) * (Cin / 64) + (input-channel block)
+// grid: decode_item's, dz the A side and x the B side: pair = (output-channel block) * (Cin / 64) + (input-channel block)
 // partial = (b * bands + band) * segs + seg: rows [16 band, +16) and columns [64 seg, +64) of sample b
 // SX (pp_convt3x3_split_wgrad_nhwc_dev, include/train/pp_convt_train.h: a transposed conv's weight gradient is this one
 // with the roles exchanged, the output gradient in the x role): the scale s multiplies x instead of dz
@@ -84,15 +117,12 @@ __global__ __launch_bounds__(kThreads) void k_conv3x3_wgrad(const float *__restr
                                                            float *__restrict__ ws) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[kLdsBytes];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nci = Cin >> 6, pairs = nci * (Cout >> 6);
-  const int pair = blockIdx.x % pairs, part = blockIdx.x / pairs;
-  const int cob = pair / nci, cib = pair - cob * nci;
-  const int seg = part % segs, band = part / segs % bands, b = part / segs / bands;
-  const int y0 = band * kRb, y1 = min(H, y0 + kRb), xs = seg * kTw, xe = min(W, xs + kTw);
+  const Item it = decode_item(Cin >> 6, Cout >> 6, bands, segs);
+  const int y0 = it.band * kRb, y1 = min(H, y0 + kRb), xs = it.seg * kTw, xe = min(W, xs + kTw);
   const int segw = xe - xs, nsteps = (segw + 15) >> 4;
   const float s = dz_scale ? dz_scale[0] : 1.0f, inv = dz_scale ? dz_scale[1] : 1.0f;
-  const float *xb = x + (int64_t)b * H * W * Cin + cib * 64;
-  const float *db = dz + (int64_t)b * H * W * Cout + cob * 64;
+  const float *xb = x + (int64_t)it.b * H * W * Cin + it.bblk * 64;
+  const float *db = dz + (int64_t)it.b * H * W * Cout + it.ablk * 64;
 
   // the stager's items of this thread, i = tid and tid + 768, 4 channels of one pixel each: x item i is image column
   // xs - 1 + (i >> 4), dz item i column xs + (i >> 4); channels 4 (i & 15) .. +3 of the block.  768 = 48 * 16: the
@@ -130,8 +160,7 @@ __global__ __launch_bounds__(kThreads) void k_conv3x3_wgrad(const float *__restr
   const int q = lane >> 2 & 3, p = lane & 3, c16 = lane >> 4 & 1, kh = lane >> 5;
   const int aoff = (8 * kh + q) * kPix + (coh * 32 + c16 * 16 + 4 * p) * 2;
   const int boff = (8 * kh + q) * kPix + (cih * 32 + c16 * 16 + 4 * p) * 2;
-  // the last step of a row where the partial's width is no multiple of 16: dz is zero past the edge, and x is made
-  // zero there too, so that a NaN of x stays with the taps that read it
+  // the last step of a row where the partial's width is no multiple of 16 (tail_mask)
   const int nv = segw - 16 * (nsteps - 1);
   const bool tail = nv < 16;
   const int rem = nv - 8 * kh;                       // this lane's pixels of that step that are inside
@@ -164,15 +193,12 @@ __global__ __launch_bounds__(kThreads) void k_conv3x3_wgrad(const float *__restr
         if (mask) {
 #pragma unroll
           for (int d = 0; d < 4; ++d) {
-            const unsigned m = (2 * d < rem ? 0xffffu : 0u) | (2 * d + 1 < rem ? 0xffff0000u : 0u);
-            uh[d] &= m;
-            ul[d] &= m;
+            uh[d] &= tail_mask(d, rem);
+            ul[d] &= tail_mask(d, rem);
           }
         }
         const f16x8 bh = __builtin_bit_cast(f16x8, uh), bl = __builtin_bit_cast(f16x8, ul);
-        acc_main[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc_main[kx], 0, 0, 0);
-        acc_corr[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc_corr[kx], 0, 0, 0);
-        acc_corr[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc_corr[kx], 0, 0, 0);
+        mfma3(ah, al, bh, bl, acc_main[kx], acc_corr[kx]);
       }
     }
     if (more) store_rows(y + 2, true, y + 1);
@@ -180,7 +206,7 @@ __global__ __launch_bounds__(kThreads) void k_conv3x3_wgrad(const float *__restr
   }
 
   // accumulator i of lane l: output channel (i & 3) + 8 (i >> 2) + 4 (l >> 5), input channel l & 31 of the tile
-  float *out = ws + ((int64_t)pair * (gridDim.x / pairs) + part) * kPartFloats;
+  float *out = ws + ((int64_t)it.pair * (gridDim.x / it.pairs) + it.part) * kPartFloats;
 #pragma unroll
   for (int kx = 0; kx < 3; ++kx) {
 #pragma unroll
@@ -250,15 +276,12 @@ __global__ __launch_bounds__(kThreads) void k_conv3x3_s2_wgrad(const float *__re
                                                               float *__restrict__ ws) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[kS2LdsBytes];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nci = Cin >> 6, pairs = nci * (Cout >> 6);
-  const int pair = blockIdx.x % pairs, part = blockIdx.x / pairs;
-  const int cob = pair / nci, cib = pair - cob * nci;
-  const int seg = part % segs, band = part / segs % bands, b = part / segs / bands;
-  const int y0 = band * kRb, y1 = min(Ho, y0 + kRb), xs = seg * kS2Tw, xe = min(Wo, xs + kS2Tw);
+  const Item it = decode_item(Cin >> 6, Cout >> 6, bands, segs);
+  const int y0 = it.band * kRb, y1 = min(Ho, y0 + kRb), xs = it.seg * kS2Tw, xe = min(Wo, xs + kS2Tw);
   const int segw = xe - xs, nsteps = (segw + 15) >> 4;
   const float s = dz_scale ? dz_scale[0] : 1.0f, inv = dz_scale ? dz_scale[1] : 1.0f;
-  const float *xb = x + (int64_t)b * H * W * Cin + cib * 64;
-  const float *db = dz + (int64_t)b * Ho * Wo * Cout + cob * 64;
+  const float *xb = x + (int64_t)it.b * H * W * Cin + it.bblk * 64;
+  const float *db = dz + (int64_t)it.b * Ho * Wo * Cout + it.ablk * 64;
 
   // the stager's items of this thread, 4 channels (4 (tid & 15) .. +3 of the block) of one pixel each; pos = tid >> 4
   // in [0, 48).  Of the two x rows staged per dz row: halo column pos of either row (items 0 and 1: one offset, one
@@ -305,8 +328,7 @@ __global__ __launch_bounds__(kThreads) void k_conv3x3_s2_wgrad(const float *__re
   const int q = lane >> 2 & 3, p = lane & 3, c16 = lane >> 4 & 1, kh = lane >> 5;
   const int aoff = (8 * kh + q) * kPix + (coh * 32 + c16 * 16 + 4 * p) * 2;
   const int boff = (8 * kh + q) * kPix + (cih * 32 + c16 * 16 + 4 * p) * 2;
-  // the last step of a row where the partial's width is no multiple of 16: dz is zero past the edge, and x is made
-  // zero there too, so that a NaN of x stays with the taps that read it
+  // the last step of a row where the partial's width is no multiple of 16 (tail_mask)
   const int nv = segw - 16 * (nsteps - 1);
   const bool tail = nv < 16;
   const int rem = nv - 8 * kh;                       // this lane's pixels of that step that are inside
@@ -340,15 +362,12 @@ __global__ __launch_bounds__(kThreads) void k_conv3x3_s2_wgrad(const float *__re
         if (mask) {
 #pragma unroll
           for (int d = 0; d < 4; ++d) {
-            const unsigned m = (2 * d < rem ? 0xffffu : 0u) | (2 * d + 1 < rem ? 0xffff0000u : 0u);
-            uh[d] &= m;
-            ul[d] &= m;
+            uh[d] &= tail_mask(d, rem);
+            ul[d] &= tail_mask(d, rem);
           }
         }
         const f16x8 bh = __builtin_bit_cast(f16x8, uh), bl = __builtin_bit_cast(f16x8, ul);
-        acc_main[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc_main[kx], 0, 0, 0);
-        acc_corr[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc_corr[kx], 0, 0, 0);
-        acc_corr[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc_corr[kx], 0, 0, 0);
+        mfma3(ah, al, bh, bl, acc_main[kx], acc_corr[kx]);
       }
     }
     if (more) store_rows(2 * y + 2, y + 1);
@@ -356,7 +375,7 @@ __global__ __launch_bounds__(kThreads) void k_conv3x3_s2_wgrad(const float *__re
   }
 
   // accumulator i of lane l: output channel (i & 3) + 8 (i >> 2) + 4 (l >> 5), input channel l & 31 of the tile
-  float *out = ws + ((int64_t)pair * (gridDim.x / pairs) + part) * kPartFloats;
+  float *out = ws + ((int64_t)it.pair * (gridDim.x / it.pairs) + it.part) * kPartFloats;
 #pragma unroll
   for (int kx = 0; kx < 3; ++kx) {
 #pragma unroll
@@ -392,7 +411,7 @@ static_assert(kS4LdsBytes == 102400 && kThreads == 3 * kS4Tw * 16, "one dy item 
 
 }  // namespace
 
-// grid: partial * pairs + pair, pair = (Ci block) * (Co / 64) + (Co block): dw's order, k_conv3x3_wgrad_sum's
+// grid: decode_item's, x the A side and dy the B side: pair = (Ci block) * (Co / 64) + (Co block), dw's order
 // partial = (b * bands + band) * segs + seg: x rows [32 band, +32) and x columns [16 seg, +16) of sample b
 __global__ __launch_bounds__(kThreads) void k_convt3x3_s4_wgrad(const float *__restrict__ x,
                                                                const float *__restrict__ dy, int H, int W, int Ho,
@@ -401,14 +420,11 @@ __global__ __launch_bounds__(kThreads) void k_convt3x3_s4_wgrad(const float *__r
                                                                float *__restrict__ ws) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[kS4LdsBytes];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nco = Co >> 6, pairs = nco * (Ci >> 6);
-  const int pair = blockIdx.x % pairs, part = blockIdx.x / pairs;
-  const int cib = pair / nco, cob = pair - cib * nco;
-  const int seg = part % segs, band = part / segs % bands, b = part / segs / bands;
-  const int y0 = band * kS4Rb, y1 = min(H, y0 + kS4Rb), xs = seg * kS4Tw, xe = min(W, xs + kS4Tw);
+  const Item it = decode_item(Co >> 6, Ci >> 6, bands, segs);
+  const int y0 = it.band * kS4Rb, y1 = min(H, y0 + kS4Rb), xs = it.seg * kS4Tw, xe = min(W, xs + kS4Tw);
   const float s = dy_scale ? dy_scale[0] : 1.0f, inv = dy_scale ? dy_scale[1] : 1.0f;
-  const float *xb = x + (int64_t)b * H * W * Ci + cib * 64;
-  const float *db = dy + (int64_t)b * Ho * Wo * Co + cob * 64;
+  const float *xb = x + (int64_t)it.b * H * W * Ci + it.ablk * 64;
+  const float *db = dy + (int64_t)it.b * Ho * Wo * Co + it.bblk * 64;
 
   // the stager's items of this thread, 4 channels (4 (tid & 15) .. +3 of the block) of one pixel each; pos = tid >> 4
   // in [0, 48) is (kx, j) = (pos / 16, pos % 16): dy column 4 (xs + j) - 1 + kx of each of the three live rows, and
@@ -468,16 +484,14 @@ __global__ __launch_bounds__(kThreads) void k_convt3x3_s4_wgrad(const float *__r
     for (int kx = 0; kx < 3; ++kx) {
       const f16x8 bh = __builtin_bit_cast(f16x8, read_tr8(cur + boff + kx * kS4Run));
       const f16x8 bl = __builtin_bit_cast(f16x8, read_tr8(cur + boff + kx * kS4Run + kLo));
-      acc_main[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc_main[kx], 0, 0, 0);
-      acc_corr[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc_corr[kx], 0, 0, 0);
-      acc_corr[kx] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc_corr[kx], 0, 0, 0);
+      mfma3(ah, al, bh, bl, acc_main[kx], acc_corr[kx]);
     }
     if (more) store_row(lds + ((y - y0 + 1) & 1) * kS4Buf);
     __syncthreads();
   }
 
   // accumulator i of lane l: x channel (i & 3) + 8 (i >> 2) + 4 (l >> 5), dy channel l & 31 of the tile
-  float *out = ws + ((int64_t)pair * (gridDim.x / pairs) + part) * kPartFloats;
+  float *out = ws + ((int64_t)it.pair * (gridDim.x / it.pairs) + it.part) * kPartFloats;
 #pragma unroll
   for (int kx = 0; kx < 3; ++kx) {
 #pragma unroll
@@ -490,23 +504,106 @@ __global__ __launch_bounds__(kThreads) void k_convt3x3_s4_wgrad(const float *__r
 
 namespace {
 
-// the partials of one channel block and the channel blocks; false for arguments the entry point refuses
-bool wgrad_plan(int batch, int height, int width, int in_channels, int out_channels, int64_t *nparts, int64_t *pairs,
-                bool *too_large) {
-  *too_large = false;
-  if (batch < 1 || height < 1 || width < 1 || in_channels < 64 || in_channels % 64 || out_channels < 64 ||
-      out_channels % 64 || in_channels > 16384 || out_channels > 16384)
-    return false;
-  const int bands = (height + kRb - 1) / kRb, segs = (width + kTw - 1) / kTw;
-  *nparts = (int64_t)batch * bands * segs;
-  *pairs = (int64_t)(in_channels / 64) * (out_channels / 64);
-  // the kernels index one sample with 32-bit offsets, the grid has 2^31 - 1 workgroups at most
-  if ((int64_t)height * width * std::max(in_channels, out_channels) > 0x7fffffff || *nparts > 0x7fffffff ||
-      *nparts * *pairs > 0x7fffffff) {
-    *too_large = true;
-    return false;
+// what an entry point's arguments come to.  `big` is the tensor in the stride-1 kernel's x role -- the larger one, whose
+// extent, channel count and 32-bit offsets are checked: x of a conv, dy of a transposed conv -- with `other_c` channels
+// on the other tensor; the partials tile the walked tensor (dz of a conv, x of a transposed conv), rb rows x tw columns
+// each.  valid: what the entry point checks beyond that holds
+struct Geom {
+  bool valid;
+  int big_h, big_w, big_c, other_c, walk_h, walk_w, rb, tw;
+};
+
+Geom conv_geom(int height, int width, int in_channels, int out_channels, int stride) {
+  const int ho = stride == 2 ? (height + 1) / 2 : height, wo = stride == 2 ? (width + 1) / 2 : width;
+  return {true, height, width, in_channels, out_channels, ho, wo, kRb, stride == 2 ? kS2Tw : kTw};
+}
+
+// the transposed convs' weight gradient (include/train/pp_convt_train.h): the kernels with the roles exchanged -- x
+// [B][H][W][Ci] in the dz role, dy [B][Ho][Wo][Co] in the x role and carrying the scale
+Geom convt_geom(int height, int width, int in_channels, int out_channels, int stride, int out_height, int out_width) {
+  const int64_t s = stride;
+  const bool valid = (stride == 1 || stride == 2 || stride == 4) && height >= 1 && width >= 1 &&
+                     out_height >= s * height - s + 1 && out_height <= s * height && out_width >= s * width - s + 1 &&
+                     out_width <= s * width;
+  return {valid, out_height, out_width, out_channels, in_channels, height, width, stride == 4 ? kS4Rb : kRb,
+          stride == 4 ? kS4Tw : stride == 2 ? kS2Tw : kTw};
+}
+
+// the partials of one channel block and the channel blocks; ok is false for arguments the entry point refuses
+struct Plan {
+  bool ok = false, too_large = false;
+  int bands = 0, segs = 0, inner = 0;             // inner: dw's second extent, k_conv3x3_wgrad_sum's Cin
+  int64_t nparts = 0, pairs = 0;
+  int64_t bytes() const { return nparts * pairs * kPartFloats * (int64_t)sizeof(float); }
+};
+
+Plan wgrad_plan(int batch, const Geom &g) {
+  Plan p;
+  if (!g.valid || batch < 1 || g.big_h < 1 || g.big_w < 1 || g.big_c < 64 || g.big_c % 64 || g.other_c < 64 ||
+      g.other_c % 64 || g.big_c > 16384 || g.other_c > 16384)
+    return p;
+  p.pairs = (int64_t)(g.big_c / 64) * (g.other_c / 64);
+  // the kernels index one sample with 32-bit offsets, the grid has 2^31 - 1 workgroups at most; the count is checked
+  // for stride-1 partials on the big tensor too (no fewer than a stride-2 conv's own: ceil(Ho / 16) <= ceil(H / 16),
+  // ceil(Wo / 32) = ceil(W / 64)), then for the walked tensor's
+  const int64_t big_parts = (int64_t)batch * ((g.big_h + kRb - 1) / kRb) * ((g.big_w + kTw - 1) / kTw);
+  p.bands = (g.walk_h + g.rb - 1) / g.rb, p.segs = (g.walk_w + g.tw - 1) / g.tw;
+  p.nparts = (int64_t)batch * p.bands * p.segs;
+  p.inner = g.big_c;
+  p.too_large = (int64_t)g.big_h * g.big_w * std::max(g.big_c, g.other_c) > 0x7fffffff || big_parts > 0x7fffffff ||
+                big_parts * p.pairs > 0x7fffffff || p.nparts > 0x7fffffff || p.nparts * p.pairs > 0x7fffffff;
+  p.ok = !p.too_large;
+  return p;
+}
+
+// what every entry point does once its plan is made: the refusals in their order -- NULL, too large, `refuse` (which
+// sets the message that names the entry point's requirements), the workspace -- then `partials`, which launches the
+// entry point's kernel on (grid, stream, workspace), and the sum.  a and b: the two activations
+template <class Refuse, class Partials>
+int wgrad_run(const char *fn, const char *bytes_fn, const char *kernels, pp_ctx_t *ctx, void *stream_, const float *a,
+              const float *b, const float *scale, void *workspace_dev, int64_t workspace_bytes, float *dw_dev,
+              const Plan &p, Refuse &&refuse, Partials &&partials) {
+  if (!ctx || !a || !b || !workspace_dev || !dw_dev) {
+    set_error("%s: NULL argument", fn);
+    return PP_ERR_VALUE;
   }
-  return true;
+  if (p.too_large) {
+    set_error("%s: tensor too large", fn);
+    return PP_ERR_VALUE;
+  }
+  if (!p.ok ||
+      ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(workspace_dev) |
+        reinterpret_cast<uintptr_t>(dw_dev)) & 15) ||
+      (reinterpret_cast<uintptr_t>(scale) & 3)) {
+    refuse();
+    return PP_ERR_VALUE;
+  }
+  if (workspace_bytes < p.bytes()) {
+    set_error("%s: the workspace has %lld bytes, %s asks for %lld", fn, (long long)workspace_bytes, bytes_fn,
+              (long long)p.bytes());
+    return PP_ERR_VALUE;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  float *ws = static_cast<float *>(workspace_dev);
+  return launch_on_device(ctx, kernels, [&] {
+    partials(dim3((unsigned)(p.nparts * p.pairs)), st, ws);
+    hipLaunchKernelGGL(k_conv3x3_wgrad_sum, dim3((unsigned)(p.pairs * (kPartFloats / 256))), dim3(256), 0, st, ws,
+                       (int)p.nparts, p.inner, dw_dev);
+  });
+}
+
+// a conv's entry point, stride 1 or 2
+template <class Partials>
+int conv_wgrad_run(const char *fn, const char *bytes_fn, const char *kernels, pp_ctx_t *ctx, void *stream_,
+                   const float *x_dev, const float *dz_dev, int batch, int height, int width, int in_channels,
+                   int out_channels, const float *dz_scale_dev, void *workspace_dev, int64_t workspace_bytes,
+                   float *dw_dev, const Plan &p, Partials &&partials) {
+  return wgrad_run(fn, bytes_fn, kernels, ctx, stream_, x_dev, dz_dev, dz_scale_dev, workspace_dev, workspace_bytes,
+                   dw_dev, p, [&] {
+    set_error("%s: need in_channels and out_channels multiples of 64 (at most 16384), 16-byte aligned x, dz, "
+              "workspace and dw, a 4-byte aligned dz_scale (batch=%d %dx%d in=%d out=%d)", fn, batch, height, width,
+              in_channels, out_channels);
+  }, partials);
 }
 
 }  // namespace
@@ -517,155 +614,54 @@ using namespace pp;
 
 extern "C" int64_t pp_conv3x3_split_wgrad_workspace_bytes(int batch, int height, int width, int in_channels,
                                                           int out_channels) {
-  int64_t nparts = 0, pairs = 0;
-  bool too_large = false;
-  if (!wgrad_plan(batch, height, width, in_channels, out_channels, &nparts, &pairs, &too_large)) return -1;
-  return nparts * pairs * kPartFloats * (int64_t)sizeof(float);
+  const Plan p = wgrad_plan(batch, conv_geom(height, width, in_channels, out_channels, 1));
+  return p.ok ? p.bytes() : -1;
 }
 
 extern "C" int pp_conv3x3_split_wgrad_nhwc_dev(pp_ctx_t *ctx, void *stream_, const float *x_dev, const float *dz_dev,
                                                int batch, int height, int width, int in_channels, int out_channels,
                                                const float *dz_scale_dev, void *workspace_dev,
                                                int64_t workspace_bytes, float *dw_dev) {
-  static const char fn[] = "pp_conv3x3_split_wgrad_nhwc_dev";
-  if (!ctx || !x_dev || !dz_dev || !workspace_dev || !dw_dev) {
-    set_error("%s: NULL argument", fn);
-    return PP_ERR_VALUE;
-  }
-  int64_t nparts = 0, pairs = 0;
-  bool too_large = false;
-  const bool ok = wgrad_plan(batch, height, width, in_channels, out_channels, &nparts, &pairs, &too_large);
-  if (too_large) {
-    set_error("%s: tensor too large", fn);
-    return PP_ERR_VALUE;
-  }
-  if (!ok ||
-      ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(dz_dev) |
-        reinterpret_cast<uintptr_t>(workspace_dev) | reinterpret_cast<uintptr_t>(dw_dev)) & 15) ||
-      (reinterpret_cast<uintptr_t>(dz_scale_dev) & 3)) {
-    set_error("%s: need in_channels and out_channels multiples of 64 (at most 16384), 16-byte aligned x, dz, "
-              "workspace and dw, a 4-byte aligned dz_scale (batch=%d %dx%d in=%d out=%d)", fn, batch, height, width,
-              in_channels, out_channels);
-    return PP_ERR_VALUE;
-  }
-  const int64_t need = nparts * pairs * kPartFloats * (int64_t)sizeof(float);
-  if (workspace_bytes < need) {
-    set_error("%s: the workspace has %lld bytes, pp_conv3x3_split_wgrad_workspace_bytes asks for %lld", fn,
-              (long long)workspace_bytes, (long long)need);
-    return PP_ERR_VALUE;
-  }
-  const int bands = (height + kRb - 1) / kRb, segs = (width + kTw - 1) / kTw;
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  float *ws = static_cast<float *>(workspace_dev);
-  return launch_on_device(ctx, "k_conv3x3_wgrad / k_conv3x3_wgrad_sum", [&] {
-    hipLaunchKernelGGL(k_conv3x3_wgrad<false>, dim3((unsigned)(nparts * pairs)), dim3(kThreads), 0, st, x_dev, dz_dev, height,
-                       width, in_channels, out_channels, bands, segs, dz_scale_dev, ws);
-    hipLaunchKernelGGL(k_conv3x3_wgrad_sum, dim3((unsigned)(pairs * (kPartFloats / 256))), dim3(256), 0, st, ws,
-                       (int)nparts, in_channels, dw_dev);
+  const Plan p = wgrad_plan(batch, conv_geom(height, width, in_channels, out_channels, 1));
+  return conv_wgrad_run("pp_conv3x3_split_wgrad_nhwc_dev", "pp_conv3x3_split_wgrad_workspace_bytes",
+                        "k_conv3x3_wgrad / k_conv3x3_wgrad_sum", ctx, stream_, x_dev, dz_dev, batch, height, width,
+                        in_channels, out_channels, dz_scale_dev, workspace_dev, workspace_bytes, dw_dev, p,
+                        [&](dim3 grid, hipStream_t st, float *ws) {
+    hipLaunchKernelGGL(k_conv3x3_wgrad<false>, grid, dim3(kThreads), 0, st, x_dev, dz_dev, height, width, in_channels,
+                       out_channels, p.bands, p.segs, dz_scale_dev, ws);
   });
 }
 
 // ---- the stride-2 form: the stride-1 pair's checks on x's extent, the partials counted on dz's
 
-namespace {
-
-bool wgrad_s2_plan(int batch, int height, int width, int in_channels, int out_channels, int64_t *nparts,
-                   int64_t *pairs, bool *too_large) {
-  if (!wgrad_plan(batch, height, width, in_channels, out_channels, nparts, pairs, too_large)) return false;
-  const int ho = (height + 1) / 2, wo = (width + 1) / 2;
-  *nparts = (int64_t)batch * ((ho + kRb - 1) / kRb) * ((wo + kS2Tw - 1) / kS2Tw);
-  // ceil(Ho / 16) <= ceil(H / 16) and ceil(Wo / 32) = ceil(W / 64): no more partials than the stride-1 plan has checked
-  return true;
-}
-
-}  // namespace
-
 extern "C" int64_t pp_conv3x3_s2_split_wgrad_workspace_bytes(int batch, int height, int width, int in_channels,
                                                              int out_channels) {
-  int64_t nparts = 0, pairs = 0;
-  bool too_large = false;
-  if (!wgrad_s2_plan(batch, height, width, in_channels, out_channels, &nparts, &pairs, &too_large)) return -1;
-  return nparts * pairs * kPartFloats * (int64_t)sizeof(float);
+  const Plan p = wgrad_plan(batch, conv_geom(height, width, in_channels, out_channels, 2));
+  return p.ok ? p.bytes() : -1;
 }
 
 extern "C" int pp_conv3x3_s2_split_wgrad_nhwc_dev(pp_ctx_t *ctx, void *stream_, const float *x_dev,
                                                   const float *dz_dev, int batch, int height, int width,
                                                   int in_channels, int out_channels, const float *dz_scale_dev,
                                                   void *workspace_dev, int64_t workspace_bytes, float *dw_dev) {
-  static const char fn[] = "pp_conv3x3_s2_split_wgrad_nhwc_dev";
-  if (!ctx || !x_dev || !dz_dev || !workspace_dev || !dw_dev) {
-    set_error("%s: NULL argument", fn);
-    return PP_ERR_VALUE;
-  }
-  int64_t nparts = 0, pairs = 0;
-  bool too_large = false;
-  const bool ok = wgrad_s2_plan(batch, height, width, in_channels, out_channels, &nparts, &pairs, &too_large);
-  if (too_large) {
-    set_error("%s: tensor too large", fn);
-    return PP_ERR_VALUE;
-  }
-  if (!ok ||
-      ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(dz_dev) |
-        reinterpret_cast<uintptr_t>(workspace_dev) | reinterpret_cast<uintptr_t>(dw_dev)) & 15) ||
-      (reinterpret_cast<uintptr_t>(dz_scale_dev) & 3)) {
-    set_error("%s: need in_channels and out_channels multiples of 64 (at most 16384), 16-byte aligned x, dz, "
-              "workspace and dw, a 4-byte aligned dz_scale (batch=%d %dx%d in=%d out=%d)", fn, batch, height, width,
-              in_channels, out_channels);
-    return PP_ERR_VALUE;
-  }
-  const int64_t need = nparts * pairs * kPartFloats * (int64_t)sizeof(float);
-  if (workspace_bytes < need) {
-    set_error("%s: the workspace has %lld bytes, pp_conv3x3_s2_split_wgrad_workspace_bytes asks for %lld", fn,
-              (long long)workspace_bytes, (long long)need);
-    return PP_ERR_VALUE;
-  }
-  const int ho = (height + 1) / 2, wo = (width + 1) / 2;
-  const int bands = (ho + kRb - 1) / kRb, segs = (wo + kS2Tw - 1) / kS2Tw;
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  float *ws = static_cast<float *>(workspace_dev);
-  return launch_on_device(ctx, "k_conv3x3_s2_wgrad / k_conv3x3_wgrad_sum", [&] {
-    hipLaunchKernelGGL(k_conv3x3_s2_wgrad<false>, dim3((unsigned)(nparts * pairs)), dim3(kThreads), 0, st, x_dev, dz_dev,
-                       height, width, ho, wo, in_channels, out_channels, bands, segs, dz_scale_dev, ws);
-    hipLaunchKernelGGL(k_conv3x3_wgrad_sum, dim3((unsigned)(pairs * (kPartFloats / 256))), dim3(256), 0, st, ws,
-                       (int)nparts, in_channels, dw_dev);
+  const Geom g = conv_geom(height, width, in_channels, out_channels, 2);
+  const Plan p = wgrad_plan(batch, g);
+  return conv_wgrad_run("pp_conv3x3_s2_split_wgrad_nhwc_dev", "pp_conv3x3_s2_split_wgrad_workspace_bytes",
+                        "k_conv3x3_s2_wgrad / k_conv3x3_wgrad_sum", ctx, stream_, x_dev, dz_dev, batch, height, width,
+                        in_channels, out_channels, dz_scale_dev, workspace_dev, workspace_bytes, dw_dev, p,
+                        [&](dim3 grid, hipStream_t st, float *ws) {
+    hipLaunchKernelGGL(k_conv3x3_s2_wgrad<false>, grid, dim3(kThreads), 0, st, x_dev, dz_dev, height, width, g.walk_h,
+                       g.walk_w, in_channels, out_channels, p.bands, p.segs, dz_scale_dev, ws);
   });
 }
 
-// ---- the transposed convs' weight gradient (include/train/pp_convt_train.h): the kernels above with the roles
-// exchanged -- x [B][H][W][Ci] in the dz role, dy [B][Ho][Wo][Co] in the x role and carrying the scale
-
-namespace {
-
-bool convt_wgrad_plan(int batch, int height, int width, int in_channels, int out_channels, int stride, int out_height,
-                      int out_width, int64_t *nparts, int64_t *pairs, bool *too_large) {
-  *too_large = false;
-  if ((stride != 1 && stride != 2 && stride != 4) || height < 1 || width < 1) return false;
-  const int64_t s = stride;
-  if (out_height < s * height - s + 1 || out_height > s * height || out_width < s * width - s + 1 ||
-      out_width > s * width)
-    return false;
-  // dy is the larger tensor: the channel counts, its extent and the 32-bit offsets are checked on it
-  if (!wgrad_plan(batch, out_height, out_width, out_channels, in_channels, nparts, pairs, too_large)) return false;
-  const int rb = stride == 4 ? kS4Rb : kRb, tw = stride == 4 ? kS4Tw : stride == 2 ? kS2Tw : kTw;
-  *nparts = (int64_t)batch * ((height + rb - 1) / rb) * ((width + tw - 1) / tw);
-  if (*nparts > 0x7fffffff || *nparts * *pairs > 0x7fffffff) {
-    *too_large = true;
-    return false;
-  }
-  return true;
-}
-
-}  // namespace
+// ---- the transposed convs' weight gradient (convt_geom)
 
 extern "C" int64_t pp_convt3x3_split_wgrad_workspace_bytes(int batch, int height, int width, int in_channels,
                                                            int out_channels, int stride, int out_height,
                                                            int out_width) {
-  int64_t nparts = 0, pairs = 0;
-  bool too_large = false;
-  if (!convt_wgrad_plan(batch, height, width, in_channels, out_channels, stride, out_height, out_width, &nparts,
-                        &pairs, &too_large))
-    return -1;
-  return nparts * pairs * kPartFloats * (int64_t)sizeof(float);
+  const Plan p = wgrad_plan(batch, convt_geom(height, width, in_channels, out_channels, stride, out_height, out_width));
+  return p.ok ? p.bytes() : -1;
 }
 
 extern "C" int pp_convt3x3_split_wgrad_nhwc_dev(pp_ctx_t *ctx, void *stream_, const float *x_dev, const float *dy_dev,
@@ -673,51 +669,24 @@ extern "C" int pp_convt3x3_split_wgrad_nhwc_dev(pp_ctx_t *ctx, void *stream_, co
                                                 int stride, int out_height, int out_width, const float *dy_scale_dev,
                                                 void *workspace_dev, int64_t workspace_bytes, float *dw_dev) {
   static const char fn[] = "pp_convt3x3_split_wgrad_nhwc_dev";
-  if (!ctx || !x_dev || !dy_dev || !workspace_dev || !dw_dev) {
-    set_error("%s: NULL argument", fn);
-    return PP_ERR_VALUE;
-  }
-  int64_t nparts = 0, pairs = 0;
-  bool too_large = false;
-  const bool ok = convt_wgrad_plan(batch, height, width, in_channels, out_channels, stride, out_height, out_width,
-                                   &nparts, &pairs, &too_large);
-  if (too_large) {
-    set_error("%s: tensor too large", fn);
-    return PP_ERR_VALUE;
-  }
-  if (!ok ||
-      ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(dy_dev) |
-        reinterpret_cast<uintptr_t>(workspace_dev) | reinterpret_cast<uintptr_t>(dw_dev)) & 15) ||
-      (reinterpret_cast<uintptr_t>(dy_scale_dev) & 3)) {
+  const Plan p = wgrad_plan(batch, convt_geom(height, width, in_channels, out_channels, stride, out_height, out_width));
+  return wgrad_run(fn, "pp_convt3x3_split_wgrad_workspace_bytes",
+                   "k_conv3x3_wgrad<SX> / k_conv3x3_s2_wgrad<SX> / k_convt3x3_s4_wgrad / k_conv3x3_wgrad_sum", ctx,
+                   stream_, x_dev, dy_dev, dy_scale_dev, workspace_dev, workspace_bytes, dw_dev, p, [&] {
     set_error("%s: need stride 1, 2 or 4, out_height in [S H - S + 1, S H] and out_width likewise, in_channels and "
               "out_channels multiples of 64 (at most 16384), 16-byte aligned x, dy, workspace and dw, a 4-byte aligned "
               "dy_scale (batch=%d x %dx%d dy %dx%d stride=%d in=%d out=%d)", fn, batch, height, width, out_height,
               out_width, stride, in_channels, out_channels);
-    return PP_ERR_VALUE;
-  }
-  const int64_t need = nparts * pairs * kPartFloats * (int64_t)sizeof(float);
-  if (workspace_bytes < need) {
-    set_error("%s: the workspace has %lld bytes, pp_convt3x3_split_wgrad_workspace_bytes asks for %lld", fn,
-              (long long)workspace_bytes, (long long)need);
-    return PP_ERR_VALUE;
-  }
-  const int rb = stride == 4 ? kS4Rb : kRb, tw = stride == 4 ? kS4Tw : stride == 2 ? kS2Tw : kTw;
-  const int bands = (height + rb - 1) / rb, segs = (width + tw - 1) / tw;
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  float *ws = static_cast<float *>(workspace_dev);
-  const dim3 grid((unsigned)(nparts * pairs));
-  // the conv kernels' x is dy (their Cin = out_channels), their dz is x (their Cout = in_channels)
-  return launch_on_device(ctx, "k_conv3x3_wgrad<SX> / k_conv3x3_s2_wgrad<SX> / k_convt3x3_s4_wgrad / k_conv3x3_wgrad_sum", [&] {
+  }, [&](dim3 grid, hipStream_t st, float *ws) {
+    // the conv kernels' x is dy (their Cin = out_channels), their dz is x (their Cout = in_channels)
     if (stride == 1)
       hipLaunchKernelGGL(k_conv3x3_wgrad<true>, grid, dim3(kThreads), 0, st, dy_dev, x_dev, height, width, out_channels,
-                         in_channels, bands, segs, dy_scale_dev, ws);
+                         in_channels, p.bands, p.segs, dy_scale_dev, ws);
     else if (stride == 2)
       hipLaunchKernelGGL(k_conv3x3_s2_wgrad<true>, grid, dim3(kThreads), 0, st, dy_dev, x_dev, out_height, out_width,
-                         height, width, out_channels, in_channels, bands, segs, dy_scale_dev, ws);
+                         height, width, out_channels, in_channels, p.bands, p.segs, dy_scale_dev, ws);
     else
       hipLaunchKernelGGL(k_convt3x3_s4_wgrad, grid, dim3(kThreads), 0, st, x_dev, dy_dev, height, width, out_height,
-                         out_width, in_channels, out_channels, bands, segs, dy_scale_dev, ws);
-    hipLaunchKernelGGL(k_conv3x3_wgrad_sum, dim3((unsigned)(pairs * (kPartFloats / 256))), dim3(256), 0, st, ws,
-                       (int)nparts, out_channels, dw_dev);
+                         out_width, in_channels, out_channels, p.bands, p.segs, dy_scale_dev, ws);
   });
 }

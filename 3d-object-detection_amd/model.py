@@ -221,13 +221,41 @@ def _split_pack(weight, into=None, s2=False):
     return fwd, dgrad
 
 
-def _conv_split_bare(x, ws, cout, x_scale=None):
-    """pp_conv3x3_split_bare_nhwc_dev (include/pp_conv_train.h): ``_conv_split``'s layer without an epilogue, the
-    bare conv output, into a new channels-last tensor.  ``x_scale``: None, or the device pair ``{s, 1/s}`` of
+#: the bare split-fp16 conv of stride s (include/pp_conv_train.h, include/train/pp_conv_s2_train.h, pp_convt_train.h)
+_CONV_BARE = {1: "pp_conv3x3_split_bare_nhwc_dev", 2: "pp_conv3x3_s2_split_bare_nhwc_dev",
+              4: "pp_conv3x3_s4_split_bare_nhwc_dev"}
+
+
+def _conv_bare(x, ws, cout, stride=1, x_scale=None):
+    """The bare output of Conv2d(3x3, ``stride`` 1, 2 or 4, padding 1) of the channels-last ``x``, without an epilogue,
+    into a new channels-last tensor: the forward of a training conv and the data gradient of a transposed conv.
+    ``ws``: the split operand (``_split_filter``'s layout).  ``x_scale``: None, or the device pair ``{s, 1/s}`` of
     ``_pow2_scale``: x is multiplied by s on its way in and the output by 1/s."""
     B, C, H, W = x.shape
-    out = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    _call("pp_conv3x3_split_bare_nhwc_dev", x.device, _vp(x), B, H, W, C, _vp(ws), cout, _vp(x_scale), _vp(out), cout, 0)
+    out = torch.empty((B, cout, (H + stride - 1) // stride, (W + stride - 1) // stride), dtype=torch.float32,
+                      device=x.device, memory_format=torch.channels_last)
+    slice_args = () if stride == 4 else (cout, 0)       # the stride-4 entry point writes whole tensors only
+    _call(_CONV_BARE[stride], x.device, _vp(x), B, H, W, C, _vp(ws), cout, _vp(x_scale), _vp(out), *slice_args)
+    return out
+
+
+def _convt_bare(x, ws, cout, stride, out_hw, x_scale=None):
+    """The bare output [B,cout,*out_hw] of ConvTranspose2d(3x3, ``stride`` 1, 2 or 4, padding 1) of the channels-last
+    ``x``: the forward of a transposed training conv and the data gradient of a conv (include/train/pp_convt_train.h).
+    Stride 1 is the stride-1 bare conv, ``ws`` being the flipped operand; stride 2 the stride-2 conv's data gradient
+    kernel; stride 4 pp_convt3x3_s4_split_bare_nhwc_dev, both with ``_convt_split_filter``'s operand.  ``x_scale`` as
+    in ``_conv_bare``."""
+    if stride == 1:
+        return _conv_bare(x, ws, cout, 1, x_scale)
+    B, C, H, W = x.shape
+    ho, wo = out_hw
+    out = torch.empty((B, cout, ho, wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    if stride == 2:
+        _call("pp_conv3x3_s2_split_dgrad_nhwc_dev", x.device, _vp(x), B, H, W, C, _vp(ws), ho, wo, cout, _vp(x_scale),
+              _vp(out))
+    else:
+        _call("pp_convt3x3_s4_split_bare_nhwc_dev", x.device, _vp(x), B, H, W, C, _vp(ws), cout, ho, wo, _vp(x_scale),
+              _vp(out))
     return out
 
 
@@ -238,117 +266,33 @@ def _pow2_scale(x):
     return scale
 
 
-def _wgrad_split(x, dz, dz_scale, fused):
-    """pp_conv3x3_split_wgrad_nhwc_dev (include/train/pp_conv_wgrad.h): the weight gradient [Cout,Cin,3,3] of the
-    stride-1 3x3 conv from its channels-last input ``x`` and output gradient ``dz``, as they lie.  ``dz_scale``:
-    ``_pow2_scale(dz)``.  ``fused``: the layer's ``_FusedConv``, which keeps the split-K workspace."""
+def _wgrad_split(x, dz, stride, transposed, dz_scale, fused):
+    """The split-K weight gradient of the 3x3, padding-1 conv of ``stride`` 1 or 2 ([Cout,Cin,3,3]:
+    include/train/pp_conv_wgrad.h, pp_conv_s2_train.h) or, ``transposed``, of the transposed conv of stride 1, 2 or 4
+    ([Cin,Cout,3,3]: pp_convt_train.h) from its channels-last input ``x`` and output gradient ``dz``, as they lie.
+    ``dz_scale``: ``_pow2_scale(dz)``.  ``fused``: the layer's ``_FusedConv``, which keeps the split-K workspace."""
     B, C, H, W = x.shape
-    cout = dz.shape[1]
-    nbytes = _lib.lib().pp_conv3x3_split_wgrad_workspace_bytes(B, H, W, C, cout)
-    if nbytes < 0:
-        raise ValueError(f"pp_conv3x3_split_wgrad_nhwc_dev does not take x {tuple(x.shape)}, dz {tuple(dz.shape)}")
+    cout, ho, wo = dz.shape[1:]
+    # the entry point's stem, what it takes between the channel counts and the scale, and dw's shape
+    if transposed:
+        name, geometry, dw_shape = "pp_convt3x3_split_wgrad", (stride, ho, wo), (C, cout, 3, 3)
+    else:
+        name, geometry, dw_shape = ("pp_conv3x3_split_wgrad", "pp_conv3x3_s2_split_wgrad")[stride - 1], (), (cout, C, 3, 3)
+    nbytes = getattr(_lib.lib(), name + "_workspace_bytes")(B, H, W, C, cout, *geometry)
+    if nbytes < 0 or (not transposed and stride == 2 and (ho, wo) != ((H + 1) // 2, (W + 1) // 2)):
+        raise ValueError(f"{name}_nhwc_dev does not take x {tuple(x.shape)}, "
+                         + (f"dy {tuple(dz.shape)}, stride {stride}" if transposed else f"dz {tuple(dz.shape)}"))
     ws = fused.wgrad_workspace(nbytes, x.device)
-    dw = torch.empty((cout, C, 3, 3), dtype=torch.float32, device=x.device)
-    _call("pp_conv3x3_split_wgrad_nhwc_dev", x.device, _vp(x), _vp(dz), B, H, W, C, cout, _vp(dz_scale), _vp(ws),
-          nbytes, _vp(dw))
+    dw = torch.empty(dw_shape, dtype=torch.float32, device=x.device)
+    _call(name + "_nhwc_dev", x.device, _vp(x), _vp(dz), B, H, W, C, cout, *geometry, _vp(dz_scale), _vp(ws), nbytes,
+          _vp(dw))
     return dw
 
 
-def _wgrad_miopen(dz, x, weight):
-    """MIOpen's weight gradient of the stride-1, padding-1 3x3 conv: ``_Conv3x3Train``'s without ``split_wgrad``."""
-    return torch.ops.aten.convolution_backward(dz, x, weight, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1,
+def _wgrad_miopen(dz, x, weight, stride):
+    """MIOpen's weight gradient of the 3x3, padding-1 conv of ``stride``: ``_ConvTrain``'s without ``split_wgrad``."""
+    return torch.ops.aten.convolution_backward(dz, x, weight, None, (stride, stride), (1, 1), (1, 1), False, (0, 0), 1,
                                                (False, True, False))[1]
-
-
-def _conv_s2_split_bare(x, ws, cout, x_scale=None):
-    """pp_conv3x3_s2_split_bare_nhwc_dev (include/train/pp_conv_s2_train.h): the bare output of Conv2d(3x3, stride 2,
-    padding 1) of the channels-last ``x`` into a new channels-last tensor; ``ws`` and ``x_scale`` as in
-    ``_conv_split_bare``."""
-    B, C, H, W = x.shape
-    out = torch.empty((B, cout, (H + 1) // 2, (W + 1) // 2), dtype=torch.float32, device=x.device,
-                      memory_format=torch.channels_last)
-    _call("pp_conv3x3_s2_split_bare_nhwc_dev", x.device, _vp(x), B, H, W, C, _vp(ws), cout, _vp(x_scale), _vp(out),
-          cout, 0)
-    return out
-
-
-def _dgrad_s2_split(dz, ws, cin, height, width, dz_scale=None):
-    """pp_conv3x3_s2_split_dgrad_nhwc_dev: the data gradient [B,cin,height,width] of that conv from the channels-last
-    ``dz``, a transposed conv with ``ws`` from ``_split_pack(..., s2=True)`` (``_convt_split_filter`` of the conv
-    weight); ``dz_scale``: ``_pow2_scale(dz)``."""
-    B, cout, ho, wo = dz.shape
-    dx = torch.empty((B, cin, height, width), dtype=torch.float32, device=dz.device, memory_format=torch.channels_last)
-    _call("pp_conv3x3_s2_split_dgrad_nhwc_dev", dz.device, _vp(dz), B, ho, wo, cout, _vp(ws), height, width, cin,
-          _vp(dz_scale), _vp(dx))
-    return dx
-
-
-def _wgrad_s2_split(x, dz, dz_scale, fused):
-    """pp_conv3x3_s2_split_wgrad_nhwc_dev: ``_wgrad_split`` for the stride-2 conv, ``dz`` at half of ``x``'s extent."""
-    B, C, H, W = x.shape
-    cout = dz.shape[1]
-    nbytes = _lib.lib().pp_conv3x3_s2_split_wgrad_workspace_bytes(B, H, W, C, cout)
-    if nbytes < 0 or tuple(dz.shape[2:]) != ((H + 1) // 2, (W + 1) // 2):
-        raise ValueError(f"pp_conv3x3_s2_split_wgrad_nhwc_dev does not take x {tuple(x.shape)}, dz {tuple(dz.shape)}")
-    ws = fused.wgrad_workspace(nbytes, x.device)
-    dw = torch.empty((cout, C, 3, 3), dtype=torch.float32, device=x.device)
-    _call("pp_conv3x3_s2_split_wgrad_nhwc_dev", x.device, _vp(x), _vp(dz), B, H, W, C, cout, _vp(dz_scale), _vp(ws),
-          nbytes, _vp(dw))
-    return dw
-
-
-def _wgrad_s2_miopen(dz, x, weight):
-    """MIOpen's weight gradient of the stride-2, padding-1 3x3 conv: ``_Conv3x3S2Train``'s without ``split_wgrad``."""
-    return torch.ops.aten.convolution_backward(dz, x, weight, None, (2, 2), (1, 1), (1, 1), False, (0, 0), 1,
-                                               (False, True, False))[1]
-
-
-def _convt_split_bare(x, ws, cout, stride, out_hw):
-    """The bare output [B,cout,*out_hw] of ConvTranspose2d(3x3, padding 1, ``stride`` 1, 2 or 4) of the channels-last
-    ``x`` (include/train/pp_convt_train.h): the stride-1 bare conv on the flipped operand, the stride-2 conv's data
-    gradient kernel with ``x`` for ``dz``, or pp_convt3x3_s4_split_bare_nhwc_dev; ``ws``: the forward operand of
-    ``_FusedConv.train_operands(..., transposed=True)``."""
-    if stride == 1:
-        return _conv_split_bare(x, ws, cout)
-    if stride == 2:
-        return _dgrad_s2_split(x, ws, cout, *out_hw)
-    B, C, H, W = x.shape
-    out = torch.empty((B, cout) + tuple(out_hw), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    _call("pp_convt3x3_s4_split_bare_nhwc_dev", x.device, _vp(x), B, H, W, C, _vp(ws), cout, out_hw[0], out_hw[1], None,
-          _vp(out))
-    return out
-
-
-def _convt_dgrad_split(dy, ws, cin, stride, dy_scale=None):
-    """The data gradient [B,cin,H,W] of that transposed conv from the channels-last ``dy``: ``conv2d(dy, w_t, stride,
-    padding 1)`` on the bare split kernel of that stride (stride 4: pp_conv3x3_s4_split_bare_nhwc_dev); ``ws``: the
-    data gradient's operand of ``train_operands``; ``dy_scale``: ``_pow2_scale(dy)``."""
-    if stride == 1:
-        return _conv_split_bare(dy, ws, cin, dy_scale)
-    if stride == 2:
-        return _conv_s2_split_bare(dy, ws, cin, dy_scale)
-    B, C, H, W = dy.shape
-    dx = torch.empty((B, cin, (H + 3) // 4, (W + 3) // 4), dtype=torch.float32, device=dy.device,
-                     memory_format=torch.channels_last)
-    _call("pp_conv3x3_s4_split_bare_nhwc_dev", dy.device, _vp(dy), B, H, W, C, _vp(ws), cin, _vp(dy_scale), _vp(dx))
-    return dx
-
-
-def _wgrad_convt_split(x, dy, stride, dy_scale, fused):
-    """pp_convt3x3_split_wgrad_nhwc_dev: the weight gradient [Cin,Cout,3,3] of that transposed conv from its
-    channels-last input ``x`` and output gradient ``dy``, as they lie; ``dy_scale``: ``_pow2_scale(dy)``; ``fused``
-    keeps the split-K workspace."""
-    B, C, H, W = x.shape
-    cout, ho, wo = dy.shape[1:]
-    nbytes = _lib.lib().pp_convt3x3_split_wgrad_workspace_bytes(B, H, W, C, cout, stride, ho, wo)
-    if nbytes < 0:
-        raise ValueError(f"pp_convt3x3_split_wgrad_nhwc_dev does not take x {tuple(x.shape)}, dy {tuple(dy.shape)}, "
-                         f"stride {stride}")
-    ws = fused.wgrad_workspace(nbytes, x.device)
-    dw = torch.empty((C, cout, 3, 3), dtype=torch.float32, device=x.device)
-    _call("pp_convt3x3_split_wgrad_nhwc_dev", x.device, _vp(x), _vp(dy), B, H, W, C, cout, stride, ho, wo,
-          _vp(dy_scale), _vp(ws), nbytes, _vp(dw))
-    return dw
 
 
 def _conv_s2_f16(x, w16, table, cout, out=None, channel_offset=0):
@@ -721,23 +665,53 @@ def _relu_bn(z, bn, enabled=True, conv_bias=None):
     return bn(F.relu(z))
 
 
-class _Conv3x3Train(torch.autograd.Function):
-    """The bare 3x3, stride-1, padding-1 conv of a training layer on the split-fp16 MFMA kernel, forward and data
-    gradient (include/pp_conv_train.h): ``z = conv(x, weight)`` with ``x`` channels-last; the layer's bias and its
-    gradient stay with ``_relu_bn(..., conv_bias=)``.  The data gradient is the same conv on ``dz`` with the weight's
-    first two axes exchanged and its taps flipped, ``dz`` rescaled by a power of two of its own (``_pow2_scale``: the
-    split arithmetic resolves 2^-35 absolutely, which gradients fall under).  The weight gradient is MIOpen's
-    (``_wgrad_miopen``) or, with ``split_wgrad``, the split-K kernel's on the saved ``x`` and on ``dz`` with the same
-    scale (``_wgrad_split``, include/train/pp_conv_wgrad.h).
+def _split_train_stride(on, conv, x, transposed=False):
+    """The stride of ``conv`` where ``_ConvTrain`` takes it on ``x``, else 0: the block's switch ``on``, a CUDA f32
+    input, a 3x3, padding-1 conv of stride 1 or 2 or (``transposed``) ConvTranspose of stride 1, 2 or 4 with output
+    paddings below the stride, f32 weights, both channel counts multiples of 64."""
+    if not (on and x.is_cuda and x.dtype == torch.float32 and conv.in_channels % 64 == 0
+            and conv.out_channels % 64 == 0 and conv.weight.dtype == torch.float32):
+        return 0
+    if transposed:
+        # wider than ``_conv_kind``'s "up" and "s1": the two output paddings may differ, and stride 1 may have one
+        s, op = tuple(conv.stride), tuple(conv.output_padding)
+        if not (x.dim() == 4 and tuple(conv.kernel_size) == (3, 3) and tuple(conv.padding) == (1, 1)
+                and tuple(conv.dilation) == (1, 1) and conv.groups == 1 and s in ((1, 1), (2, 2), (4, 4))
+                and 0 <= op[0] < s[0] and 0 <= op[1] < s[0]):
+            return 0
+        stride = s[0]
+    else:
+        stride = {"s1": 1, "s2": 2}.get(_conv_kind(conv), 0)
+    # the blocks that open a channels-last stretch (stride 2, transposed) convert their input unless it is channels-last
+    # already: a dense channels-last tensor off 16 bytes would not be moved by the conversion and stays with MIOpen
+    if (transposed or stride == 2) and _is_nhwc(x) and x.data_ptr() % 16 != 0:
+        return 0
+    return stride
+
+
+class _ConvTrain(torch.autograd.Function):
+    """The bare 3x3, padding-1 conv of a training layer on the split-fp16 MFMA kernels in every direction
+    (include/pp_conv_train.h, include/train/pp_conv_s2_train.h, pp_convt_train.h): ``z = conv(x, weight)`` of ``stride``
+    1 or 2 or, ``transposed``, ``conv_transpose2d(x, weight)`` of stride 1, 2 or 4 at ``out_hw``, with ``x``
+    channels-last; the layer's bias and its gradient stay with ``_relu_bn(..., conv_bias=)``.
+
+    There are three geometries, one per stride.  A ConvTranspose weight read as the conv weight of the same stride
+    exchanges forward and data gradient: a conv runs ``_conv_bare`` forward and ``_convt_bare`` on ``dz`` at ``x``'s
+    extent, a transposed conv the other way round.  ``dz`` is rescaled by a power of two of its own (``_pow2_scale``: the
+    split arithmetic resolves 2^-35 absolutely, which gradients fall under), one scale for both gradients.  The weight
+    gradient is the split-K kernel's on the saved ``x`` and on ``dz`` (``_wgrad_split``); for a conv without
+    ``split_wgrad`` it is MIOpen's (``_wgrad_miopen``), which the transposed form does not have.
     ``fused``: the layer's ``_FusedConv``, which keeps both packed operands per version of the weight."""
 
     @staticmethod
-    def forward(ctx, x, weight, fused, split_wgrad=False):
-        fwd, dgrad = fused.train_operands(weight)
+    def forward(ctx, x, weight, fused, stride=1, transposed=False, out_hw=None, split_wgrad=True):
+        fwd, dgrad = fused.train_operands(weight, s2=stride != 1, transposed=transposed)
         ctx.save_for_backward(x, weight)
-        ctx.dgrad = dgrad
-        ctx.wgrad_fused = fused if split_wgrad else None
-        return _conv_split_bare(x, fwd, weight.shape[0])
+        ctx.dgrad, ctx.stride, ctx.transposed = dgrad, stride, transposed
+        ctx.wgrad_fused = fused if split_wgrad or transposed else None
+        if transposed:
+            return _convt_bare(x, fwd, weight.shape[1], stride, out_hw)
+        return _conv_bare(x, fwd, weight.shape[0], stride)
 
     @staticmethod
     def backward(ctx, dz):
@@ -747,73 +721,15 @@ class _Conv3x3Train(torch.autograd.Function):
         dx = dw = None
         split_wgrad = ctx.wgrad_fused is not None and ctx.needs_input_grad[1]
         scale = _pow2_scale(dz) if ctx.needs_input_grad[0] or split_wgrad else None     # one for dx and dw
-        if ctx.needs_input_grad[0]:
-            dx = _conv_split_bare(dz, ctx.dgrad, weight.shape[1], scale)
+        if ctx.needs_input_grad[0] and ctx.transposed:
+            dx = _conv_bare(dz, ctx.dgrad, weight.shape[0], ctx.stride, scale)
+        elif ctx.needs_input_grad[0]:
+            dx = _convt_bare(dz, ctx.dgrad, weight.shape[1], ctx.stride, tuple(x.shape[2:]), scale)
         if split_wgrad:
-            dw = _wgrad_split(x, dz, scale, ctx.wgrad_fused)
+            dw = _wgrad_split(x, dz, ctx.stride, ctx.transposed, scale, ctx.wgrad_fused)
         elif ctx.needs_input_grad[1]:
-            dw = _wgrad_miopen(dz, x, weight)
-        return dx, dw, None, None
-
-
-class _Conv3x3S2Train(torch.autograd.Function):
-    """``_Conv3x3Train`` for the 3x3, stride-2, padding-1 conv that opens a down block
-    (include/train/pp_conv_s2_train.h): ``z = conv(x, weight)`` with ``x`` channels-last on the bare stride-2 split
-    kernel.  The data gradient is the transposed conv of ``dz`` with the weight as it lies (taps not flipped), at
-    ``x``'s extent, ``dz`` rescaled by ``_pow2_scale``; the weight gradient is MIOpen's (``_wgrad_s2_miopen``) or, with
-    ``split_wgrad``, the stride-2 split-K kernel's with the same scale (``_wgrad_s2_split``)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, fused, split_wgrad=False):
-        fwd, dgrad = fused.train_operands(weight, s2=True)
-        ctx.save_for_backward(x, weight)
-        ctx.dgrad = dgrad
-        ctx.wgrad_fused = fused if split_wgrad else None
-        return _conv_s2_split_bare(x, fwd, weight.shape[0])
-
-    @staticmethod
-    def backward(ctx, dz):
-        x, weight = ctx.saved_tensors
-        if not _nhwc_f32(dz):
-            dz = dz.float().contiguous(memory_format=torch.channels_last)
-        dx = dw = None
-        split_wgrad = ctx.wgrad_fused is not None and ctx.needs_input_grad[1]
-        scale = _pow2_scale(dz) if ctx.needs_input_grad[0] or split_wgrad else None     # one for dx and dw
-        if ctx.needs_input_grad[0]:
-            dx = _dgrad_s2_split(dz, ctx.dgrad, weight.shape[1], x.shape[2], x.shape[3], scale)
-        if split_wgrad:
-            dw = _wgrad_s2_split(x, dz, scale, ctx.wgrad_fused)
-        elif ctx.needs_input_grad[1]:
-            dw = _wgrad_s2_miopen(dz, x, weight)
-        return dx, dw, None, None
-
-
-class _ConvT3x3Train(torch.autograd.Function):
-    """``_Conv3x3S2Train``'s counterpart for the 3x3, padding-1 transposed conv of an up block, stride 1, 2 or 4
-    (include/train/pp_convt_train.h): ``y = conv_transpose2d(x, weight)`` at ``out_hw`` with ``x`` channels-last.  With
-    ``weight`` read as the weight of a conv of that stride, the forward is that conv's data gradient, the data
-    gradient its forward on ``dy`` rescaled by ``_pow2_scale``, and the weight gradient its split-K weight gradient
-    with the roles exchanged (``_wgrad_convt_split``) and the same scale; there is no MIOpen variant."""
-
-    @staticmethod
-    def forward(ctx, x, weight, fused, stride, out_hw):
-        fwd, dgrad = fused.train_operands(weight, s2=stride != 1, transposed=True)
-        ctx.save_for_backward(x, weight)
-        ctx.dgrad, ctx.fused, ctx.stride = dgrad, fused, stride
-        return _convt_split_bare(x, fwd, weight.shape[1], stride, out_hw)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, weight = ctx.saved_tensors
-        if not _nhwc_f32(dy):
-            dy = dy.float().contiguous(memory_format=torch.channels_last)
-        dx = dw = None
-        scale = _pow2_scale(dy) if ctx.needs_input_grad[0] or ctx.needs_input_grad[1] else None   # one for dx and dw
-        if ctx.needs_input_grad[0]:
-            dx = _convt_dgrad_split(dy, ctx.dgrad, weight.shape[0], ctx.stride, scale)
-        if ctx.needs_input_grad[1]:
-            dw = _wgrad_convt_split(x, dy, ctx.stride, scale, ctx.fused)
-        return dx, dw, None, None, None
+            dw = _wgrad_miopen(dz, x, weight, ctx.stride)
+        return dx, dw, None, None, None, None, None
 
 
 class PPFeatureNet(nn.Module):
@@ -971,7 +887,7 @@ class PPDownBlock(nn.Module):
         self.split_mma_s2 = False
         #: opt-in (``PillarPipeline(with_targets=True, split_train=True)``): in train(), with ``fused_train``, the
         #: stride-1 layers' forward conv and data gradient on the split-fp16 MFMA kernel and their ReLU -> BatchNorm
-        #: tail channels-last (``_Conv3x3Train``, include/pp_conv_train.h) instead of MIOpen's NCHW f32 convolutions;
+        #: tail channels-last (``_ConvTrain``, include/pp_conv_train.h) instead of MIOpen's NCHW f32 convolutions;
         #: the weight gradient stays MIOpen's.  Forward activations with |x| >= 65520 give NaN
         self.split_train = False
         #: opt-in, with ``split_train`` (``PillarPipeline(..., split_train=True, split_wgrad=True)``): those layers'
@@ -981,7 +897,7 @@ class PPDownBlock(nn.Module):
         self.split_wgrad = False
         #: opt-in, with ``split_train`` (``PillarPipeline(..., split_train=True, split_train_s2=True)``): the stride-2
         #: conv that opens the block too, forward and data gradient on the split-fp16 kernels with the channels-last
-        #: tail (``_Conv3x3S2Train``, include/train/pp_conv_s2_train.h), its weight gradient MIOpen's or, with
+        #: tail (``_ConvTrain``, include/train/pp_conv_s2_train.h), its weight gradient MIOpen's or, with
         #: ``split_wgrad``, the stride-2 split-K kernel's; the block then takes and returns channels-last tensors and
         #: copies no layout inside.  Without ``split_train`` it does nothing
         self.split_train_s2 = False
@@ -995,49 +911,28 @@ class PPDownBlock(nn.Module):
         w_taps = fused.packed("stem", conv.weight, _stem_filter)
         return _conv_stem(feats, inds, h, w, w_taps, fused.table(conv.bias, bn), conv.out_channels)
 
-    def _split_train_ok(self, x):
-        """``split_train`` applies: a CUDA f32 tensor and stride-1 layers the kernels take, every one of them."""
-        convs = [self.block[3 * i] for i in range(1, len(self._fused))]
-        return bool(self.split_train and convs and x.is_cuda and x.dtype == torch.float32
-                    and all(_conv_kind(c) == "s1" and c.in_channels % 64 == 0 and c.out_channels % 64 == 0
-                            and c.weight.dtype == torch.float32 for c in convs))
-
-    def _split_train_s2_ok(self, x):
-        """``split_train_s2`` applies: ``split_train`` does, and layer 0 is a stride-2 conv the kernels take."""
-        conv = self.block[0]
-        # a dense channels-last tensor off 16 bytes would not be moved by the conversion: it stays with MIOpen
-        return bool(self.split_train_s2 and self._split_train_ok(x) and _conv_kind(conv) == "s2"
-                    and (not _is_nhwc(x) or x.data_ptr() % 16 == 0)
-                    and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0 and conv.weight.dtype == torch.float32)
-
     def forward(self, x, first=0):
         """``first`` = 1: ``x`` is ``stem``'s output and has passed layer 0 already."""
         if not _use_fused_epilogue(self, x):
             if first:
                 raise RuntimeError("PPDownBlock: a tensor past layer 0 needs the fused inference path")
             if self.training and self.fused_train and x.is_cuda:
-                split = self._split_train_ok(x)
-                if split and self._split_train_s2_ok(x):
-                    # every layer channels-last, in and out: the next block takes the result as it lies
-                    if not _nhwc_f32(x):
-                        x = x.contiguous(memory_format=torch.channels_last)
-                    for i in range(len(self._fused)):
-                        conv, bn = self.block[3 * i], self.block[3 * i + 2]
-                        fn = _Conv3x3Train if i else _Conv3x3S2Train
-                        x = _relu_bn(fn.apply(x, conv.weight, self._fused[i], bool(self.split_wgrad)), bn,
-                                     conv_bias=conv.bias)
-                    return x
-                for i in range(len(self._fused)):
-                    conv, bn = self.block[3 * i], self.block[3 * i + 2]
-                    if split and i > 0:
-                        x = _relu_bn(_Conv3x3Train.apply(x, conv.weight, self._fused[i], bool(self.split_wgrad)), bn,
-                                     conv_bias=conv.bias)
-                        continue
-                    x = _relu_bn(F.conv2d(x, conv.weight, None, conv.stride, conv.padding), bn,
-                                 conv_bias=conv.bias)
-                    if split:           # past layer 0: the stride-1 layers run channels-last
-                        x = x.contiguous(memory_format=torch.channels_last)
-                return x.contiguous() if split else x
+                convs = [self.block[3 * i] for i in range(len(self._fused))]
+                # ``split_train`` asks that every stride-1 layer qualifies; ``split_train_s2`` adds layer 0 to those
+                split = bool(convs[1:]) and all(_split_train_stride(self.split_train, c, x) == 1 for c in convs[1:])
+                s2 = split and _split_train_stride(self.split_train_s2, convs[0], x) == 2
+                for i, conv in enumerate(convs):
+                    if split and (i or s2):
+                        # where a channels-last stretch begins: at the block's entry, or past a layer 0 on MIOpen
+                        if not _nhwc_f32(x):
+                            x = x.contiguous(memory_format=torch.channels_last)
+                        z = _ConvTrain.apply(x, conv.weight, self._fused[i], conv.stride[0], False, None,
+                                             bool(self.split_wgrad))
+                    else:
+                        z = F.conv2d(x, conv.weight, None, conv.stride, conv.padding)
+                    x = _relu_bn(z, self.block[3 * i + 2], conv_bias=conv.bias)
+                # with layer 0 on the split kernels the next block takes the channels-last result as it lies
+                return x.contiguous() if split and not s2 else x
             return self.block(x)
         for i in range(first, len(self._fused)):
             x = self._fused[i](self, self.block[3 * i], self.block[3 * i + 2], x)
@@ -1066,24 +961,12 @@ class PPUpBlock(nn.Module):
         self.split_mma_up = False
         #: opt-in (``PillarPipeline(with_targets=True, split_train_up=True)``): in train(), with ``fused_train``, the
         #: transposed conv on the split-fp16 MFMA kernels in all three directions, forward, data gradient and weight
-        #: gradient, with the channels-last ReLU -> BatchNorm tail (``_ConvT3x3Train``,
+        #: gradient, with the channels-last ReLU -> BatchNorm tail (``_ConvTrain``,
         #: include/train/pp_convt_train.h) instead of MIOpen's; the block converts an input that does not arrive
         #: channels-last once and returns its channels-last tensor as it lies.  Forward activations with
         #: |x| >= 65520 give NaN
         self.split_train_up = False
         self._fused = _FusedConv()
-
-    def _split_train_up_ok(self, x):
-        """``split_train_up`` applies: a CUDA f32 tensor and a 3x3, padding-1 transposed conv of stride 1, 2 or 4 with
-        channel counts the kernels take."""
-        ct = self.conv2d_t
-        s, op = tuple(ct.stride), tuple(ct.output_padding)
-        # a dense channels-last tensor off 16 bytes would not be moved by the conversion: it stays with MIOpen
-        return bool(self.split_train_up and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
-                    and (not _is_nhwc(x) or x.data_ptr() % 16 == 0)
-                    and tuple(ct.kernel_size) == (3, 3) and tuple(ct.padding) == (1, 1) and tuple(ct.dilation) == (1, 1)
-                    and ct.groups == 1 and s in ((1, 1), (2, 2), (4, 4)) and 0 <= op[0] < s[0] and 0 <= op[1] < s[0]
-                    and ct.in_channels % 64 == 0 and ct.out_channels % 64 == 0 and ct.weight.dtype == torch.float32)
 
     def forward(self, x, out=None, channel_offset=0, defer=False):
         """``defer``: ``_FusedConv.__call__``'s, on the fused inference path only."""
@@ -1092,12 +975,13 @@ class PPUpBlock(nn.Module):
                 raise RuntimeError("PPUpBlock: a deferred epilogue needs the fused inference path")
             if self.fused_train and _relu_bn_fusable(x, self.bn):
                 ct = self.conv2d_t
-                if self._split_train_up_ok(x):
+                s = _split_train_stride(self.split_train_up, ct, x, transposed=True)
+                if s:
                     if not _nhwc_f32(x):
                         x = x.contiguous(memory_format=torch.channels_last)
-                    s, op = ct.stride[0], ct.output_padding
+                    op = ct.output_padding
                     out_hw = ((x.shape[2] - 1) * s + 1 + op[0], (x.shape[3] - 1) * s + 1 + op[1])
-                    return _relu_bn(_ConvT3x3Train.apply(x, ct.weight, self._fused, s, out_hw), self.bn,
+                    return _relu_bn(_ConvTrain.apply(x, ct.weight, self._fused, s, True, out_hw), self.bn,
                                     conv_bias=ct.bias)
                 return _relu_bn(F.conv_transpose2d(x, ct.weight, None, ct.stride, ct.padding, ct.output_padding),
                                 self.bn, conv_bias=ct.bias)

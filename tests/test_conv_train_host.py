@@ -158,9 +158,10 @@ def test_constructor_checks_and_defaults():
     bb = model.backbone
     assert [b.split_train for b in (bb.down1, bb.down2, bb.down3)] == [False] * 3
     assert not any(hasattr(m, "split_train") for m in (model, bb, bb.up1, bb.up2, bb.up3, model.det_head))
-    assert not bb.down1._split_train_ok(torch.zeros(1, 64, 4, 4))                   # off, and a CPU tensor
+    conv = bb.down1.block[3]
+    assert not M._split_train_stride(bb.down1.split_train, conv, torch.zeros(1, 64, 4, 4))   # off, and a CPU tensor
     bb.down1.split_train = True
-    assert not bb.down1._split_train_ok(torch.zeros(1, 64, 4, 4))                   # on: still no CUDA tensor
+    assert not M._split_train_stride(bb.down1.split_train, conv, torch.zeros(1, 64, 4, 4))   # on: still no CUDA tensor
 
 
 # ------------------------------------------------------------------------------------------------------- replica

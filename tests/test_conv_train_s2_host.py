@@ -256,11 +256,13 @@ def test_constructor_checks_and_defaults():
     assert [b.split_train_s2 for b in (bb.down1, bb.down2, bb.down3)] == [False] * 3
     assert not any(hasattr(m, "split_train_s2") for m in (model, bb, bb.up1, bb.up2, bb.up3, model.det_head))
     x = torch.zeros(1, 64, 4, 4)
-    assert not bb.down1._split_train_s2_ok(x)
+    conv = bb.down1.block[0]
+    assert not M._split_train_stride(bb.down1.split_train_s2, conv, x)
     bb.down1.split_train_s2 = True
-    assert not bb.down1._split_train_s2_ok(x)                      # without split_train, and a CPU tensor
-    assert callable(M._wgrad_s2_miopen) and callable(M._wgrad_s2_split) and callable(M._dgrad_s2_split)
-    assert issubclass(M._Conv3x3S2Train, torch.autograd.Function)
+    assert not M._split_train_stride(bb.down1.split_train_s2, conv, x)      # a CPU tensor
+    assert not M._split_train_stride(bb.down1.split_train, bb.down1.block[3], x)    # and without split_train
+    assert callable(M._wgrad_miopen) and callable(M._wgrad_split) and callable(M._convt_bare)
+    assert issubclass(M._ConvTrain, torch.autograd.Function)
 
 
 # ------------------------------------------------------------------------------------------------------ identity

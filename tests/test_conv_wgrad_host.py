@@ -179,6 +179,7 @@ def test_constructor_checks_and_defaults():
     assert [b.split_wgrad for b in (bb.down1, bb.down2, bb.down3)] == [False] * 3
     assert not any(hasattr(m, "split_wgrad") for m in (model, bb, bb.up1, bb.up2, bb.up3, model.det_head))
     assert callable(M._wgrad_miopen) and callable(M._wgrad_split)
+    assert issubclass(M._ConvTrain, torch.autograd.Function)
 
 
 # ------------------------------------------------------------------------------------------------ the case table

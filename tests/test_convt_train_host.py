@@ -270,11 +270,11 @@ def test_constructor_checks_and_defaults():
     assert [b.split_train_up for b in (bb.up1, bb.up2, bb.up3)] == [False] * 3
     assert not any(hasattr(b, "split_train") for b in (bb.up1, bb.up2, bb.up3))       # the down blocks' name stays theirs
     x = torch.zeros(1, 64, 4, 4)
-    assert not bb.up1._split_train_up_ok(x)
+    assert not M._split_train_stride(bb.up1.split_train_up, bb.up1.conv2d_t, x, transposed=True)
     bb.up1.split_train_up = True
-    assert not bb.up1._split_train_up_ok(x)                                   # a CPU tensor
-    assert issubclass(M._ConvT3x3Train, torch.autograd.Function)
-    assert callable(M._convt_split_bare) and callable(M._convt_dgrad_split) and callable(M._wgrad_convt_split)
+    assert not M._split_train_stride(bb.up1.split_train_up, bb.up1.conv2d_t, x, transposed=True)     # a CPU tensor
+    assert issubclass(M._ConvTrain, torch.autograd.Function)
+    assert callable(M._convt_bare) and callable(M._conv_bare) and callable(M._wgrad_split)
     assert "transposed" in inspect.signature(M._FusedConv.train_operands).parameters
 
 

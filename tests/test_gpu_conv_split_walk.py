@@ -194,7 +194,7 @@ def test_bare_entry_point_under_the_walk(gpu, three_chunks, scaled):
     bit-equal to its solo launch, and the batch within |err| <= 2e-6 * conv(|x|,|w|) of f64."""
     x, w, _, xd, ws, _, _ = three_chunks
     scale = torch.tensor([2.0 ** 7, 2.0 ** -7], device=gpu) if scaled else None
-    run = lambda s: M._conv_split_bare(s, ws, CO, scale)  # noqa: E731
+    run = lambda s: M._conv_bare(s, ws, CO, 1, scale)  # noqa: E731
     with torch.no_grad():
         y = run(xd)
         torch.cuda.synchronize()

@@ -1,16 +1,16 @@
 """The training step with ``PillarPipeline(with_targets=True, split_train=True, split_train_s2=True)``: the legs of
 tests/test_gpu_train_step_split.py and tests/test_gpu_train_step_wgrad.py with the stride-2 conv that opens each of
-down1, down2 and down3 on ``_Conv3x3S2Train`` (include/train/pp_conv_s2_train.h) too.  Cases a and c through
+down1, down2 and down3 on ``_ConvTrain`` (include/train/pp_conv_s2_train.h) too.  Cases a and c through
 tests/test_gpu_train_step.py's ``_data``, ``_plain``, ``_step`` and ``_check`` and ``train_step_reference.compare``,
 their gates unchanged: per backbone/head tensor e <= 4 * max(e_plain, E), the feature net's e <= 4 * e_plain + 2e-5,
 buffers and outputs e <= 4 * e_plain + 1e-6, loss scalars within RTOL_SCALAR.  Case a's canvases 44 -> 22 -> 11 -> 6
 give both parities of the data gradient.
 
-  leg 1   split_train + split_train_s2                  the three weight gradients on ``_wgrad_s2_miopen``
+  leg 1   split_train + split_train_s2                  the three weight gradients on ``_wgrad_miopen(..., 2)``
   leg 2   split_train + split_train_s2 + split_wgrad    ... on pp_conv3x3_s2_split_wgrad_nhwc_dev, beside the 13
                                                         stride-1 calls of pp_conv3x3_split_wgrad_nhwc_dev
 
-Dispatch per step, counted through ``model._call``, ``model._wgrad_miopen`` and ``model._wgrad_s2_miopen``:
+Dispatch per step, counted through ``model._call`` and ``model._wgrad_miopen`` (per stride argument):
 ``F.conv2d`` inside a down block 0 times; the bare stride-2 forward 3 times; the data-gradient entry point 3 times --
 every layer-0 input requires a gradient: down2's and down3's are the block before them, down1's is the canvas, which
 is scattered from the feature net's output, and the feature net has parameters; 13 + 3 packs, 16 scales, 26 bare
@@ -46,7 +46,7 @@ pytestmark = pytest.mark.gpu
 BARE_S2, DGRAD_S2, PACK_S2 = ("pp_conv3x3_s2_split_bare_nhwc_dev", "pp_conv3x3_s2_split_dgrad_nhwc_dev",
                               "pp_split_pack_s2_dev")
 WGRAD_S2 = "pp_conv3x3_s2_split_wgrad_nhwc_dev"
-MIOPEN_S2 = "_wgrad_s2_miopen"
+MIOPEN_S2 = G.MIOPEN_S2
 TAIL_F_DOWN = "pp_relu_bn_train_fwd_nhwc_dev in a down block"
 LEGS = {"s2": False, "s2+wgrad": True}          # leg -> split_wgrad
 
@@ -65,9 +65,9 @@ def _pipe(case, leg):
 
 @contextlib.contextmanager
 def _counting(model):
-    """tests/test_gpu_train_step_wgrad.py's counter, plus the calls of ``model._wgrad_s2_miopen``."""
+    """tests/test_gpu_train_step_wgrad.py's counter (``model._wgrad_miopen`` per stride), plus the forward tails inside
+    a down block."""
     import pp_amd.model as M
-    miopen0 = M._wgrad_s2_miopen
     inside = [0]
     hooks = []
     for b in S._downs(model):
@@ -79,15 +79,11 @@ def _counting(model):
         def call(name, *a):
             calls[TAIL_F_DOWN] += 1 if inside[0] and name == S.TAIL_F else 0
             return call1(name, *a)
-
-        def miopen(*a):
-            calls[MIOPEN_S2] += 1
-            return miopen0(*a)
-        M._wgrad_s2_miopen, M._call = miopen, call
+        M._call = call
         try:
             yield calls
         finally:
-            M._wgrad_s2_miopen, M._call = miopen0, call1
+            M._call = call1
             for h in hooks:
                 h.remove()
 

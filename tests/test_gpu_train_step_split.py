@@ -1,7 +1,7 @@
 """The training step with ``PillarPipeline(with_targets=True, split_train=True)``: tests/test_gpu_train_step.py's
 check -- outputs, the four losses, every parameter gradient, every running statistic and counter against f64 on the
 run's own ReLU masks -- for a leg ``split``: everything on (the ``hip+loss`` leg) plus the 13 stride-1 layers of
-down1, down2 and down3 on ``_Conv3x3Train`` and the channels-last ReLU -> BatchNorm tail (include/pp_conv_train.h).
+down1, down2 and down3 on ``_ConvTrain`` and the channels-last ReLU -> BatchNorm tail (include/pp_conv_train.h).
 Cases a and c (BatchNorm planes 484 / 121 / 36 with B = 3, 400 / 100 / 25 with B = 2), that file's ``_data``,
 ``_plain``, ``_step`` and ``_check`` and its gates, unchanged: per backbone/head tensor e <= 4 * max(e_plain, E), the
 feature net's e <= 4 * e_plain + 2e-5, buffers and outputs e <= 4 * e_plain + 1e-6, loss scalars within RTOL_SCALAR.

@@ -1,5 +1,5 @@
 """The training step with ``PillarPipeline(with_targets=True, split_train_up=True)``: the transposed convs of up1, up2
-and up3 on ``_ConvT3x3Train`` (include/train/pp_convt_train.h) in all three directions.  Cases a and c through
+and up3 on ``_ConvTrain`` (include/train/pp_convt_train.h) in all three directions.  Cases a and c through
 tests/test_gpu_train_step.py's ``_data``, ``_plain``, ``_step`` and ``_check`` and ``train_step_reference.compare``,
 their gates unchanged: per backbone/head tensor e <= 4 * max(e_plain, E), the feature net's e <= 4 * e_plain + 2e-5,
 buffers and outputs e <= 4 * e_plain + 1e-6, loss scalars within RTOL_SCALAR.

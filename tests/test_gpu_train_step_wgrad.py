@@ -5,8 +5,8 @@ pp_conv3x3_split_wgrad_nhwc_dev (include/train/pp_conv_wgrad.h) too.  Cases a an
 e <= 4 * max(e_plain, E), the feature net's e <= 4 * e_plain + 2e-5, buffers and outputs e <= 4 * e_plain + 1e-6, loss
 scalars within RTOL_SCALAR.
 
-Dispatch per step, counted through ``model._call`` and ``model._wgrad_miopen``: the new entry point 13 times,
-``_wgrad_miopen`` 0 times, 13 scales (one per layer serves the data gradient and the weight gradient), 13 + 13 bare
+Dispatch per step, counted through ``model._call`` and ``model._wgrad_miopen`` (by its stride argument; the stride-1
+calls are meant here): the new entry point 13 times, ``_wgrad_miopen`` 0 times, 13 scales (one per layer serves the data gradient and the weight gradient), 13 + 13 bare
 convs, 13 packs, the tails as before, ``F.conv2d`` 3 times inside the down blocks.  With the switch off, in the same
 file: ``_wgrad_miopen`` 13 times and the new entry point 0 times.  A second step after an SGD step reuses every
 workspace (the same ``data_ptr``), and its running statistics stay within 4 * plain + 1e-6.
@@ -31,7 +31,8 @@ import train_step_reference as R
 pytestmark = pytest.mark.gpu
 
 WGRAD = "pp_conv3x3_split_wgrad_nhwc_dev"
-MIOPEN = "_wgrad_miopen"
+MIOPEN = "_wgrad_miopen"                      # its calls with stride 1
+MIOPEN_S2 = "_wgrad_miopen, stride 2"
 
 
 def _pipe(case, split_wgrad=True):
@@ -48,13 +49,13 @@ def _pipe(case, split_wgrad=True):
 
 @contextlib.contextmanager
 def _counting(model):
-    """tests/test_gpu_train_step_split.py's counter, plus the calls of ``model._wgrad_miopen``."""
+    """tests/test_gpu_train_step_split.py's counter, plus the calls of ``model._wgrad_miopen`` per stride."""
     import pp_amd.model as M
     miopen0 = M._wgrad_miopen
     with S._counting(model) as calls:
-        def miopen(*a):
-            calls[MIOPEN] += 1
-            return miopen0(*a)
+        def miopen(dz, x, weight, stride):
+            calls[{1: MIOPEN, 2: MIOPEN_S2}[stride]] += 1
+            return miopen0(dz, x, weight, stride)
         M._wgrad_miopen = miopen
         try:
             yield calls
