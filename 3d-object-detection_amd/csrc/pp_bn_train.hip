@@ -103,7 +103,7 @@ __device__ __forceinline__ float rbn_shift(const float *__restrict__ z, float bc
   if (lane < n) {
     const int64_t j = M * lane / n;  // < 2^46
     const int64_t b = j / g.HW;
-    v = fmaxf(z[(b * g.C + c) * g.HW + (j - b * g.HW)] + bc, 0.0f);
+    v = relu_keeps_nan(z[(b * g.C + c) * g.HW + (j - b * g.HW)] + bc);
   }
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
@@ -137,12 +137,12 @@ __global__ __launch_bounds__(kRbnThreads) void k_rbn_stats(const float *__restri
   rbn_foreach(g, c, s, [&](int64_t o, int64_t od, int n) {
     if (n == 4) {
       const float4 v = *reinterpret_cast<const float4 *>(z + o);
-      const float r0 = fmaxf(v.x + bc, 0.0f) - c0, r1 = fmaxf(v.y + bc, 0.0f) - c0,
-                  r2 = fmaxf(v.z + bc, 0.0f) - c0, r3 = fmaxf(v.w + bc, 0.0f) - c0;
+      const float r0 = relu_keeps_nan(v.x + bc) - c0, r1 = relu_keeps_nan(v.y + bc) - c0,
+                  r2 = relu_keeps_nan(v.z + bc) - c0, r3 = relu_keeps_nan(v.w + bc) - c0;
       sum += (r0 + r1) + (r2 + r3);
       sq = fmaf(r0, r0, fmaf(r1, r1, fmaf(r2, r2, fmaf(r3, r3, sq))));
     } else {
-      const float r = fmaxf(z[o] + bc, 0.0f) - c0;
+      const float r = relu_keeps_nan(z[o] + bc) - c0;
       sum += r;
       sq = fmaf(r, r, sq);
     }
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(kRbnThreads) void k_rbn_apply(
   const double dm = v[0] / M;  // sums are about rbn_shift()
   const double mean = (double)rbn_shift(z, bc, c, g) + dm;
   double var = v[1] / M - dm * dm;  // biased: what BatchNorm normalises with
-  var = var > 0.0 ? var : 0.0;
+  var = var < 0.0 ? 0.0 : var;  // a NaN stays one: invstd is then not finite either, and the backward stays loud
   const double invstd = 1.0 / sqrt(var + eps);
   // y = (r - mu)*sc + sh with mu the f32 mean and sh = beta - (mean - mu)*gamma*invstd: the form s*r + t
   // loses ulp(mean*gamma*invstd), which is large against y where the spread of a channel is small against
@@ -180,20 +180,24 @@ __global__ __launch_bounds__(kRbnThreads) void k_rbn_apply(
     invstd_out[c] = (float)invstd;
     if (running_mean) {
       const double unbiased = M > 1.0 ? var * (M / (M - 1.0)) : var;
-      running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * mean);
-      running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unbiased);
+      const float rm = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * mean);
+      const float rv = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unbiased);
+      if (stats_finite(rm, rv)) {  // else the channel keeps its running statistics
+        running_mean[c] = rm;
+        running_var[c] = rv;
+      }
     }
   }
   rbn_foreach(g, c, s, [&](int64_t o, int64_t od, int n) {
     if (n == 4) {
       float4 q = *reinterpret_cast<const float4 *>(z + o);
-      q.x = fmaf(fmaxf(q.x + bc, 0.0f) - mu, sc, sh);
-      q.y = fmaf(fmaxf(q.y + bc, 0.0f) - mu, sc, sh);
-      q.z = fmaf(fmaxf(q.z + bc, 0.0f) - mu, sc, sh);
-      q.w = fmaf(fmaxf(q.w + bc, 0.0f) - mu, sc, sh);
+      q.x = fmaf(relu_keeps_nan(q.x + bc) - mu, sc, sh);
+      q.y = fmaf(relu_keeps_nan(q.y + bc) - mu, sc, sh);
+      q.z = fmaf(relu_keeps_nan(q.z + bc) - mu, sc, sh);
+      q.w = fmaf(relu_keeps_nan(q.w + bc) - mu, sc, sh);
       *reinterpret_cast<float4 *>(y + o) = q;
     } else {
-      y[o] = fmaf(fmaxf(z[o] + bc, 0.0f) - mu, sc, sh);
+      y[o] = fmaf(relu_keeps_nan(z[o] + bc) - mu, sc, sh);
     }
   });
 }
@@ -213,7 +217,7 @@ __global__ __launch_bounds__(kRbnThreads) void k_rbn_bwd_stats(const float *__re
   float sd = 0.0f, sdx = 0.0f, md = 0.0f, mc = 0.0f, mx = 0.0f;
   auto one = [&](float zv, float d) {
     zv += bc;
-    const float xh = (fmaxf(zv, 0.0f) - mu) * is;
+    const float xh = (relu_keeps_nan(zv) - mu) * is;
     const float m = zv > 0.0f ? 1.0f : 0.0f;
     sd += d;
     sdx = fmaf(d, xh, sdx);
@@ -259,7 +263,7 @@ __global__ __launch_bounds__(kRbnThreads) void k_rbn_bwd_apply(
   const float k1 = (float)(v[0] / M), k2 = (float)(v[1] / M);
   auto one = [&](float zv, float d) {
     zv += bc;
-    const float xh = (fmaxf(zv, 0.0f) - mu) * is;
+    const float xh = (relu_keeps_nan(zv) - mu) * is;
     return zv > 0.0f ? sc * (d - k1 - xh * k2) : 0.0f;
   };
   rbn_foreach(g, c, s, [&](int64_t o, int64_t od, int n) {

@@ -60,7 +60,7 @@ __device__ __forceinline__ float4 bias4(const float *bias, int cg) {
   return bias ? chan4(bias, cg) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
-__device__ __forceinline__ float relu_b(float z, float b) { return fmaxf(z + b, 0.0f); }
+__device__ __forceinline__ float relu_b(float z, float b) { return relu_keeps_nan(z + b); }
 
 // The provisional value of the lane's four channels.  The workgroup's rows load the samples, one each, into
 // s_smp [kSamples][kMaxTw]; every lane then adds its channels' samples in index order.  Called by every thread.
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(kThreads) void k_rbn_nhwc_apply(
     const double dm = v[0][j] / M;  // sums are about c0
     const double mean = (double)get(c0, j) + dm;
     double var = v[1][j] / M - dm * dm;  // biased: what BatchNorm normalises with
-    var = var > 0.0 ? var : 0.0;
+    var = var < 0.0 ? 0.0 : var;  // a NaN stays one: invstd is then not finite either, and the backward stays loud
     const double invstd = 1.0 / sqrt(var + eps);
     // y = (r - mu)*sc + sh with mu the f32 mean and sh = beta - (mean - mu)*gamma*invstd, as pp_bn_train.hip has it
     mu[j] = (float)mean;
@@ -208,8 +208,12 @@ __global__ __launch_bounds__(kThreads) void k_rbn_nhwc_apply(
       invstd_out[c] = (float)invstd;
       if (running_mean) {
         const double unbiased = M > 1.0 ? var * (M / (M - 1.0)) : var;
-        running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * mean);
-        running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unbiased);
+        const float rm = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * mean);
+        const float rv = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unbiased);
+        if (stats_finite(rm, rv)) {  // else the channel keeps its running statistics
+          running_mean[c] = rm;
+          running_var[c] = rv;
+        }
       }
     }
   }
@@ -241,7 +245,7 @@ __global__ __launch_bounds__(kThreads) void k_rbn_nhwc_bwd_stats(const float *__
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float zv = get(q, j) + get(b, j), d = get(d4, j);
-        const float xh = (fmaxf(zv, 0.0f) - get(mu, j)) * get(is, j);
+        const float xh = (relu_keeps_nan(zv) - get(mu, j)) * get(is, j);
         const float m = zv > 0.0f ? 1.0f : 0.0f;
         v[0][j] += d;
         v[1][j] = fmaf(d, xh, v[1][j]);
@@ -284,7 +288,7 @@ __global__ __launch_bounds__(kThreads) void k_rbn_nhwc_bwd_apply(
   }
   auto one = [&](float zv, float d, int j) {
     zv += get(b, j);
-    const float xh = (fmaxf(zv, 0.0f) - mu[j]) * is[j];
+    const float xh = (relu_keeps_nan(zv) - mu[j]) * is[j];
     return zv > 0.0f ? sc[j] * (d - k1[j] - xh * k2[j]) : 0.0f;
   };
   foreach_pixel(g, l, s, [&](int64_t p) {

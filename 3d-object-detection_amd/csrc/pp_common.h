@@ -112,6 +112,18 @@ __device__ __forceinline__ void wave_sync() {
 
 __device__ __forceinline__ float sigmoid_f32(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// max(u, 0) as torch.relu has it: a NaN stays one (fmaxf would return the 0).  An activation beyond the fp16
+// range makes the split-fp16 convs write NaN wherever that pixel is read, and a training tail that turned it
+// into 0 would hand the optimizer a finite, wrong step: it has to stay loud
+__device__ __forceinline__ float relu_keeps_nan(float u) { return u < 0.0f ? 0.0f : u; }
+
+// The running-statistics rule of the training tails (include/pp_hip.h): a channel whose batch mean or variance
+// is not finite keeps its running_mean and running_var, so that the model of a dropped step still evaluates.
+// Tested on the f32 values that would be stored: a finite f64 statistic beyond FLT_MAX is +-inf in f32 too
+__device__ __forceinline__ bool stats_finite(float new_mean, float new_var) {
+  return __builtin_isfinite(new_mean) && __builtin_isfinite(new_var);
+}
+
 // Inclusive prefix sum over the wave's 64 lanes on the DPP path (row shifts inside the rows of 16,
 // then the two row broadcasts of gfx9): 6 VALU adds with DPP operands instead of 6 ds_bpermute
 // round trips through the LDS pipeline.  ALL 64 lanes must be active at the call (a DPP read of an

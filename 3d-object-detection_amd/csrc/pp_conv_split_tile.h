@@ -9,9 +9,8 @@ namespace pp {
 
 namespace {
 
-// max(u, 0) as torch.relu has it: a NaN stays one (fmaxf would return the 0).  An activation beyond the fp16
-// range gives main = +-inf and corr = -+inf or NaN, so v is NaN wherever that pixel is read: it has to stay loud
-__device__ __forceinline__ float relu_keeps_nan(float u) { return u < 0.0f ? 0.0f : u; }
+// An activation beyond the fp16 range gives main = +-inf and corr = -+inf or NaN, so v is NaN wherever that pixel is
+// read: the epilogue's ReLU is pp_common.h's relu_keeps_nan
 
 // The bare form's tail (include/pp_conv_train.h): y = v * (1/s), s the power of two the stager multiplied x by.
 struct Unscale {

@@ -111,7 +111,7 @@ __global__ __launch_bounds__(kTrWaves * 64) void k_pfn_train_stats(const float *
 #pragma unroll
       for (int d = 0; d < 9; ++d) xv[d] = sx[d][j];
       const float z = tr_z(A, xv);
-      const float r = fmaxf(z, 0.0f);
+      const float r = relu_keeps_nan(z);
       const float mk = z > 0.0f ? 1.0f : 0.0f;
       const double rs = (double)r - (double)c0;  // exactly 0 on a zero-padded slot
       acc[0] += mk;
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(kTrWaves * 64) void k_pfn_train_bwd(
         float xv[9];
 #pragma unroll
         for (int d = 0; d < 9; ++d) xv[d] = sx[d][j];
-        const float r = fmaxf(tr_z(A, xv), 0.0f);
+        const float r = relu_keeps_nan(tr_z(A, xv));
         const bool better = best_n < 0 || (scale >= 0.0f ? r > best : r < best);
         best = better ? r : best;
         best_n = better ? n0 + j : best_n;

@@ -567,9 +567,14 @@ class _PfnTrain(torch.autograd.Function):
         out = _pfn_dense(x, table)
         if running_mean is not None:
             with torch.no_grad():
-                running_mean.mul_(1.0 - momentum).add_(mean.to(running_mean.dtype), alpha=momentum)
+                # a channel whose batch statistics are not finite keeps its running statistics (include/pp_hip.h):
+                # the optimizer drops such a step, and eval() of the model has to work after it.  No host wait.
                 unbiased = var * (M / max(M - 1, 1))
-                running_var.mul_(1.0 - momentum).add_(unbiased.to(running_var.dtype), alpha=momentum)
+                new_mean = running_mean.mul(1.0 - momentum).add_(mean.to(running_mean.dtype), alpha=momentum)
+                new_var = running_var.mul(1.0 - momentum).add_(unbiased.to(running_var.dtype), alpha=momentum)
+                keep = ~(torch.isfinite(new_mean) & torch.isfinite(new_var))     # the values that would be stored
+                running_mean.copy_(torch.where(keep, running_mean, new_mean))
+                running_var.copy_(torch.where(keep, running_var, new_var))
         sums[1] += M * c0                                        # now sum r (the backward's db term)
         ctx.save_for_backward(x, table, mean.float(), invstd.float(), sums)
         ctx.M = M
@@ -888,7 +893,11 @@ class PPDownBlock(nn.Module):
         #: opt-in (``PillarPipeline(with_targets=True, split_train=True)``): in train(), with ``fused_train``, the
         #: stride-1 layers' forward conv and data gradient on the split-fp16 MFMA kernel and their ReLU -> BatchNorm
         #: tail channels-last (``_ConvTrain``, include/pp_conv_train.h) instead of MIOpen's NCHW f32 convolutions;
-        #: the weight gradient stays MIOpen's.  Forward activations with |x| >= 65520 give NaN
+        #: the weight gradient stays MIOpen's.  Forward activations with |x| >= 65520 give NaN; the tail keeps it
+        #: (its ReLU is ``torch.relu``'s), so the step's loss and gradients are NaN and
+        #: ``FusedAdam(skip_nonfinite=True)`` drops it.  Such a step keeps the parameters, the moments and the running
+        #: statistics of every layer whose batch statistics were not finite; not those of the layers before it, nor
+        #: ``num_batches_tracked``
         self.split_train = False
         #: opt-in, with ``split_train`` (``PillarPipeline(..., split_train=True, split_wgrad=True)``): those layers'
         #: weight gradient on the split-fp16 MFMA pipe too, a deterministic split-K kernel on the channels-last

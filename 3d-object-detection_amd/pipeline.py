@@ -53,8 +53,12 @@ class PillarPipeline:
         gradient on the split-fp16 MFMA kernel and their ReLU -> BatchNorm tail channels-last
         (include/pp_conv_train.h) instead of MIOpen's NCHW f32 convolutions; the weight gradient stays MIOpen's.
         Window: forward activations with |x| >= 65520 give NaN.  A stride-1 layer's input is always a BatchNorm
-        output, ``optim.FusedAdam(skip_nonfinite=True)`` drops such a step, and the gradients are rescaled per tensor
-        by a power of two and have no window.  eval() is untouched.
+        output, and the gradients are rescaled per tensor by a power of two and have no window.  The training tails
+        keep that NaN through their ReLU (as ``torch.relu`` does), so the loss and the gradients of such a step are
+        NaN and ``optim.FusedAdam(skip_nonfinite=True)`` drops it, with any of these switches.  A dropped step keeps
+        every parameter, both moments and the running statistics of every layer whose batch statistics were not
+        finite; it does not keep the running statistics of the layers before that one, which are updated as in any
+        step, nor ``num_batches_tracked`` (incremented on the host without a wait).  eval() is untouched.
         ``split_wgrad``: with ``split_train`` only (else a ``ValueError``): those layers' weight gradient too
         (``PPDownBlock.split_wgrad``) runs on the split-fp16 MFMA pipe, a deterministic split-K kernel on the
         channels-last tensors as they lie (include/train/pp_conv_wgrad.h), with the data gradient's power-of-two scale

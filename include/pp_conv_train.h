@@ -58,6 +58,11 @@
  *             backward also returns dbias_dev = sum dz (may be NULL).
  *   Sums are taken about a provisional per-channel value sampled from the channel; partial sums are f64; no atomics
  *   and a fixed order: bit-identical from call to call.
+ *   Non-finite input, pp_hip.h's two rules: the ReLU is u < 0 ? 0 : u, so the NaN that the bare conv writes on purpose
+ *   outside its window stays a NaN here (that channel's mean_out / invstd_out are not finite, its y is NaN, and the
+ *   backward gives NaN dgamma, dbias and, where z + bias > 0, dz); and a channel whose batch mean or variance is not
+ *   finite keeps running_mean and running_var.  A step that left the window thus reaches the optimizer with NaN
+ *   gradients, whichever kernel computes the weight gradient, and FusedAdam(skip_nonfinite=True) drops it.
  */
 #ifndef PP_CONV_TRAIN_H
 #define PP_CONV_TRAIN_H

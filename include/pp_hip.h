@@ -217,6 +217,10 @@ int pp_scatter_canvas_dev(pp_ctx_t *ctx, void *stream, const float *features_dev
  *                   variance), S1[d] = sum_{z>0} x_d (9 rows), S2[d] = sum r*x_d (9 rows),
  *                   over all batch*P*N slots
  * The forward output is then pp_pfn_dense_dev with scale/shift from the batch statistics.
+ * r is torch.relu's (z < 0 ? 0 : z): a NaN in the pillars makes rows 1 and 2 NaN in every
+ * column, a NaN in a row of weight_bias_dev in that channel's column alone; c0 = max(bias, 0) is
+ * taken of a parameter.  The caller keeps the running statistics of a channel whose derived mean
+ * or variance is not finite, as pp_relu_bn_train_fwd_dev does.
  */
 int pp_pfn_train_stats_dev(pp_ctx_t *ctx, void *stream, const float *pillars_dev, int batch,
                            int max_pillars, int max_points_per_pillar, const float *weight_bias_dev,
@@ -733,6 +737,21 @@ int pp_head1x1_nhwc_dev(pp_ctx_t *ctx, void *stream, int64_t pixels, int n_src,
  *             tensor (the gradient of one input of torch.cat), read in place
  *   conv_bias_dev [channels] or NULL: z is then the convolution WITHOUT its bias, the kernels
  *             use z + bias, and the backward also returns dbias_dev = sum dz (may be NULL)
+ * Non-finite input, two rules (tests/test_gpu_bn_train_nonfinite.py):
+ *   The ReLU is torch.relu's, u < 0 ? 0 : u, in both directions: a NaN stays a NaN (fmaxf would
+ *             return the 0), +inf stays +inf, -inf becomes 0.  A NaN or +inf in a channel makes
+ *             mean_out and invstd_out of that channel non-finite and every y of it NaN; the
+ *             backward on those statistics gives NaN dgamma and dbias, and dz NaN where
+ *             z + bias > 0 (0 where it is <= 0: the strict mask).  No other channel changes.
+ *   A channel whose batch mean or variance is not finite KEEPS running_mean and running_var:
+ *             (1 - momentum)*NaN would stay NaN for good, and the model of a step that the
+ *             optimizer dropped has to evaluate afterwards.  mean_out / invstd_out stay non-finite.
+ *             The test is made on the two f32 values that would be stored, so a finite f64
+ *             statistic beyond FLT_MAX is kept out as well: these kernels never store a
+ *             non-finite running statistic over a finite one.
+ *   What a dropped step does not keep is outside these kernels: the layers ahead of the bad one
+ *             saw ordinary statistics and update theirs, and the caller's num_batches_tracked
+ *             (model.py increments it on the host, without a wait, at every call) may advance.
  */
 int pp_relu_bn_train_fwd_dev(pp_ctx_t *ctx, void *stream, const float *z_dev,
                              const float *conv_bias_dev, int64_t batch, int channels, int64_t hw,

@@ -104,6 +104,54 @@ def test_bn_train_reference_is_autograd_f64():
     assert np.array_equal(one["rv"], [0.5, 0.5]) and np.array_equal(one["rm"], [0.5, 0.5])
 
 
+def test_bn_train_reference_on_non_finite_input_is_autograd_f64_but_for_the_running_statistics():
+    """One NaN, +inf or -inf in z: ``bn_train_ref`` has the NaN sets of f64 batch_norm(relu(z + b)) + autograd in
+    every output and its values everywhere else.  Only the running statistics differ, and only in the bad channel:
+    PyTorch makes them NaN for good, the reference (the kernels' rule, include/pp_hip.h) keeps the caller's."""
+    rng = np.random.default_rng(5)
+    shape, c = (3, 4, 35), 2
+    for value in (np.nan, np.inf, -np.inf):
+        for b, i in ((0, 0), (2, 34), (1, 17)):
+            p = T._params(rng, shape[1])
+            z, dy = T._well_conditioned(rng, shape)
+            z[b, c, i] = value
+            with np.errstate(invalid="ignore"):
+                ref = T.bn_train_ref(z, p["bias"], p["gamma"], p["beta"], T.EPS, T.MOMENTUM, p["rm"], p["rv"], dy)
+            t = lambda v, g=False: torch.from_numpy(np.asarray(v, np.float64)).requires_grad_(g)   # noqa: E731
+            zt, gamma, beta, bias = t(z, True), t(p["gamma"], True), t(p["beta"], True), t(p["bias"], True)
+            rm, rv = t(p["rm"]), t(p["rv"])
+            r = torch.relu(zt + bias[None, :, None])
+            y = torch.nn.functional.batch_norm(r, rm, rv, gamma, beta, True, T.MOMENTUM, T.EPS)
+            y.backward(t(dy))
+            var, mean = torch.var_mean(r.detach(), (0, 2), unbiased=False)
+            want = dict(y=y.detach(), mean=mean, invstd=torch.rsqrt(var + T.EPS), dz=zt.grad, dgamma=gamma.grad,
+                        dbeta=beta.grad, dbias=bias.grad)
+            loud = value != -np.inf                       # the ReLU makes -inf a 0: everything stays finite
+            for k, v in want.items():
+                v = v.numpy()
+                if k == "dz":                             # at the bad element itself the gradient is not specified
+                    v, mine = v.copy(), ref[k].copy()
+                    v[b, c, i] = mine[b, c, i] = 0.0
+                else:
+                    mine = ref[k]
+                # non-finite, not NaN: the mean of a channel with a +inf is +inf here and NaN in var_mean's recurrence
+                assert np.array_equal(~np.isfinite(mine), ~np.isfinite(v)), (value, k)
+                ok = np.isfinite(v)
+                assert np.abs(mine[ok] - v[ok]).max() <= 1e-11 * max(1.0, np.abs(v[ok]).max()), (value, k)
+                if k in ("y", "invstd", "dgamma", "dbias"):
+                    assert np.isnan(v[:, c] if k == "y" else v[c]).all() == loud, (value, k)
+                    assert np.isnan(mine[:, c] if k == "y" else mine[c]).all() == loud, (value, k)
+            # the running statistics: the bad channel keeps the caller's bits, where PyTorch's are NaN from then on
+            others = np.arange(shape[1]) != c
+            for k, mine, theirs, start in (("rm", ref["rm"], rm.numpy(), p["rm"]),
+                                           ("rv", ref["rv"], rv.numpy(), p["rv"])):
+                assert np.abs(mine[others] - theirs[others]).max() <= 1e-11, (value, k)
+                if loud:
+                    assert not np.isfinite(theirs[c]) and mine[c] == np.float64(start[c]), (value, k)
+                else:
+                    assert abs(mine[c] - theirs[c]) <= 1e-11, (value, k)
+
+
 def test_pfn_train_references_are_autograd_f64():
     """The 21 + 12 rows, combined as include/pp_hip.h says the caller combines them, give the gradients autograd
     finds for conv -> ReLU -> BatchNorm (batch statistics) -> max over the points."""

@@ -78,12 +78,16 @@ def bn_train_ref(z, bias, gamma, beta, eps, momentum, rm, rv, dy):
     invstd = 1.0 / np.sqrt(var + eps)
     xhat = (r - col(mean)) * col(invstd)
     out = {"y": col(gamma) * xhat + col(beta), "mean": mean, "invstd": invstd}
-    if rm is not None:
-        unbiased = var * (M / (M - 1.0)) if M > 1 else var
-        out["rm"] = (1.0 - momentum) * rm + momentum * mean
-        out["rv"] = (1.0 - momentum) * rv + momentum * unbiased
+    if rm is not None:           # a channel whose batch mean or variance is not finite keeps its running statistics:
+        unbiased = var * (M / (M - 1.0)) if M > 1 else var          # ... tested on the f32 values that would be stored
+        new_rm, new_rv = (1.0 - momentum) * rm + momentum * mean, (1.0 - momentum) * rv + momentum * unbiased
+        with np.errstate(over="ignore", invalid="ignore"):
+            keep = ~(np.isfinite(new_rm.astype(np.float32)) & np.isfinite(new_rv.astype(np.float32)))
+        out["rm"] = np.where(keep, rm, new_rm)
+        out["rv"] = np.where(keep, rv, new_rv)
     dbeta, dgamma = dy.sum((0, 2)), (dy * xhat).sum((0, 2))
-    dz = (a > 0.0) * col(gamma * invstd) * (dy - col(dbeta) / M - xhat * col(dgamma) / M)
+    # where, not a product with the mask: a clamped element's gradient is 0 in a channel whose statistics are NaN too
+    dz = np.where(a > 0.0, col(gamma * invstd) * (dy - col(dbeta) / M - xhat * col(dgamma) / M), 0.0)
     out.update(dz=dz, dgamma=dgamma, dbeta=dbeta)
     if bias is not None:
         out["dbias"] = dz.sum((0, 2))
@@ -130,7 +134,8 @@ def run_hip(gpu, z, p, dy, offset=0, dy_extra=0, running=True, want_dbias=True):
         out[key] = h[offset:offset + n].reshape(B, C, hw).astype(np.float64)
         rest = np.concatenate([h[:offset], h[offset + n:]])
         assert (rest == np.float32(-777.25)).all(), f"{key}: wrote outside the tensor"
-    assert np.array_equal(zb.cpu().numpy()[offset:offset + n], z.ravel()), "z changed"
+    assert np.array_equal(zb.cpu().numpy()[offset:offset + n].view(np.uint32),          # by bits: z may hold a NaN
+                          np.ascontiguousarray(z, np.float32).ravel().view(np.uint32)), "z changed"
     for key, t in (("mean", mean), ("invstd", invstd), ("rm", rm), ("rv", rv), ("dgamma", dgamma), ("dbeta", dbeta),
                    ("dbias", dbias)):
         if t is not None:

@@ -64,7 +64,8 @@ def run_nhwc(gpu, z, p, dy, running=True, want_dbias=True):
         h = t.cpu().numpy()
         out[key] = h[GUARD:GUARD + n].reshape(B, hw, C).transpose(0, 2, 1).astype(np.float64)
         assert (np.concatenate([h[:GUARD], h[GUARD + n:]]) == np.float32(FILL)).all(), f"{key}: wrote outside"
-    assert np.array_equal(zb.cpu().numpy()[GUARD:GUARD + n].reshape(B, hw, C).transpose(0, 2, 1), z), "z changed"
+    z_nhwc = np.ascontiguousarray(np.asarray(z, np.float32).transpose(0, 2, 1)).ravel()
+    assert np.array_equal(zb.cpu().numpy()[GUARD:GUARD + n].view(np.uint32), z_nhwc.view(np.uint32)), "z changed"  # bits: NaN
     for key, t in (("mean", mean), ("invstd", invstd), ("rm", rm), ("rv", rv), ("dgamma", dgamma), ("dbeta", dbeta),
                    ("dbias", dbias)):
         if t is not None:
